@@ -1,20 +1,26 @@
 """bench.py — headline benchmark: MojoPagedDecodeGQA, Llama-3-8B shape, on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A *step* is one pass of the hot path over one batch: paged decode attention for B=64 sequences
 (32 q heads / 8 kv heads, head_dim 128, page 16, bf16, ctx 4096 each, block tables a random
 permutation) with all inputs resident in HBM.  ``value`` = tokens/s = B * steps / time, whole job.
 With N > 1 every rank runs its own batch (the op has no exchange step: replicas, weak scaling).
+The inputs are drawn from fixed seeds: the same arguments give the same inputs on every run.
+
+A plain run sets up, settles and warms up the device, times the K steps and prints the result line; nothing else.
+``--dump-outputs DIR`` then writes what the last timed step returned as ``DIR/<name>.npy`` (float32, rank 0), so
+that two builds can be compared output for output.  ``--full`` adds everything else the benchmark measures.
 
 Output (benchmarks/result_line.py):
   LAST stdout line — compact JSON (<= 4 KB, asserted): the contract fields + ``roofline`` (HBM roofline of the
-                 decode op from HIP-event time of the timed region), ``cpu_baseline`` (the torch-native oracle, a port
-                 of the reference's golden backend, timed on the host cores on a bounded sample of the same
-                 workload) and a six-key ``roofline_group_gemm``.
-  an EARLIER line ``EXTRAS {...}`` and ``bench_extras.json`` — everything else measured in the same run: the other
-                 hot-path ops (absolute rate + roofline fraction), per-op CPU baselines, GEMM + collective cases.
+                 decode op from HIP-event time of the timed region).  With ``--full`` also ``cpu_baseline`` (the
+                 torch-native oracle, a port of the reference's golden backend, timed on the host cores on a bounded
+                 sample of the same workload), a six-key ``roofline_group_gemm`` and, with N > 1, a ``comm`` block.
+  with ``--full``, an EARLIER line ``EXTRAS {...}`` and ``bench_extras.json`` — everything else measured in the same
+                 run: the other hot-path ops (absolute rate + roofline fraction), per-op CPU baselines, GEMM +
+                 collective cases.
 """
 import argparse
 import json
@@ -77,17 +83,27 @@ import torch  # noqa: E402
 
 def build_decode_inputs(device, ctx=CTX, batch=B, seed=20260716, sets=2):
     g = torch.Generator().manual_seed(seed)
+    g_dev = torch.Generator(device=device).manual_seed(seed)     # the caches are drawn where they live (1 GB per set)
     pages_per_seq = ctx // PAGE
     n_pages = batch * pages_per_seq + 10
     out = []
     for s in range(sets):
         q = torch.randn(batch, HQ, D, generator=g).to(torch.bfloat16).to(device)
-        k = torch.randn(n_pages, HKV, PAGE, D, device=device, dtype=torch.bfloat16)
-        v = torch.randn(n_pages, HKV, PAGE, D, device=device, dtype=torch.bfloat16)
+        k = torch.randn(n_pages, HKV, PAGE, D, device=device, dtype=torch.bfloat16, generator=g_dev)
+        v = torch.randn(n_pages, HKV, PAGE, D, device=device, dtype=torch.bfloat16, generator=g_dev)
         table = torch.randperm(n_pages, generator=g, dtype=torch.int32)[: batch * pages_per_seq].view(batch, -1)
         lens = torch.full((batch,), ctx, dtype=torch.int32)
         out.append((q, k, v, lens.to(device), table.to(device)))
     return out
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs``: every array as ``<out_dir>/<name>.npy`` in float32."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
 
 
 def decode_algorithmic_bytes(lens, max_blocks):
@@ -269,10 +285,16 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--settle-ms", type=float, default=300.0, help="untimed device settle time before the warmup steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the output of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extras (other ops and configs, GEMM + collective cases), the CPU baselines "
+                         "and, with N > 1, the comm block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
     ap.add_argument("--extras-deadline", type=float, default=900.0, help="seconds before the extras are abandoned")
     ns = ap.parse_args()
+    if ns.steps < 1 or ns.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if ns.gpus != world:
@@ -324,8 +346,9 @@ def main():
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()
-    for i in range(ns.steps):
+    for i in range(ns.steps - 1):
         step(i)
+    out = step(ns.steps - 1)                # what --dump-outputs writes
     ev1.record()
     torch.cuda.synchronize()
     if dist_on:
@@ -337,6 +360,8 @@ def main():
         t = torch.tensor([wall], dtype=torch.float64, device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if ns.dump_outputs and rank == 0:
+        dump_outputs(ns.dump_outputs, {"paged_decode_gqa_out": out})
 
     lens_cpu = sets[0][3].cpu()
     alg_bytes = decode_algorithmic_bytes(lens_cpu, sets[0][4].shape[1])
@@ -376,7 +401,7 @@ def main():
                      "algorithmic_bytes_per_launch": alg_bytes, "device_us_per_launch": kernel_s * 1e6,
                      "kernel": _headline_kernel()},
     }
-    if dist_on:                     # what the collective library itself reports: a SCALE line must describe its own fabric
+    if dist_on and ns.full:         # what the collective library itself reports: a SCALE line must describe its own fabric
         try:
             names = [None] * world
             dist.all_gather_object(names, f"{torch.cuda.get_device_name(device)} (device {device.index})")
@@ -388,7 +413,7 @@ def main():
         except Exception as e:
             line["comm"] = {"error": repr(e)}
     hung = False
-    if not ns.no_extras:            # every rank takes part: the GEMM + collective cases contain collectives
+    if ns.full and not ns.no_extras:    # every rank takes part: the GEMM + collective cases contain collectives
         # Extras run under a deadline in a worker thread: a collective that one rank never enters (an exception on a
         # peer, a fabric problem) must not take the headline line down with it.
         box = {}
@@ -493,23 +518,27 @@ def main():
         gg.update({"target": 0.80, "ceiling_at_sustained_clock": None if not clk else clk / 2400.0,
                    "note": "target 0.80 of the nominal 2.5 PF is formally missed: at the clock the chip holds under this load "
                            "a 100 % busy matrix pipe would deliver `ceiling_at_sustained_clock` of the nominal peak"})
-    try:
-        from mojo_opset_amd import switches
-        line["switches_set"] = {k: v for k, v in switches.in_effect().items() if v is not None}     # which build / route produced the numbers
-        from mojo_opset_amd.backends.hip import lib as _lib
-        line["library"] = _lib.load().mojo_hip_version().decode()
-    except Exception as e:
-        line["switches_set"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not ns.no_cpu_baseline:
+    if ns.full:
+        try:
+            from mojo_opset_amd import switches
+            line["switches_set"] = {k: v for k, v in switches.in_effect().items() if v is not None}     # which build / route produced the numbers
+            from mojo_opset_amd.backends.hip import lib as _lib
+            line["library"] = _lib.load().mojo_hip_version().decode()
+        except Exception as e:
+            line["switches_set"] = {"error": repr(e)}
+    if ns.full and rank == 0 and world == 1 and not ns.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()
         if not ns.no_extras:
             line["cpu_baseline_per_op"] = cpu_baselines_per_op()
     if rank == 0:                   # the line goes out before any further collective can get in its way
-        from benchmarks.result_line import emit
+        from benchmarks.result_line import compact_line, emit
 
-        # everything measured -> bench_extras.json + an `EXTRAS ` stdout line; the LAST stdout line is the compact
-        # (<= 4 KB) contract line the driver parses
-        emit(line)
+        # --full: everything measured -> bench_extras.json + an `EXTRAS ` stdout line; the LAST stdout line is always
+        # the compact (<= 4 KB) contract line the driver parses
+        if ns.full:
+            emit(line)
+        else:
+            print(compact_line(line), flush=True)
     if dist_on and not hung:
         closer = threading.Thread(target=lambda: (dist.barrier(), dist.destroy_process_group()), daemon=True)
         closer.start()

@@ -89,7 +89,7 @@ def test_oversized_or_incomplete_records_degrade_to_a_parseable_line(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_last_line_parses_on_the_gpu_box():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-extras"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-extras"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     last = p.stdout.strip().splitlines()[-1]
@@ -98,6 +98,43 @@ def test_bench_last_line_parses_on_the_gpu_box():
     assert rec["steps"] == 5 and rec["warmup"] == 2 and rec["n_gpus"] == 1
     assert rec["value"] > 0 and 0 < rec["roofline"]["frac"] < 1
     assert rec["cpu_baseline"]["value"] > 0 and rec["cpu_baseline"]["kind"] == "port"
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain run prints the contract line only (no EXTRAS line, no CPU baseline) and ``--dump-outputs`` writes the last
+    step's output; two runs with the same arguments see the same inputs, so they dump the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out_dir)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = p.stdout.strip().splitlines()
+        assert not any(ln.startswith("EXTRAS ") for ln in lines)
+        rec = json.loads(lines[-1])
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and "cpu_baseline" not in rec
+        assert rec["value"] == pytest.approx(64 * 1e3 / rec["ms_per_step"], rel=1e-3)
+        assert sorted(os.listdir(out_dir)) == ["paged_decode_gqa_out.npy"]
+        dumps.append(np.load(out_dir / "paged_decode_gqa_out.npy"))
+    assert dumps[0].shape == (64, 32, 128) and dumps[0].dtype == np.float32 and np.isfinite(dumps[0]).all()
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+    # the dump is the op's output on the inputs of the last step (step 2 -> set 0): two sequences against the oracle
+    import math
+
+    import torch
+
+    import bench
+    import mojo_opset_amd as mo
+    import oracle  # noqa: F401
+
+    (q, k, v, lens, table), = bench.build_decode_inputs("cuda", sets=1)
+    rows = [0, 63]
+    ref = mo.MojoPagedDecodeGQA.get_backend_impl("torch", strict=True)(is_causal=True, gqa_layout="AABB")
+    want = ref(q[rows].cpu(), k.cpu(), v.cpu(), lens[rows].cpu(), table[rows].cpu(), softmax_scale=1 / math.sqrt(128))
+    torch.testing.assert_close(torch.from_numpy(dumps[0][rows]), want.float(), atol=2e-2, rtol=2e-2)
 
 
 @pytest.mark.parametrize("world,full", [(1, False), (2, False), (8, False), (8, True)])
