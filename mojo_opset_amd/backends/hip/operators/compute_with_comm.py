@@ -7,6 +7,7 @@ from ....comm import peer, select
 from ....core.operators.compute_with_comm import (MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce,
                                                   MojoGemmReduceScatter, is_dist_initialized)
 from .. import lib as L
+from .gemm import weight_strides
 
 _ROCM = ["rocm"]
 
@@ -18,16 +19,7 @@ class HipGemmEngine(GemmEngine):
         L.require_cuda(x, weight, bias, out)
         if weight.dim() != 2 or x.dtype != weight.dtype or (bias is not None and bias.dtype != x.dtype):
             raise NotImplementedError("hip gemm: 2-D weight and one common dtype required")
-        k = x.shape[-1]
-        if trans_weight:
-            assert weight.shape[0] == k, "input K must match weight K"
-            n = weight.shape[1]
-        else:
-            assert weight.shape[1] == k, "input K must match weight K"
-            n = weight.shape[0]
-        if weight.stride(0) != 1 and weight.stride(1) != 1:
-            weight = weight.contiguous()
-        w_k, w_n = (weight.stride(0), weight.stride(1)) if trans_weight else (weight.stride(1), weight.stride(0))
+        weight, k, n, w_k, w_n = weight_strides(x, weight, trans_weight)
         if x.stride(-1) != 1:
             x = x.contiguous()
         rows = x.shape[0] if rows is None else rows

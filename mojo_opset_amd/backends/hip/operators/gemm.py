@@ -8,22 +8,26 @@ from .. import lib as L
 _ROCM = ["rocm"]
 
 
+def weight_strides(x: torch.Tensor, weight: torch.Tensor, trans_weight: bool):
+    """``(weight, k, n, w_k, w_n)`` of the 2-D ``weight`` of ``x @ W``: ``[K,N]`` (trans_weight) or ``[N,K]`` (F.linear layout),
+    element ``(k, n)`` at ``k * w_k + n * w_n``.  A weight strided along both dimensions is made contiguous.  The C side reads
+    the bias rounding from the layout: ``w_k == 1`` is F.linear's (bias in the accumulator, one rounding)."""
+    k = x.shape[-1]
+    assert (weight.shape[0] if trans_weight else weight.shape[1]) == k, "input K must match weight K"
+    n = weight.shape[1] if trans_weight else weight.shape[0]
+    if weight.stride(0) != 1 and weight.stride(1) != 1:
+        weight = weight.contiguous()
+    w_k, w_n = (weight.stride(0), weight.stride(1)) if trans_weight else (weight.stride(1), weight.stride(0))
+    return weight, k, n, w_k, w_n
+
+
 def dense_gemm(x: torch.Tensor, weight: torch.Tensor, bias, trans_weight: bool) -> torch.Tensor:
     """``x @ weight (+ bias)`` for ``weight [K,N]`` (trans_weight) or ``[N,K]`` (F.linear layout) through
     `mojo_hip_gemm`; leading dimensions of ``x`` are flattened.  Shared by the GEMM+collective ops."""
     L.require_cuda(x, weight, bias)
     if weight.dim() != 2 or x.dtype != weight.dtype or (bias is not None and bias.dtype != x.dtype):
         raise NotImplementedError("hip gemm: 2-D weight and one common dtype required")
-    k = x.shape[-1]
-    if trans_weight:
-        assert weight.shape[0] == k, "input K must match weight K"
-        n = weight.shape[1]
-    else:
-        assert weight.shape[1] == k, "input K must match weight K"
-        n = weight.shape[0]
-    if weight.stride(0) != 1 and weight.stride(1) != 1:
-        weight = weight.contiguous()
-    w_k, w_n = (weight.stride(0), weight.stride(1)) if trans_weight else (weight.stride(1), weight.stride(0))
+    weight, k, n, w_k, w_n = weight_strides(x, weight, trans_weight)
     x2 = x.reshape(-1, k)
     if x2.stride(1) != 1:
         x2 = x2.contiguous()
@@ -70,12 +74,7 @@ def dense_gemm_residual_rmsnorm(x: torch.Tensor, weight: torch.Tensor, bias, res
     L.require_cuda(x, weight, bias, residual, norm_weight)
     if weight.dim() != 2 or x.dtype != weight.dtype or x.dtype not in (torch.bfloat16, torch.float16):
         raise NotImplementedError("hip gemm_residual_rmsnorm: 2-D weight and one 16-bit dtype required")
-    k = x.shape[-1]
-    n = weight.shape[1] if trans_weight else weight.shape[0]
-    assert (weight.shape[0] if trans_weight else weight.shape[1]) == k, "input K must match weight K"
-    if weight.stride(0) != 1 and weight.stride(1) != 1:
-        weight = weight.contiguous()
-    w_k, w_n = (weight.stride(0), weight.stride(1)) if trans_weight else (weight.stride(1), weight.stride(0))
+    weight, k, n, w_k, w_n = weight_strides(x, weight, trans_weight)
     x2 = x.reshape(-1, k)
     if x2.stride(1) != 1:
         x2 = x2.contiguous()

@@ -105,7 +105,20 @@ bool gemm_mfma256_glu_ok(const GemmArgs& a, int dtype);
 bool gemm_skinny_ok(const GemmArgs& a, int dtype);
 int gemm_skinny_splitk(int64_t m, int64_t k, int64_t n, int64_t groups);
 int launch_gemm_skinny(const GemmArgs& a, int dtype, hipStream_t s);
-bool gemm_rows128_takes_tile128(const GemmArgs& a, int dtype, int64_t m, int64_t k, int64_t n, int* splitk128);   // gemm_api.hip: mojo_hip_gemm's route for at most 128 rows of [N,K] weights
+
+// The route mojo_hip_gemm takes for one dense product (G = 1, uniform rows, no split set in `a`) and the K split it uses; a split's
+// slabs live at workspace + 64 (gemm_api.hip).  The fused callers plan with the arguments of the mojo_hip_gemm call they replace.
+struct DensePlan {
+  enum Route { DEFAULT,      // run_gemm's own chain (weight stream unsplit, 256 x 256 tiles unsplit, generic)
+               TILES128,     // 128-row tiles (gemm_tile128.hip), split: + launch_gemm_splitk_finalize
+               STREAM,       // the weight-streaming kernel cut along K (splitk > 1)
+               TILES256      // the 256 x 256 kernel cut along K (splitk > 1) + launch_gemm_splitk_finalize
+  } route = DEFAULT;
+  int splitk = 1;
+  bool rows128 = false;      // TILES128 from the at-most-128-rows rule (against the weight stream), not the mid-M model
+};
+DensePlan plan_dense_gemm(const GemmArgs& a, int dtype, int64_t m, const void* workspace, int64_t workspace_bytes);
+
 int launch_gemm_splitk_finalize(const GemmArgs& a, int dtype, int64_t m_total, hipStream_t s);   // C = round(sum of the fp32 K-slice slabs) (+ bias)
 bool gemm_skinny_glu_ok(const GemmArgs& a, int dtype);                            // dense, <= 64 rows, W = [gate | up] rows: SwiGLU in the epilogue
 int launch_gemm_skinny_glu(const GemmArgs& a, int dtype, hipStream_t s);

@@ -278,12 +278,32 @@ static bool gemm_rows128_prefers_tile128(int64_t m, int64_t k, int64_t n, int* s
   return t128 < t_stream;
 }
 
-// (for the fused callers outside this file that must take mojo_hip_gemm's route: qkv_fused.hip)
-bool mojo::gemm_rows128_takes_tile128(const GemmArgs& a, int dtype, int64_t m, int64_t k, int64_t n, int* splitk128) {
-  *splitk128 = 1;
-  if (!(a.w_k == 1 && m <= 128 && (dtype == MOJO_BF16 || dtype == MOJO_F16) && k % 64 == 0)) return false;
-  const bool prefers = gemm_rows128_prefers_tile128(m, k, n, splitk128);
-  return gemm_tile128_use(a, dtype, m, prefers);
+// mojo_hip_gemm's route (gemm.h: DensePlan).  Tried in order: the 128-row tiles for at most 128 rows of [N,K] weights where
+// they model under the weight stream; the weight stream's K split; the 128-row tiles from the mid-M model; the 256 x 256 kernel's
+// split.  A split is taken only where the workspace holds its slabs (64 bytes of header, sk x m x n fp32, 16-byte aligned).
+DensePlan mojo::plan_dense_gemm(const GemmArgs& a, int dtype, int64_t m, const void* workspace, int64_t workspace_bytes) {
+  const int64_t k = a.K, n = a.N;
+  const bool half = dtype == MOJO_BF16 || dtype == MOJO_F16;
+  auto fits = [&](int sk) { return sk > 1 && workspace_bytes >= 64 + static_cast<int64_t>(sk) * m * n * 4 && aligned_to(workspace, 16); };
+  auto tiles128 = [&](int sk128, bool rows128) { return DensePlan{DensePlan::TILES128, fits(sk128) ? sk128 : 1, rows128}; };
+  int sk128 = 1;
+  if (a.w_k == 1 && m <= 128 && half && k % 64 == 0 && gemm_tile128_use(a, dtype, m, gemm_rows128_prefers_tile128(m, k, n, &sk128)))
+    return tiles128(sk128, true);
+  if (a.w_k == 1 && half) {                              // decode-sized, K-major weights: maybe split K
+    GemmArgs t = a;
+    t.splitk = gemm_skinny_splitk(m, k, n, 1);
+    t.slab = static_cast<char*>(const_cast<void*>(workspace)) + 64;
+    if (fits(t.splitk) && gemm_skinny_ok(t, dtype)) return DensePlan{DensePlan::STREAM, t.splitk};
+  }
+  if (!half || gemm_skinny_ok(a, dtype)) return DensePlan{};
+  // (up to 64 rows of [N,K] weights the weight stream cannot take — N % 64: the 256 kernel, whose unsplit bits the fused decode forms share)
+  if (k % 64 == 0 && (m > 64 || a.w_k != 1) && gemm_tile128_use(a, dtype, m, gemm_dense_prefers_tile128(m, k, n, a.w_n == 1, &sk128)))
+    return tiles128(sk128, false);
+  if (gemm_mfma256_ok(a, dtype)) {                       // few output tiles: cut K, sum the slices in a second launch
+    const int sk = gemm_dense_splitk256(m, k, n);
+    if (fits(sk)) return DensePlan{DensePlan::TILES256, sk};
+  }
+  return DensePlan{};
 }
 
 extern "C" int64_t mojo_hip_gemm_workspace_bytes(int64_t m, int64_t k, int64_t n) {
@@ -324,41 +344,16 @@ extern "C" int mojo_hip_gemm_rowmap(const void* input, const void* weight, const
   a.row_start = ws; a.tile_start = ws + 2;
   hipStream_t s = static_cast<hipStream_t>(stream);
   a.uniform_rows = static_cast<int>(m);
-  auto take_split128 = [&](int sk128) {                  // the 128-row tiles' own K split, if the workspace holds its slabs
-    if (sk128 > 1 && workspace_bytes >= 64 + static_cast<int64_t>(sk128) * m * n * 4 && aligned_to(workspace, 16)) {
-      a.splitk = sk128; a.slab = static_cast<char*>(workspace) + 64; a.slab_rows = static_cast<int>(m);
-    }
-  };
-  if (int sk128 = 1; gemm_rows128_takes_tile128(a, dtype, m, k, n, &sk128)) {
-    take_split128(sk128);
-    return launch_gemm_tile128(a, dtype, m, s);
-  }
-  if (w_k_stride == 1 && (dtype == MOJO_BF16 || dtype == MOJO_F16)) {          // decode-sized, K-major weights: maybe split K
-    const int sk = gemm_skinny_splitk(m, k, n, 1);
-    if (sk > 1 && workspace_bytes >= 64 + static_cast<int64_t>(sk) * m * n * 4 && aligned_to(workspace, 16)) {
-      a.splitk = sk; a.slab = static_cast<char*>(workspace) + 64; a.slab_rows = static_cast<int>(m);
-      if (!gemm_skinny_ok(a, dtype)) { a.splitk = 1; a.slab = nullptr; }
-    }
-  }
-  // (up to 64 rows of [N,K] weights the weight stream cannot take — N % 64: the 256 kernel, whose unsplit bits the fused decode forms share)
-  if (a.splitk == 1 && !gemm_skinny_ok(a, dtype) && (dtype == MOJO_BF16 || dtype == MOJO_F16) && k % 64 == 0 && (m > 64 || w_k_stride != 1)) {
-    int sk128 = 1;
-    const bool prefers = gemm_dense_prefers_tile128(m, k, n, w_n_stride == 1, &sk128);
-    if (gemm_tile128_use(a, dtype, m, prefers)) {
-      take_split128(sk128);
-      return launch_gemm_tile128(a, dtype, m, s);      // (split: + launch_gemm_splitk_finalize)
-    }
-  }
-  if (a.splitk == 1 && (dtype == MOJO_BF16 || dtype == MOJO_F16) && !gemm_skinny_ok(a, dtype) && gemm_mfma256_ok(a, dtype)) {
-    const int sk = gemm_dense_splitk256(m, k, n);       // few output tiles: cut K, sum the slices in a second launch
-    if (sk > 1 && workspace_bytes >= 64 + static_cast<int64_t>(sk) * m * n * 4 && aligned_to(workspace, 16)) {
-      a.splitk = sk; a.slab = static_cast<char*>(workspace) + 64; a.slab_rows = static_cast<int>(m);
+  const DensePlan plan = plan_dense_gemm(a, dtype, m, workspace, workspace_bytes);
+  if (plan.splitk > 1) { a.splitk = plan.splitk; a.slab = static_cast<char*>(workspace) + 64; a.slab_rows = static_cast<int>(m); }
+  switch (plan.route) {
+    case DensePlan::TILES128: return launch_gemm_tile128(a, dtype, m, s);      // (split: + launch_gemm_splitk_finalize)
+    case DensePlan::TILES256: {
       const int rc = launch_gemm_mfma256(a, dtype, m, s);
-      if (rc) return rc;
-      return launch_gemm_splitk_finalize(a, dtype, m, s);
+      return rc ? rc : launch_gemm_splitk_finalize(a, dtype, m, s);
     }
+    default: return run_gemm(a, dtype, m, s);          // (STREAM: the split is set, run_gemm's first choice takes it)
   }
-  return run_gemm(a, dtype, m, s);
 }
 
 extern "C" int mojo_hip_gemm(const void* input, const void* weight, const void* bias, void* out, int64_t m, int64_t k,
@@ -437,56 +432,25 @@ extern "C" int mojo_hip_gemm_residual_rmsnorm(const void* input, const void* wei
   char* ws2 = prod + m * n * 2;
   ws2 += (16 - (reinterpret_cast<uintptr_t>(ws2) & 15)) & 15;
   const int64_t ws2_bytes = workspace_bytes - (ws2 - static_cast<char*>(workspace));
-  // A split product's slabs go straight into the norm (the finalize launch IS the norm).  The plan below is mojo_hip_gemm's own,
-  // step for step, so the fused form and the separate calls add the same slices in the same order (same bits).
-  GemmArgs a;
-  a.A = input; a.W = weight; a.C = gemm_out; a.bias = bias;
+  void* p = gemm_out ? gemm_out : static_cast<void*>(prod);
+  GemmArgs a;                                            // the arguments of the separate mojo_hip_gemm call
+  a.A = input; a.W = weight; a.C = p; a.bias = bias;
   a.bias_fused = (bias && w_k_stride == 1) ? 1 : 0;                      // [N,K]: F.linear semantics, as mojo_hip_gemm
   a.lda = lda; a.ldc = n; a.w_group = 0; a.w_k = w_k_stride; a.w_n = w_n_stride;
   a.K = static_cast<int>(k); a.N = static_cast<int>(n); a.G = 1;
   a.row_start = nullptr; a.tile_start = nullptr;
   a.uniform_rows = static_cast<int>(m);
-  auto slabs = [&](int sk) {
-    if (sk <= 1 || ws2_bytes < 64 + static_cast<int64_t>(sk) * m * n * 4) return false;
-    a.splitk = sk; a.slab = ws2 + 64; a.slab_rows = static_cast<int>(m); a.defer_finalize = 1;
-    return true;
-  };
-  auto unsplit = [&]() { a.splitk = 1; a.slab = nullptr; a.defer_finalize = 0; };
-  auto tiles128_into_norm = [&](int sk128) -> int {     // 1 = launched, 0 = not this way, < 0 = error code
-    if (!slabs(sk128)) return 0;
-    if (!gemm_tile128_group_ok(a, dtype) || !gemm_splitk_resnorm_ok(a, dtype, residual, norm_weight, normed_out, sum_out)) { unsplit(); return 0; }
-    int rc = launch_gemm_tile128(a, dtype, m, s);
-    if (!rc) rc = launch_gemm_splitk_resnorm(a, dtype, m, residual, norm_weight, normed_out, sum_out, eps, s);
-    return rc ? rc : 1;
-  };
-  bool planned = false;                                  // true: mojo_hip_gemm takes a route that is not fused here
-  if (int sk128 = 1; gemm_rows128_takes_tile128(a, dtype, m, k, n, &sk128)) {   // at most 128 rows: 128-row tiles where the model says so
-    const int r = tiles128_into_norm(sk128);
-    if (r) return r < 0 ? r : MOJO_OK;
-    planned = true;
-  }
-  if (!planned && w_k_stride == 1) {                                     // decode-sized split of the weight-streaming kernel
-    const int sk = gemm_skinny_splitk(m, k, n, 1);
-    if (slabs(sk)) {
-      if (gemm_skinny_ok(a, dtype)) {
-        if (gemm_splitk_resnorm_ok(a, dtype, residual, norm_weight, normed_out, sum_out)) {
-          const int rc = launch_gemm_skinny(a, dtype, s);
-          if (rc) return rc;
-          return launch_gemm_splitk_resnorm(a, dtype, m, residual, norm_weight, normed_out, sum_out, eps, s);
-        }
-        planned = true;
-      }
-    }
-    unsplit();
-  }
-  if (!planned && !gemm_skinny_ok(a, dtype) && k % 64 == 0 && (m > 64 || w_k_stride != 1)) {   // 128-row tiles with their own split (a prefill chunk's o_proj / down_proj)
-    int sk128 = 1;
-    if (gemm_tile128_use(a, dtype, m, gemm_dense_prefers_tile128(m, k, n, w_n_stride == 1, &sk128))) {
-      const int r = tiles128_into_norm(sk128);
-      if (r) return r < 0 ? r : MOJO_OK;
+  const DensePlan plan = plan_dense_gemm(a, dtype, m, ws2, ws2_bytes);
+  // A split product's slabs go straight into the norm (the finalize launch IS the norm): the same slices as the separate calls,
+  // summed in the same order (same bits).
+  if (plan.splitk > 1 && (plan.route == DensePlan::STREAM || plan.route == DensePlan::TILES128)) {
+    a.C = gemm_out; a.splitk = plan.splitk; a.slab = ws2 + 64; a.slab_rows = static_cast<int>(m); a.defer_finalize = 1;
+    if ((plan.route == DensePlan::STREAM || gemm_tile128_group_ok(a, dtype)) &&
+        gemm_splitk_resnorm_ok(a, dtype, residual, norm_weight, normed_out, sum_out)) {
+      const int rc = plan.route == DensePlan::STREAM ? launch_gemm_skinny(a, dtype, s) : launch_gemm_tile128(a, dtype, m, s);
+      return rc ? rc : launch_gemm_splitk_resnorm(a, dtype, m, residual, norm_weight, normed_out, sum_out, eps, s);
     }
   }
-  void* p = gemm_out ? gemm_out : static_cast<void*>(prod);
   int rc = mojo_hip_gemm(input, weight, bias, p, m, k, n, lda, n, w_k_stride, w_n_stride, dtype, ws2, ws2_bytes, stream);
   if (rc) return rc;
   return mojo_hip_residual_add_rmsnorm(p, residual, norm_weight, normed_out, sum_out, m, n, dtype, eps, stream);

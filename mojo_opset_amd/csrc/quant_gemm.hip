@@ -454,6 +454,33 @@ static int quant_skinny_splitk(int k, int n, int64_t m) {            // (workspa
   return a > b ? a : b;
 }
 
+// Split launches of every 8-bit kernel: sum the K slices' int32 / fp32 slabs in slice order, apply the scales, store C.
+template <typename TO>
+static int launch_quant_finalize(const void* slab_ws, int sk, int64_t m, int n, bool fp8, const float* rs, const bf16_t* cs, TO* C,
+                                 hipStream_t s) {
+  int64_t blocks = ceil_div(m * n, 256);
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  if (fp8)
+    hipLaunchKernelGGL((quant_finalize_kernel<TO, float>), dim3(blocks), dim3(256), 0, s, static_cast<const float*>(slab_ws), sk, m, n, rs, cs, C);
+  else
+    hipLaunchKernelGGL((quant_finalize_kernel<TO, int>), dim3(blocks), dim3(256), 0, s, static_cast<const int*>(slab_ws), sk, m, n, rs, cs, C);
+  MOJO_CHECK_LAUNCH("quant_gemm(finalize)");
+  return MOJO_OK;
+}
+
+// The 8-bit product on one kernel family, the 128-row tiles (TILE128: four outputs per store) or the 256 x 256 kernel, with the
+// dequantising epilogue.
+template <bool TILE128, typename TO>
+static int launch_quant_dequant(const GemmArgs& a, bool fp8, const float* rs, const bf16_t* cs, int64_t m, hipStream_t s) {
+  auto launch = [&](auto pol) {
+    using P = decltype(pol);
+    g256::EpilogueDequant<TO, typename P::acc_t> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, 0.f, TILE128};
+    if constexpr (TILE128) return g128::launch<P>(a, epi, m, s);
+    else return g256::gemm256_launch<P>(a, epi, m, s);
+  };
+  return fp8 ? launch(g256::PolF8{}) : launch(g256::PolI8{});
+}
+
 template <typename TO, bool FP8>
 static int launch_quant_skinny(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m, void* slab_ws, hipStream_t s) {
   constexpr bool kWide = std::is_same<TO, bf16_t>::value;   // (other output types: four-wave workgroups only — compile time)
@@ -487,15 +514,7 @@ static int launch_quant_skinny(const GemmArgs& a, const float* rs, const bf16_t*
 #undef SKINNY
   MOJO_CHECK_LAUNCH("quant_gemm(skinny)");
   note_launch("quant_skinny:waves%d:splitk%d", plan.nw, sk);
-  if (sk > 1 && slot < 0) {
-    int64_t blocks = ceil_div(m * a.N, 256);
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (FP8)
-      hipLaunchKernelGGL((quant_finalize_kernel<TO, float>), dim3(blocks), dim3(256), 0, s, static_cast<const float*>(slab_ws), sk, m, a.N, rs, cs, C);
-    else
-      hipLaunchKernelGGL((quant_finalize_kernel<TO, int>), dim3(blocks), dim3(256), 0, s, static_cast<const int*>(slab_ws), sk, m, a.N, rs, cs, C);
-    MOJO_CHECK_LAUNCH("quant_gemm(finalize)");
-  }
+  if (sk > 1 && slot < 0) return launch_quant_finalize(slab_ws, sk, m, a.N, FP8, rs, cs, C, s);
   return MOJO_OK;
 }
 
@@ -583,55 +602,21 @@ static int run_quant(GemmArgs a, const float* rs, const bf16_t* cs, int64_t m, i
       if (sk128 > 1 && a.ldc == a.N) {                 // (the finalize writes a dense [M, N]; mojo_hip_quant_gemm_workspace_bytes covers the slabs)
         a.splitk = sk128; a.slab = slab_ws; a.slab_rows = static_cast<int>(m);
       }
-      int rc;
-      if (fp8) {
-        g256::EpilogueDequant<TO, f32x4> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, 0.f, true};
-        rc = g128::launch<g256::PolF8>(a, epi, m, s);
-      } else {
-        g256::EpilogueDequant<TO, i32x4> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, 0.f, true};
-        rc = g128::launch<g256::PolI8>(a, epi, m, s);
-      }
+      const int rc = launch_quant_dequant<true, TO>(a, fp8, rs, cs, m, s);
       if (rc || a.splitk == 1) return rc;
-      int64_t blocks = ceil_div(m * a.N, 256);
-      if (blocks > 256 * 8) blocks = 256 * 8;
-      if (fp8)
-        hipLaunchKernelGGL((quant_finalize_kernel<TO, float>), dim3(blocks), dim3(256), 0, s, static_cast<const float*>(slab_ws), a.splitk, m, a.N, rs, cs, static_cast<TO*>(a.C));
-      else
-        hipLaunchKernelGGL((quant_finalize_kernel<TO, int>), dim3(blocks), dim3(256), 0, s, static_cast<const int*>(slab_ws), a.splitk, m, a.N, rs, cs, static_cast<TO*>(a.C));
-      MOJO_CHECK_LAUNCH("quant_gemm(finalize)");
-      return MOJO_OK;
+      return launch_quant_finalize(slab_ws, a.splitk, m, a.N, fp8, rs, cs, static_cast<TO*>(a.C), s);
     }
   }
   if (g256::gemm256_layout_ok(a, 1)) {
     const int sk = quant_splitk(m, a.K, a.N);
     if (sk > 1) {
       a.splitk = sk; a.slab = slab_ws; a.slab_rows = static_cast<int>(m);
-      int rc;
-      if (fp8) {
-        g256::EpilogueDequant<TO, f32x4> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, 0.f};
-        rc = g256::gemm256_launch<g256::PolF8>(a, epi, m, s);
-      } else {
-        g256::EpilogueDequant<TO, i32x4> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, 0.f};
-        rc = g256::gemm256_launch<g256::PolI8>(a, epi, m, s);
-      }
-      if (rc) return rc;
-      int64_t blocks = ceil_div(m * a.N, 256);
-      if (blocks > 256 * 8) blocks = 256 * 8;
-      if (fp8)
-        hipLaunchKernelGGL((quant_finalize_kernel<TO, float>), dim3(blocks), dim3(256), 0, s, static_cast<const float*>(slab_ws), sk, m, a.N, rs, cs, static_cast<TO*>(a.C));
-      else
-        hipLaunchKernelGGL((quant_finalize_kernel<TO, int>), dim3(blocks), dim3(256), 0, s, static_cast<const int*>(slab_ws), sk, m, a.N, rs, cs, static_cast<TO*>(a.C));
-      MOJO_CHECK_LAUNCH("quant_gemm(finalize)");
-      return MOJO_OK;
+      const int rc = launch_quant_dequant<false, TO>(a, fp8, rs, cs, m, s);
+      return rc ? rc : launch_quant_finalize(slab_ws, sk, m, a.N, fp8, rs, cs, static_cast<TO*>(a.C), s);
     }
     const bool no_stage = MOJO_SWITCH("MOJO_HIP_GEMM_STAGE_ROWS", 1) == 0;
     a.stage_rows = (!no_stage && sizeof(TO) == 2 && a.ldc % 8 == 0 && aligned_to(a.C, 16)) ? 1 : 0;   // row-staged stores (gemm256_core.h)
-    if (fp8) {
-      g256::EpilogueDequant<TO, f32x4> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, 0.f};
-      return g256::gemm256_launch<g256::PolF8>(a, epi, m, s);
-    }
-    g256::EpilogueDequant<TO, i32x4> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, 0.f};
-    return g256::gemm256_launch<g256::PolI8>(a, epi, m, s);
+    return launch_quant_dequant<false, TO>(a, fp8, rs, cs, m, s);
   }
   int64_t blocks = ceil_div(m * a.N, 256);
   if (blocks > 256 * 32) blocks = 256 * 32;
