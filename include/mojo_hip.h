@@ -320,6 +320,48 @@ int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cache, const v
                                int layout_abab, int dtype, void* workspace, int64_t workspace_bytes,
                                mojo_stream_t stream);
 
+/* ---- MojoPagedDecodeSWA / MojoPagedPrefillSWA (core/operators/attention.py:507-744; replace the TTX backend's
+ *      sliding-window kernels, backends/ttx/operators/attention.py:240, :340).  The arguments of the GQA pair plus
+ *      local_window (< 0: none) and global_window (<= 0: none).  Query row i of a sequence of q_len queries over kv_len keys
+ *      sits at position p = kv_len - q_len + i (decode: p = kv_len - 1) and sees key j iff j <= p and
+ *      (j >= p - local_window or j < global_window); with neither window this is the GQA op (these entry points call it).
+ *      Only the key tiles of the two ranges are walked and the launch is sized on the visible keys (decode: at most
+ *      ceil16(global) + local + 16 per row), so a 4k window over a 32k context moves the bytes of a 4k context.
+ *      Pages outside the visible set are never read: their table entries may be -1 or name recycled pages (decode: pages of
+ *      the row's window; prefill: of the union of the windows of a sequence's query rows, for pages of >= 16 tokens; smaller
+ *      pages may be read at the window edges, and their keys never reach the output).  There is no hole scan: a negative
+ *      entry INSIDE the visible set reads page 0.  Everything else — hints, workspace, leave_empty_rows, zeroed rows — is
+ *      that of the GQA entry point.                                                                                        */
+int64_t mojo_hip_paged_decode_swa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                  int64_t head_dim, int64_t block_size,
+                                                  int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                  int64_t local_window, int64_t global_window);
+int mojo_hip_paged_decode_swa(const void* query, const void* key_cache, const void* value_cache,
+                              const int32_t* total_seq_lens, const int32_t* block_tables,
+                              void* out, void* workspace, int64_t workspace_bytes,
+                              int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                              int64_t block_size, int64_t max_blocks_per_seq,
+                              int64_t block_table_stride, int64_t cache_block_stride,
+                              int64_t cache_head_stride, int64_t cache_token_stride,
+                              int64_t max_seq_len_hint, float softmax_scale, int layout_abab,
+                              int leave_empty_rows, int dtype, int64_t local_window,
+                              int64_t global_window, mojo_stream_t stream);
+int64_t mojo_hip_paged_prefill_swa_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
+                                                   int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                                   int64_t max_blocks_per_seq, int64_t max_q_len_hint,
+                                                   int64_t max_kv_len_hint, int64_t local_window,
+                                                   int64_t global_window);
+int mojo_hip_paged_prefill_swa(const void* query, const void* key_cache, const void* value_cache,
+                               const int32_t* cu_q_lens, const int32_t* cu_total_seq_lens,
+                               const int32_t* block_tables, void* out, int64_t total_tokens,
+                               int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                               int64_t block_size, int64_t max_blocks_per_seq,
+                               int64_t block_table_stride, int64_t cache_block_stride,
+                               int64_t cache_head_stride, int64_t cache_token_stride,
+                               int64_t max_q_len_hint, int64_t max_kv_len_hint, float softmax_scale,
+                               int layout_abab, int dtype, void* workspace, int64_t workspace_bytes,
+                               int64_t local_window, int64_t global_window, mojo_stream_t stream);
+
 /* ---- MoE routing either side of the grouped GEMM (core/operators/moe.py).
  *      gating (:299-316): softmax(hidden.float() @ gate_weight [hidden, E] fp32) over all experts, top-k in descending
  *      order (ties: lowest expert id), gates renormalised to sum 1.  top_k <= min(E, 64), E <= 1024.  With many

@@ -4,9 +4,15 @@
 registers the ``HIP<Op>`` backend classes.  Backend selection follows the reference:
 ``MOJO_BACKEND`` is read at every construction; on a ROCm host the priority is
 ``["hip", "torch"]``.  The package contains no CPU compute path.
+
+``__all__`` is the SURVEY §8 set, whose torch goldens live in the repo-level ``oracle/`` package.  Ops beyond §8
+(``EXTENDED_OPS``: the sliding-window pair ``MojoPagedDecodeSWA`` / ``MojoPagedPrefillSWA``) are package attributes
+too, but not in ``__all__``; their goldens are test infrastructure under ``tests/`` (``tests/swa_golden.py``).
+``plugin.rebase_hip_backend`` registers both sets into the reference.
 """
 from .core import *  # noqa: F401,F403
 from .core import __all__ as _core_all
+from .core import EXTENDED_OPS, MojoPagedDecodeSWA, MojoPagedPrefillSWA  # noqa: F401
 from . import backends  # noqa: F401  (registers HIP<Op> classes)
 from .paged_cache import PagedDummyCache  # noqa: E402  device-side block allocator (SURVEY §8 f4)
 

@@ -4,8 +4,8 @@ from typing import Optional
 
 import torch
 
-from ....core.operators.attention import (MojoPagedDecodeGQA, MojoPagedPrefillGQA, assert_paged_decode_contract,
-                                          assert_paged_prefill_contract)
+from ....core.operators.attention import (MojoPagedDecodeGQA, MojoPagedDecodeSWA, MojoPagedPrefillGQA,
+                                          MojoPagedPrefillSWA, assert_paged_decode_contract, assert_paged_prefill_contract)
 from .... import switches
 from .. import lib as L
 
@@ -108,4 +108,112 @@ class HIPPagedPrefillGQA(MojoPagedPrefillGQA):
             tokens, batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
             key_cache.stride(1), key_cache.stride(2), hint_q, hint_kv, scale,
             1 if self.gqa_layout == "ABAB" else 0, L.dtype_code(q.dtype), L.ptr(ws), ws_bytes, L.stream_of(q)), "HIPPagedPrefillGQA")
+        return out
+
+
+def _swa_windows(op, what):
+    """(local, global) of the C ABI from the reference's attributes: local < 0 = none, global <= 0 = none.  Host-side
+    Python ints only (no sync, capture-safe).  Raises the ValueError of the windows that leave a row without any
+    visible key — where the golden's softmax returns NaN: a negative size, or ``global_window_size=0`` alone."""
+    local, glob = op.local_window_size, op.global_window_size
+    for name, v in (("local_window_size", local), ("global_window_size", glob)):
+        if v is not None and int(v) < 0:
+            raise ValueError(f"{what}: {name} must be None or >= 0, got {v}")
+    if local is None and glob is not None and int(glob) == 0:
+        raise ValueError(f"{what}: global_window_size=0 without a local window leaves no key visible")
+    return (-1 if local is None else int(local)), (0 if glob is None else int(glob))
+
+
+class HIPPagedDecodeSWA(MojoPagedDecodeSWA):
+    """Sliding-window paged decode: the GQA decode kernels walking only the tiles of the global and local ranges (DESIGN
+    §4.10).  With no window, or ``is_causal=False`` (no mask at all), it is `HIPPagedDecodeGQA`'s entry point."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key_cache, value_cache, total_seq_lens, block_table, softmax_scale: Optional[float] = None,
+                *, max_total_seq_len: Optional[int] = None, leave_empty_rows: Optional[bool] = None):
+        assert_paged_decode_contract(block_table, total_seq_lens)
+        local, glob = _swa_windows(self, "HIPPagedDecodeSWA")
+        if not self.is_causal:
+            local, glob = -1, 0
+        L.require_cuda(query, key_cache, value_cache, total_seq_lens, block_table)
+        batch, hq, dim = query.shape
+        n_blocks, hkv, page, dim_c = key_cache.shape
+        assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
+        assert query.dtype == key_cache.dtype == value_cache.dtype
+        _check_cache_layout(key_cache, value_cache, "HIPPagedDecodeSWA")
+        if _validate_tables() and batch > 0 and block_table.shape[1] > 0:
+            if bool(((total_seq_lens > 0) & (block_table[:, 0] < 0)).any()):
+                raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
+            if max_total_seq_len is not None and int(total_seq_lens.max()) > int(max_total_seq_len):
+                raise ValueError("HIPPagedDecodeSWA: a total_seq_lens entry exceeds max_total_seq_len")
+        q = query if query.is_contiguous() else query.contiguous()
+        tables = block_table if block_table.stride(1) == 1 else block_table.contiguous()
+        lens = total_seq_lens if total_seq_lens.is_contiguous() else total_seq_lens.contiguous()
+        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
+        hint = int(max_total_seq_len) if max_total_seq_len is not None else 0
+        out = torch.empty_like(q)
+        lib = L.load()
+        gqa = local < 0 and glob <= 0                     # no window: the GQA op itself, bit for bit
+        geometry = (batch, hq, hkv, dim, page, tables.shape[1], hint)
+        ws_bytes = (lib.mojo_hip_paged_decode_gqa_workspace_bytes(*geometry) if gqa else
+                    lib.mojo_hip_paged_decode_swa_workspace_bytes(*geometry, local, glob))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+        args = [L.ptr(q), L.ptr(key_cache), L.ptr(value_cache), L.ptr(lens), L.ptr(tables), L.ptr(out), L.ptr(ws),
+                ws.numel(), batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
+                key_cache.stride(1), key_cache.stride(2), hint, scale, 1 if self.gqa_layout == "ABAB" else 0,
+                # replay contract of padded rows (seq_len <= 0): untouched while a graph is being captured, zeros eagerly
+                1 if (_capturing(q) if leave_empty_rows is None else leave_empty_rows) else 0, L.dtype_code(q.dtype)]
+        if gqa:
+            L.check(lib.mojo_hip_paged_decode_gqa(*args, L.stream_of(q)), "HIPPagedDecodeSWA")
+        else:
+            L.check(lib.mojo_hip_paged_decode_swa(*args, local, glob, L.stream_of(q)), "HIPPagedDecodeSWA")
+        return out
+
+
+class HIPPagedPrefillSWA(MojoPagedPrefillSWA):
+    """Sliding-window paged prefill: the GQA prefill kernel walking the key tiles of the global range and of the block's
+    local range only.  With no window it is `HIPPagedPrefillGQA`'s entry point."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key_cache, value_cache, cu_q_lens, block_table, softmax_scale: Optional[float] = None,
+                cu_total_seq_lens: Optional[torch.Tensor] = None, *, max_q_len: Optional[int] = None,
+                max_total_seq_len: Optional[int] = None):
+        assert_paged_prefill_contract(cu_q_lens, block_table, cu_total_seq_lens)
+        if not self.is_causal:
+            raise NotImplementedError("HIPPagedPrefillSWA supports causal attention only")
+        local, glob = _swa_windows(self, "HIPPagedPrefillSWA")
+        L.require_cuda(query, key_cache, value_cache, cu_q_lens, block_table, cu_total_seq_lens)
+        tokens, hq, dim = query.shape
+        n_blocks, hkv, page, dim_c = key_cache.shape
+        assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
+        assert query.dtype == key_cache.dtype == value_cache.dtype
+        _check_cache_layout(key_cache, value_cache, "HIPPagedPrefillSWA")
+        batch = cu_q_lens.shape[0] - 1
+        if _validate_tables() and batch > 0 and block_table.shape[1] > 0:
+            q_lens = cu_q_lens[1:] - cu_q_lens[:-1]
+            kv_lens = q_lens if cu_total_seq_lens is None else cu_total_seq_lens[1:] - cu_total_seq_lens[:-1]
+            if bool(((q_lens > 0) & (kv_lens > 0) & (block_table[:, 0] < 0)).any()):
+                raise ValueError("Paged prefill requires a valid block table for rows with kv lens > 0.")
+        q = query if query.is_contiguous() else query.contiguous()
+        tables = block_table if block_table.stride(1) == 1 else block_table.contiguous()
+        cu_q = cu_q_lens.contiguous()
+        cu_kv = None if cu_total_seq_lens is None else cu_total_seq_lens.contiguous()
+        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
+        out = torch.empty_like(q)
+        lib = L.load()
+        hint_q = int(max_q_len) if max_q_len else 0
+        hint_kv = int(max_total_seq_len) if max_total_seq_len else 0
+        gqa = local < 0 and glob <= 0                     # no window: the GQA op itself, bit for bit
+        geometry = (tokens, batch, hq, hkv, dim, page, tables.shape[1], hint_q, hint_kv)
+        ws_bytes = (lib.mojo_hip_paged_prefill_gqa_workspace_bytes(*geometry) if gqa else
+                    lib.mojo_hip_paged_prefill_swa_workspace_bytes(*geometry, local, glob))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes > 0 else None
+        args = [L.ptr(q), L.ptr(key_cache), L.ptr(value_cache), L.ptr(cu_q), L.ptr(cu_kv), L.ptr(tables), L.ptr(out),
+                tokens, batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
+                key_cache.stride(1), key_cache.stride(2), hint_q, hint_kv, scale,
+                1 if self.gqa_layout == "ABAB" else 0, L.dtype_code(q.dtype), L.ptr(ws), ws_bytes]
+        if gqa:
+            L.check(lib.mojo_hip_paged_prefill_gqa(*args, L.stream_of(q)), "HIPPagedPrefillSWA")
+        else:
+            L.check(lib.mojo_hip_paged_prefill_swa(*args, local, glob, L.stream_of(q)), "HIPPagedPrefillSWA")
         return out

@@ -1,5 +1,5 @@
 from .activation import MojoSwiGLU
-from .attention import MojoPagedDecodeGQA, MojoPagedPrefillGQA
+from .attention import MojoPagedDecodeGQA, MojoPagedDecodeSWA, MojoPagedPrefillGQA, MojoPagedPrefillSWA
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
 from .kv_cache import MojoStorePagedKVCache, MojoStorePagedMLAKVCache, build_paged_kv_chunk_metadata
@@ -18,3 +18,7 @@ __all__ = [
     "MojoMoECombine", "MojoMoE", "MojoDynamicQuant", "MojoResidualAddRMSNormQuant", "MojoStorePagedMLAKVCache",
     "MojoGemm", "MojoSwiGLUMLP",
 ]
+
+# Ops beyond the SURVEY §8 set: importable, but not in `__all__` (whose goldens live in the repo-level `oracle/`); their
+# goldens are test infrastructure under `tests/`.
+EXTENDED_OPS = ("MojoPagedDecodeSWA", "MojoPagedPrefillSWA")

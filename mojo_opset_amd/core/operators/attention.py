@@ -1,10 +1,12 @@
-"""API classes of the paged GQA attention pair.
+"""API classes of the paged GQA attention pair and of its sliding-window pair.
 
 Constructor arguments, contracts and `forward` signatures follow
 `mojo_opset/core/operators/attention.py` (`MojoPagedDecodeGQA` :113-232,
-`MojoPagedPrefillGQA` :315-451, contracts :12-37).  The classes are API-only; see
+`MojoPagedPrefillGQA` :315-451, contracts :12-37, `MojoPagedPrefillSWA` :533-650,
+`MojoPagedDecodeSWA` :653-744).  The classes are API-only; see
 `core/operator.py` for why the golden `forward` is not here.
 """
+from typing import Optional
 
 import torch
 
@@ -72,3 +74,54 @@ class MojoPagedPrefillGQA(_PagedGQABase, MojoOperator):
     def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB"):
         super().__init__()
         self._init_gqa(is_causal, gqa_layout)
+
+
+class _PagedSWABase:
+    """Constructor of the sliding-window pair (reference :533-560, :653-680): the attributes ``is_causal``,
+    ``gqa_layout``, ``gqa_interleave``, ``global_window_size`` and ``local_window_size`` are all a backend may read
+    (the plugin keeps the reference's constructor and grafts only ``forward``)."""
+
+    def _init_swa(self, is_causal: bool, gqa_layout: str, global_window_size: Optional[int],
+                  local_window_size: Optional[int]) -> None:
+        if gqa_layout not in _GQA_LAYOUTS:
+            raise ValueError(f"gqa_layout must be one of ['ABAB', 'AABB'], got {gqa_layout}")
+        self.is_causal = is_causal
+        self.gqa_layout = gqa_layout
+        self.gqa_interleave = gqa_layout == "ABAB"
+        self.global_window_size = global_window_size
+        self.local_window_size = local_window_size
+
+    def extra_repr(self) -> str:
+        return (f"is_causal={self.is_causal}, gqa_layout={self.gqa_layout}, "
+                f"global_window_size={self.global_window_size}, local_window_size={self.local_window_size}")
+
+
+class MojoPagedDecodeSWA(_PagedSWABase, MojoOperator):
+    """One query token per sequence against a paged KV cache, sliding window.
+
+    The query sits at position ``p = kv_len - 1`` and sees key ``j`` iff ``j <= p`` and, when a window is set,
+    ``j >= p - local_window_size`` (local window: ``local + 1`` keys) or ``j < global_window_size``.
+
+    forward(query [B,Hq,D], key_cache/value_cache [N_blocks,Hkv,page,D], total_seq_lens [B] i32,
+            block_table [B,max_blocks] i32, softmax_scale=None, *, max_total_seq_len=None) -> [B,Hq,D];
+    rows with seq_len <= 0 are zeros.
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,
+                 local_window_size: Optional[int] = None):
+        super().__init__()
+        self._init_swa(is_causal, gqa_layout, global_window_size, local_window_size)
+
+
+class MojoPagedPrefillSWA(_PagedSWABase, MojoOperator):
+    """Packed var-len queries against a paged KV cache, causal offset ``kv_len - q_len``, sliding window (the
+    visibility rule of `MojoPagedDecodeSWA` for every query row).
+
+    forward(query [T,Hq,D], key_cache, value_cache, cu_q_lens [B+1] i32, block_table [B,nb] i32,
+            softmax_scale=None, cu_total_seq_lens=None, *, max_q_len=None, max_total_seq_len=None) -> [T,Hq,D]
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,
+                 local_window_size: Optional[int] = None):
+        super().__init__()
+        self._init_swa(is_causal, gqa_layout, global_window_size, local_window_size)

@@ -66,7 +66,43 @@ struct DecodeArgs {
   int fuse_group = 0;             // > 0: GROUPED form — workgroups of this many waves each own that many consecutive chunks of a row,
                                   // merge them in LDS and leave ONE partial per workgroup (slot = workgroup index along x) for the
                                   // merge launch; a row whose chunks fit one workgroup is finished there
+  // sliding window (the SWA instances only; see DecodeWin): real-length capacity, local window (< 0: none), global window (<= 0: none)
+  int swa_cap = 0, local_win = -1, global_win = 0;
 };
+
+// Sliding window (MojoPagedDecodeSWA).  Row of `len` keys, query at position len - 1: key t is visible iff t < g1 or
+// lo <= t < len, with lo = max(0, len - 1 - local) (len without a local window) and g1 = min(global, lo).  The kernels walk
+// a VIRTUAL key range of vlen tokens: [0, g_al) is the global range rounded up to the 16-token tile, then the local range from
+// its tile start lo_al = lo & ~15 on — virtual token v is real token v + gap past g_al (gap = lo_al - g_al, 0 when the two
+// ranges overlap and collapse into one).  Both cuts are tile-aligned, so a tile never straddles them; the tiles holding g1
+// or lo are masked per key ("edge" tiles).  Chunking, pairing of chunks and merging all run on vlen, which is at most
+// ceil16(global) + local + 16 whatever the context: the host sizes the launch on that, not on the table's capacity.
+struct DecodeWin { int len = 0, g1 = 0, lo = 0, g_al = 0, gap = 0; };
+__device__ __forceinline__ int decode_swa_row(const DecodeArgs& a, int b, DecodeWin& w) {
+  const int len = max(min(a.seq_lens[b], a.swa_cap), 0);
+  w.len = len;
+  w.lo = a.local_win >= 0 ? max(len - 1 - a.local_win, 0) : len;
+  w.g1 = min(max(a.global_win, 0), w.lo);
+  w.g_al = (w.g1 + DEC_TILE - 1) & ~(DEC_TILE - 1);
+  w.gap = 0;
+  int vlen = len;
+  if (w.lo >= len) {
+    vlen = w.g1;                                         // no local range: the global range alone
+  } else {
+    const int lo_al = w.lo & ~(DEC_TILE - 1);
+    if (lo_al > w.g_al) { w.gap = lo_al - w.g_al; vlen = len - w.gap; }
+  }
+  // (row-uniform: pinned to scalar registers — held in vector registers they spilled the fused matrix-core instance)
+  w.len = __builtin_amdgcn_readfirstlane(w.len);
+  w.g1 = __builtin_amdgcn_readfirstlane(w.g1);
+  w.lo = __builtin_amdgcn_readfirstlane(w.lo);
+  w.g_al = __builtin_amdgcn_readfirstlane(w.g_al);
+  w.gap = __builtin_amdgcn_readfirstlane(w.gap);
+  return __builtin_amdgcn_readfirstlane(min(vlen, a.n_chunks * a.chunk_tokens));
+}
+__device__ __forceinline__ int decode_swa_real(const DecodeWin& w, int v) { return v >= w.g_al ? v + w.gap : v; }
+__device__ __forceinline__ bool decode_swa_edge(const DecodeWin& w, int rt0) { return rt0 < w.lo && rt0 + DEC_TILE > w.g1; }
+__device__ __forceinline__ bool decode_swa_vis(const DecodeWin& w, int t) { return t < w.g1 || (t >= w.lo && t < w.len); }
 
 // Chunking is PER SEQUENCE: a sequence of `len` tokens is cut into n_chunks equal pieces (whole tiles, at least 128 tokens,
 // never more than the launch-wide chunk_tokens), so the waves of a short row of a ragged batch all work (and finish early)
@@ -100,10 +136,11 @@ __device__ __forceinline__ int decode_head(const DecodeArgs& a, int kvh, int g, 
   return (half * G + g) * (a.hkv >> a.hshift) + real;
 }
 
-template <typename T, int G, bool NT, int MODE>
+template <typename T, int G, bool NT, int MODE, bool SWA = false>
 __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_kernel(DecodeArgs a) {
   constexpr bool FUSED = MODE != DEC_SPLIT;
   constexpr bool PAIRED = MODE == DEC_PAIRED;
+  static_assert(!(SWA && PAIRED), "the paired form takes no window");
   typedef typename pack8<T>::vec V8;
   typedef typename pack8<T>::pair V2;
   const int lane = threadIdx.x & 63;
@@ -116,6 +153,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   const int kvh = blockIdx.y % a.hkv;
 
   int seq_len, chunk_tokens;
+  DecodeWin win;                                         // (SWA only)
   // paired mode: the two sequences of this workgroup, their (clamped) lengths and the waves dealt to the first
   int pb[2] = {0, -1}, plen[2] = {0, 0}, pchunk[2] = {DEC_TILE, DEC_TILE}, n_first = 8;
   if constexpr (PAIRED) {
@@ -155,7 +193,8 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
     chunk_tokens = pchunk[u];
     if (b < 0) b = pb[0];                              // a wave without a sequence: valid addresses, no work
   } else {
-    seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;      // (no table columns: nothing to attend over)
+    if constexpr (SWA) seq_len = a.max_pages > 0 ? decode_swa_row(a, b, win) : 0;
+    else seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;      // (no table columns: nothing to attend over)
     chunk_tokens = decode_seq_chunk(a, seq_len);
   }
   const int tok_begin = chunk * chunk_tokens;
@@ -217,7 +256,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
       if (neg && first_neg == 0x7fffffff) first_neg = base + u * 64 + __builtin_ctzll(neg);
     }
   };
-  if (has_work) scan_issue(0);
+  if (!SWA && has_work) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
 
   const T* kbase = static_cast<const T*>(a.kc) + (kvh >> a.hshift) * a.c_head + jd;
   const T* vbase = static_cast<const T*>(a.vc) + (kvh >> a.hshift) * a.c_head + jd;
@@ -236,7 +275,11 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   auto load_tile = [&](Tile& t, int t0) {
 #pragma unroll
     for (int u = 0; u < DEC_LOADS; ++u) {
-      const int tu = min(t0 + u * DEC_TPL, last_load);    // wave-uniform; TPL | page
+      int tu = min(t0 + u * DEC_TPL, last_load);          // wave-uniform; TPL | page
+      if constexpr (SWA) {
+        tu = decode_swa_real(win, tu);
+        if (tu >= win.g1 && tu + DEC_TPL <= win.lo) tu = win.lo & ~(DEC_TPL - 1);   // a load no key of which is visible: read
+      }                                                                               // the page of `lo` instead (masked below)
       const int lp = a.page_shift >= 0 ? (tu >> a.page_shift) : tu / a.page;
       t.lp[u] = lp;
       const int phys = max(table[min(lp, last_page)], 0);
@@ -253,11 +296,16 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
         if (t.lp[u] >= first_neg) { V8 z = {}; t.k[u] = z; t.v[u] = z; }
     }
     const bool full = t0 + DEC_TILE <= tok_end;          // wave-uniform
-    if (!full) {                                         // last tile of the chunk: slots past the length may hold NaN/Inf
+    bool edge = false;                                   // SWA: the tile holds a window edge (wave-uniform)
+    int rt0 = t0;
+    if constexpr (SWA) { rt0 = decode_swa_real(win, t0); edge = decode_swa_edge(win, rt0); }
+    if (!full || edge) {                                 // last tile of the chunk: slots past the length may hold NaN/Inf
 #pragma unroll
       for (int u = 0; u < DEC_LOADS; ++u) {
         V8 z = {};
-        if (!((t0 + u * DEC_TPL + r) < tok_end)) t.v[u] = z;
+        bool ok = (t0 + u * DEC_TPL + r) < tok_end;
+        if constexpr (SWA) ok = ok && (!edge || decode_swa_vis(win, rt0 + u * DEC_TPL + r));
+        if (!ok) t.v[u] = z;
       }
     }
     // Heads in blocks of GB = 4: eight heads at once need 32 score registers on top of 64 accumulators, 32 query registers
@@ -287,10 +335,11 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
           s[u][gg] = row16_sum(d) * a.scale_log2;
         }
       }
-      if (!full) {                                       // mask the tail
+      if (!full || edge) {                               // mask the tail (and the window edges)
 #pragma unroll
         for (int u = 0; u < DEC_LOADS; ++u) {
-          const bool valid = (t0 + u * DEC_TPL + r) < tok_end;
+          bool valid = (t0 + u * DEC_TPL + r) < tok_end;
+          if constexpr (SWA) valid = valid && (!edge || decode_swa_vis(win, rt0 + u * DEC_TPL + r));
 #pragma unroll
           for (int gg = 0; gg < GB; ++gg) s[u][gg] = valid ? s[u][gg] : -INFINITY;
         }
@@ -331,10 +380,12 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   if (has_work) {
   load_tile(ta, tok_begin);
   if (tok_begin + DEC_TILE < tok_end) load_tile(tb, tok_begin + DEC_TILE);
+  if constexpr (!SWA) {
   scan_reduce(0);
   for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {   // contexts past 256 pages
     scan_issue(base);
     scan_reduce(base);
+  }
   }
   if constexpr (RING == 3) {
     for (int t0 = tok_begin; t0 < tok_end; t0 += 3 * DEC_TILE) {
@@ -467,14 +518,16 @@ namespace mojo {
 // the chunks j, j + 8, ...; the eight partial sums meet in LDS and are added in lane order (fixed, so the bits do not depend
 // on timing).  (One thread used to walk all chunks of a row through dependent loads: a single long sequence — B = 1,
 // 16K tokens, 128 chunks — spent ~38 of its 54 us here.)
-template <typename T>
+template <typename T, bool SWA = false>
 __global__ __launch_bounds__(256) void decode_merge_kernel(DecodeArgs a, int G) {
   __shared__ float s_mx[8], s_den[8];
   __shared__ f32x4 s_num[8][32];
   const int b = blockIdx.x / a.hkv;
   const int kvh = blockIdx.x % a.hkv;
   const int g = blockIdx.y;
-  const int seq_len = decode_seq_len(a, b);
+  int seq_len;
+  if constexpr (SWA) { DecodeWin w; seq_len = decode_swa_row(a, b, w); }
+  else seq_len = decode_seq_len(a, b);
   const int chunk_tokens = decode_seq_chunk(a, seq_len);
   int n_chunks_seq = seq_len <= 0 ? 0 : (seq_len + chunk_tokens - 1) / chunk_tokens;   // <= a.n_chunks by construction
   if (a.fuse_group > 0) n_chunks_seq = (n_chunks_seq + a.fuse_group - 1) / a.fuse_group;   // grouped form: one partial per workgroup
@@ -577,6 +630,14 @@ static int64_t decode_max_len(int64_t page, int64_t max_pages, int64_t hint) {
   return (hint > 0 && hint < cap) ? hint : cap;
 }
 
+// Sliding window: the most virtual tokens (DecodeWin) a row of a launch of real capacity `max_len` can walk — the global
+// range rounded up to a tile plus the local window's local + 1 keys and the tile they start in.
+static int64_t decode_swa_cap(int64_t max_len, int64_t local_window, int64_t global_window) {
+  int64_t span = global_window > 0 ? ceil_div(global_window, DEC_TILE) * DEC_TILE : 0;
+  if (local_window >= 0) span += local_window + DEC_TILE;
+  return span < max_len ? span : max_len;
+}
+
 // The matrix-core kernel (paged_decode_mfma.h): pages of a multiple of 16 tokens, head_dim 64 / 128, groups of <= 16 heads.
 // MOJO_HIP_DECODE_MFMA: unset = where it measured faster (B 64, ctx 4096, page 16, graph replay, vector-unit -> matrix-core):
 // groups of 8 heads (Llama-3-70B 64 / 8: 356 -> 170 us; 8 / 1: 79 -> 39 us), head_dim 64 (149 -> 99 us), groups of 4 at
@@ -591,68 +652,69 @@ static bool decode_use_mfma(const DecodeArgs& a, int G) {
   return G >= 4 || a.dim == 64 || (G != 1 && G != 2);
 }
 
-template <typename T, bool NT, int MODE>
+template <typename T, bool NT, int MODE, bool SWA>
 static void launch_decode_mfma(const DecodeArgs& a, dim3 grid, dim3 block, int G, hipStream_t s) {
   const size_t waves = block.x / 64;
   const size_t lds = (MODE != DEC_SPLIT ? waves * G * (a.dim + 2) * sizeof(float) : 0) + waves * 4096;   // + one 4 KiB V image (set) per wave
   static std::atomic<uint64_t> attr_set{0};             // (per instantiation: dynamic LDS beyond 64 KiB needs the attribute)
   if (first_call_on_device(attr_set)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_kernel<T, 4, NT, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_kernel<T, 2, NT, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_kernel<T, 4, NT, MODE, SWA>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_kernel<T, 2, NT, MODE, SWA>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
-  if (a.dim == 128) hipLaunchKernelGGL((decode_mfma_kernel<T, 4, NT, MODE>), grid, block, lds, s, a, G);
-  else hipLaunchKernelGGL((decode_mfma_kernel<T, 2, NT, MODE>), grid, block, lds, s, a, G);
+  if (a.dim == 128) hipLaunchKernelGGL((decode_mfma_kernel<T, 4, NT, MODE, SWA>), grid, block, lds, s, a, G);
+  else hipLaunchKernelGGL((decode_mfma_kernel<T, 2, NT, MODE, SWA>), grid, block, lds, s, a, G);
 }
 
-template <typename T, bool NT>
+template <typename T, bool NT, bool SWA>
 static int launch_decode_nt(DecodeArgs& a, int64_t batch, int G, hipStream_t s) {
   const bool no_fuse = MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) == 0;
   const bool no_pair = MOJO_SWITCH("MOJO_HIP_DECODE_PAIR", 1) == 0;
   const char* nt_tag = NT ? "nt" : "cached";
+  const char* swa_tag = SWA ? ":swa" : "";             // (the windowed instances: never the paired form)
   if (decode_use_mfma(a, G)) {
-    if (a.n_chunks == 4 && batch >= 2 && batch <= 64 && !no_fuse && !no_pair) {
-      launch_decode_mfma<T, NT, DEC_PAIRED>(a, dim3(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv)), dim3(512), G, s);
+    if (!SWA && a.n_chunks == 4 && batch >= 2 && batch <= 64 && !no_fuse && !no_pair) {
+      launch_decode_mfma<T, NT, DEC_PAIRED, false>(a, dim3(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv)), dim3(512), G, s);
       MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, paired)");
-      note_launch("decode_mfma:paired:%s", nt_tag);
+      note_launch("decode_mfma:paired:%s%s", nt_tag, swa_tag);
       return MOJO_OK;
     }
     if (a.n_chunks <= 8 && !no_fuse) {
-      launch_decode_mfma<T, NT, DEC_FUSED>(a, dim3(1, static_cast<unsigned>(batch * a.hkv)), dim3(static_cast<unsigned>(64 * a.n_chunks)), G, s);
+      launch_decode_mfma<T, NT, DEC_FUSED, SWA>(a, dim3(1, static_cast<unsigned>(batch * a.hkv)), dim3(static_cast<unsigned>(64 * a.n_chunks)), G, s);
       MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, fused)");
-      note_launch("decode_mfma:fused:%s", nt_tag);
+      note_launch("decode_mfma:fused:%s%s", nt_tag, swa_tag);
       return MOJO_OK;
     }
     if (a.fuse_group > 0 && !no_fuse) {
       // small grids (few (sequence, kv-head) rows, many chunks each): eight-wave workgroups merge their chunks in LDS and leave
       // one partial each, so the launch keeps two waves per SIMD busy and the merge reads n_chunks / 8 partials per row
       const unsigned n_sub = static_cast<unsigned>((a.n_chunks + a.fuse_group - 1) / a.fuse_group);
-      launch_decode_mfma<T, NT, DEC_FUSED>(a, dim3(n_sub, static_cast<unsigned>(batch * a.hkv)), dim3(static_cast<unsigned>(64 * a.fuse_group)), G, s);
+      launch_decode_mfma<T, NT, DEC_FUSED, SWA>(a, dim3(n_sub, static_cast<unsigned>(batch * a.hkv)), dim3(static_cast<unsigned>(64 * a.fuse_group)), G, s);
       MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, grouped)");
-      hipLaunchKernelGGL((decode_merge_kernel<T>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
+      hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
       MOJO_CHECK_LAUNCH("paged_decode_gqa(merge)");
-      note_launch("decode_mfma:grouped+merge:%s", nt_tag);
+      note_launch("decode_mfma:grouped+merge:%s%s", nt_tag, swa_tag);
       return MOJO_OK;
     }
-    launch_decode_mfma<T, NT, DEC_SPLIT>(a, dim3(static_cast<unsigned>(a.n_chunks), static_cast<unsigned>(batch * a.hkv)), dim3(64), G, s);
+    launch_decode_mfma<T, NT, DEC_SPLIT, SWA>(a, dim3(static_cast<unsigned>(a.n_chunks), static_cast<unsigned>(batch * a.hkv)), dim3(64), G, s);
     MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, split)");
-    hipLaunchKernelGGL((decode_merge_kernel<T>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
+    hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
     MOJO_CHECK_LAUNCH("paged_decode_gqa(merge)");
-    note_launch("decode_mfma:split+merge:%s", nt_tag);
+    note_launch("decode_mfma:split+merge:%s%s", nt_tag, swa_tag);
     return MOJO_OK;
   }
-  if (a.n_chunks == 4 && batch >= 2 && batch <= 64 && a.dim % 4 == 0 && !no_fuse && !no_pair) {
+  if (!SWA && a.n_chunks == 4 && batch >= 2 && batch <= 64 && a.dim % 4 == 0 && !no_fuse && !no_pair) {
     // four waves per sequence fill the chip once: pair the sequences by length rank and deal each pair's 8 waves by length
     dim3 grid(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv));
     const size_t lds = static_cast<size_t>(8) * G * (a.dim + 2) * sizeof(float) + (G >= 8 ? static_cast<size_t>(8) * G * DEC_LPT * 16 : 0);
     switch (G) {
-      case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_PAIRED>), grid, dim3(512), lds, s, a); break;
-      case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_PAIRED>), grid, dim3(512), lds, s, a); break;
-      case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_PAIRED>), grid, dim3(512), lds, s, a); break;
-      case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_PAIRED>), grid, dim3(512), lds, s, a); break;
+      case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
+      case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
+      case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
+      case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
       default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa: group size %d (supported: 1,2,4,8)", G);
     }
     MOJO_CHECK_LAUNCH("paged_decode_gqa(paired)");
-    note_launch("decode_valu:paired:%s", nt_tag);
+    note_launch("decode_valu:paired:%s%s", nt_tag, swa_tag);
     return MOJO_OK;
   }
   if (a.n_chunks <= 8 && a.dim % 4 == 0 && !no_fuse) {   // all chunks of a (sequence, kv-head) in one workgroup: merged in LDS
@@ -661,53 +723,56 @@ static int launch_decode_nt(DecodeArgs& a, int64_t batch, int G, hipStream_t s) 
     const size_t lds = static_cast<size_t>(a.n_chunks) * G * (a.dim + 2) * sizeof(float) +
                        (G >= 8 ? static_cast<size_t>(a.n_chunks) * G * DEC_LPT * 16 : 0);
     switch (G) {
-      case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_FUSED>), grid, block, lds, s, a); break;
-      case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_FUSED>), grid, block, lds, s, a); break;
-      case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_FUSED>), grid, block, lds, s, a); break;
-      case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_FUSED>), grid, block, lds, s, a); break;
+      case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
+      case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
+      case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
+      case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
       default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa: group size %d (supported: 1,2,4,8)", G);
     }
     MOJO_CHECK_LAUNCH("paged_decode_gqa(fused)");
-    note_launch("decode_valu:fused:%s", nt_tag);
+    note_launch("decode_valu:fused:%s%s", nt_tag, swa_tag);
     return MOJO_OK;
   }
   dim3 grid(static_cast<unsigned>(a.n_chunks), static_cast<unsigned>(batch * a.hkv));
   switch (G) {
-    case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_SPLIT>), grid, dim3(64), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_SPLIT>), grid, dim3(64), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_SPLIT>), grid, dim3(64), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_SPLIT>), grid, dim3(64), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
     default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa: group size %d (supported: 1,2,4,8)", G);
   }
   MOJO_CHECK_LAUNCH("paged_decode_gqa(split)");
-  hipLaunchKernelGGL((decode_merge_kernel<T>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
+  hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
   MOJO_CHECK_LAUNCH("paged_decode_gqa(merge)");
-  note_launch("decode_valu:split+merge:%s", nt_tag);
+  note_launch("decode_valu:split+merge:%s%s", nt_tag, swa_tag);
   return MOJO_OK;
 }
 
-template <typename T>
+template <typename T, bool SWA>
 static int launch_decode(DecodeArgs& a, int64_t batch, int G, hipStream_t s) {
   // K/V are read exactly once: non-temporal loads keep them from displacing the block tables and
   // partials in L2/MALL (measured on MI355X, B=64 ctx=4096: 204 -> 190 us).  MOJO_HIP_STREAM_NT=0 disables (the switch of every
   // streaming kernel, common.h stream_nt()).
   const bool nt = MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0;
-  return nt ? launch_decode_nt<T, true>(a, batch, G, s) : launch_decode_nt<T, false>(a, batch, G, s);
+  return nt ? launch_decode_nt<T, true, SWA>(a, batch, G, s) : launch_decode_nt<T, false, SWA>(a, batch, G, s);
 }
 
 }  // namespace mojo
 
 using namespace mojo;
 
-extern "C" int64_t mojo_hip_paged_decode_gqa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
-                                                             int64_t head_dim, int64_t block_size,
-                                                             int64_t max_blocks_per_seq, int64_t max_seq_len_hint) {
+// The GQA and SWA entry points share one body: with SWA the launch is planned on the visible capacity (decode_swa_cap), the
+// windowed kernel instances run, and the paired and halved forms are not taken.
+static int64_t decode_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                      int64_t max_blocks_per_seq, int64_t max_seq_len_hint, bool swa, int64_t local_window,
+                                      int64_t global_window) {
   if (batch <= 0 || kv_heads <= 0 || q_heads <= 0) return 0;
-  const int64_t max_len = decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint);
+  int64_t max_len = decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint);
+  if (swa) max_len = decode_swa_cap(max_len, local_window, global_window);
   // (groups of 8 query heads can run as two 4-head halves on twice the grid heads — MOJO_HIP_DECODE_G8_HALVES=1 —: size for
   // whichever form cuts the sequences finer)
   int64_t slots = 0;
-  for (int64_t mult = 1; mult <= (q_heads / kv_heads == 8 ? 2 : 1); ++mult) {
+  for (int64_t mult = 1; mult <= (!swa && q_heads / kv_heads == 8 ? 2 : 1); ++mult) {
     const int chunk = decode_chunk_tokens(batch, kv_heads * mult, max_len, decode_grouped(q_heads / (kv_heads * mult), head_dim, block_size));
     const int64_t n_chunks = ceil_div(max_len > 0 ? max_len : 1, chunk);
     const int64_t sl = batch * kv_heads * n_chunks * (q_heads / kv_heads);
@@ -716,14 +781,13 @@ extern "C" int64_t mojo_hip_paged_decode_gqa_workspace_bytes(int64_t batch, int6
   return slots * (head_dim + 2) * static_cast<int64_t>(sizeof(float)) + 256;
 }
 
-extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cache, const void* value_cache,
-                                         const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
-                                         void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
-                                         int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                                         int64_t max_blocks_per_seq, int64_t block_table_stride,
-                                         int64_t cache_block_stride, int64_t cache_head_stride,
-                                         int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
-                                         int layout_abab, int leave_empty_rows, int dtype, mojo_stream_t stream) {
+template <bool SWA>
+static int paged_decode(const void* query, const void* key_cache, const void* value_cache, const int32_t* total_seq_lens,
+                        const int32_t* block_tables, void* out, void* workspace, int64_t workspace_bytes, int64_t batch,
+                        int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size, int64_t max_blocks_per_seq,
+                        int64_t block_table_stride, int64_t cache_block_stride, int64_t cache_head_stride,
+                        int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale, int layout_abab,
+                        int leave_empty_rows, int dtype, int64_t local_window, int64_t global_window, mojo_stream_t stream) {
   if (batch == 0) return MOJO_OK;
   MOJO_REQUIRE(query && key_cache && value_cache && total_seq_lens && block_tables && out, MOJO_EINVAL,
                "paged_decode_gqa: null pointer");
@@ -749,7 +813,15 @@ extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cach
   a.page_shift = (block_size & (block_size - 1)) == 0 ? __builtin_ctzll(block_size) : -1;
   a.table_stride = block_table_stride; a.c_blk = cache_block_stride; a.c_head = cache_head_stride;
   a.c_tok = cache_token_stride;
-  const int64_t max_len = decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint);
+  int64_t max_len = decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint);
+  if constexpr (SWA) {
+    MOJO_REQUIRE(max_len < (int64_t{1} << 30) && local_window < (int64_t{1} << 30) && global_window < (int64_t{1} << 30),
+                 MOJO_EUNSUPPORTED, "paged_decode_swa: lengths and windows must stay below 2^30");
+    a.swa_cap = static_cast<int>(max_len);
+    a.local_win = local_window >= 0 ? static_cast<int>(local_window) : -1;
+    a.global_win = global_window > 0 ? static_cast<int>(global_window) : 0;
+    max_len = decode_swa_cap(max_len, local_window, global_window);
+  }
   // Groups of 8 query heads per kv head (Llama-3-70B: 64 / 8).  Round 2 ran them as two 4-head halves on twice as many grid
   // heads (twice the K/V bytes: 360 us at B 64, ctx 4096) because the 8-head instance spilled; the instance now walks its heads
   // in blocks of four over a two-tile ring with the query slices parked in LDS (232 registers, no spill) and reads K/V once.
@@ -757,7 +829,7 @@ extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cach
   int G = static_cast<int>(q_heads / kv_heads);
   a.hshift = 0;
 #ifdef MOJO_HIP_BUILD_EXPERIMENTS
-  if (G == 8 && MOJO_SWITCH("MOJO_HIP_DECODE_G8_HALVES", 0) == 1) { a.hshift = 1; a.hkv *= 2; G = 4; }
+  if (!SWA && G == 8 && MOJO_SWITCH("MOJO_HIP_DECODE_G8_HALVES", 0) == 1) { a.hshift = 1; a.hkv *= 2; G = 4; }
 #endif
   const bool grouped = decode_grouped(G, head_dim, block_size);
   a.chunk_tokens = decode_chunk_tokens(batch, a.hkv, max_len, grouped);
@@ -774,5 +846,54 @@ extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cach
   a.ws_acc = static_cast<float*>(workspace);
   a.ws_ml = a.ws_acc + slots * head_dim;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return dtype == MOJO_BF16 ? launch_decode<bf16_t>(a, batch, G, s) : launch_decode<f16_t>(a, batch, G, s);
+  return dtype == MOJO_BF16 ? launch_decode<bf16_t, SWA>(a, batch, G, s) : launch_decode<f16_t, SWA>(a, batch, G, s);
+}
+
+extern "C" int64_t mojo_hip_paged_decode_gqa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                             int64_t head_dim, int64_t block_size,
+                                                             int64_t max_blocks_per_seq, int64_t max_seq_len_hint) {
+  return decode_workspace_bytes(batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, false, -1, 0);
+}
+
+extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cache, const void* value_cache,
+                                         const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                         void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                         int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                         int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                         int64_t cache_block_stride, int64_t cache_head_stride,
+                                         int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                         int layout_abab, int leave_empty_rows, int dtype, mojo_stream_t stream) {
+  return paged_decode<false>(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes,
+                             batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                             cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
+                             layout_abab, leave_empty_rows, dtype, -1, 0, stream);
+}
+
+extern "C" int64_t mojo_hip_paged_decode_swa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                             int64_t head_dim, int64_t block_size,
+                                                             int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                             int64_t local_window, int64_t global_window) {
+  const bool swa = local_window >= 0 || global_window > 0;
+  return decode_workspace_bytes(batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, swa,
+                                local_window, global_window);
+}
+
+extern "C" int mojo_hip_paged_decode_swa(const void* query, const void* key_cache, const void* value_cache,
+                                         const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                         void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                         int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                         int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                         int64_t cache_block_stride, int64_t cache_head_stride,
+                                         int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                         int layout_abab, int leave_empty_rows, int dtype, int64_t local_window,
+                                         int64_t global_window, mojo_stream_t stream) {
+  if (local_window < 0 && global_window <= 0)            // no window: the GQA op itself
+    return paged_decode<false>(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes,
+                               batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                               cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
+                               layout_abab, leave_empty_rows, dtype, -1, 0, stream);
+  return paged_decode<true>(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes,
+                            batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                            cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
+                            layout_abab, leave_empty_rows, dtype, local_window, global_window, stream);
 }

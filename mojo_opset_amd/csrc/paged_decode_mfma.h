@@ -55,10 +55,11 @@ template <> struct dec_mma<f16_t> {
 
 constexpr int DECM_TILE = 16;                 // tokens of a sub-tile (one S^T product set, one V image)
 
-template <typename T, int DK /* head_dim / 32 */, bool NT, int MODE>
+template <typename T, int DK /* head_dim / 32 */, bool NT, int MODE, bool SWA = false /* sliding window: DecodeWin */>
 __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kernel(DecodeArgs a, int G) {
   constexpr bool FUSED = MODE != DEC_SPLIT;
   constexpr bool PAIRED = MODE == DEC_PAIRED;
+  static_assert(!(SWA && PAIRED), "the paired form takes no window");
   constexpr int D = DK * 32, ND = D / 16;               // head_dim, 16-wide d tiles of O^T
   constexpr int ROWB = D * 2;                           // bytes of a token row
   constexpr int NP = D / 16;                            // 32-byte pairs per row
@@ -78,6 +79,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   const int kvh = blockIdx.y % a.hkv;
 
   int seq_len, chunk_tokens;
+  DecodeWin win;                                        // (SWA only)
   int pb[2] = {0, -1}, plen[2] = {0, 0}, pchunk[2] = {DEC_TILE, DEC_TILE}, n_first = 8;
   if constexpr (PAIRED) {                               // (identical to decode_split_kernel: the two launches must agree)
     const int cap = a.n_chunks * a.chunk_tokens;
@@ -116,7 +118,8 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
     chunk_tokens = pchunk[u];
     if (b < 0) b = pb[0];
   } else {
-    seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;
+    if constexpr (SWA) seq_len = a.max_pages > 0 ? decode_swa_row(a, b, win) : 0;
+    else seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;
     chunk_tokens = decode_seq_chunk(a, seq_len);
   }
   const int tok_begin = chunk * chunk_tokens;
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
       if (neg && first_neg == 0x7fffffff) first_neg = base + u * 64 + __builtin_ctzll(neg);
     }
   };
-  if (has_work) scan_issue(0);
+  if (!SWA && has_work) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
 
   // K: instruction (token group j, line L) = tokens 8 j + (l & 7), chunk 8 L + (l >> 3);  V: whole rows, RPI rows per instruction
   constexpr int CPR = D / 8;                            // 16-byte chunks per row
@@ -184,7 +187,8 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   auto load_tile = [&](Tile& t, int t0) {
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss) {
-      const int tu = min(t0 + DECM_TILE * ss, last_tile);   // wave-uniform; 16 | page: the sub-tile lies in one page
+      int tu = min(t0 + DECM_TILE * ss, last_tile);         // wave-uniform; 16 | page: the sub-tile lies in one page
+      if constexpr (SWA) tu = decode_swa_real(win, tu);
       const int lp = tu >> a.page_shift;
       t.lp[ss] = lp;
       const int phys = max(table[min(lp, last_page)], 0);
@@ -228,6 +232,18 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
         for (int u = 0; u < NV; ++u) t.v[ss][u] = z;
       }
     const bool full = t0 + STEP <= tok_end;              // wave-uniform
+    int rt[NS];                                          // SWA: real first token of each sub-tile, and whether it holds a window edge
+    bool edge[NS], any_edge = false;
+#pragma unroll
+    for (int ss = 0; ss < NS; ++ss) {
+      rt[ss] = t0 + DECM_TILE * ss;
+      edge[ss] = false;
+      if constexpr (SWA) {
+        rt[ss] = decode_swa_real(win, rt[ss]);
+        edge[ss] = decode_swa_edge(win, rt[ss]);
+        any_edge = any_edge || edge[ss];
+      }
+    }
     float x[NS][4];
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss) {
@@ -244,6 +260,8 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
       // stage V while the scores come out of the matrix pipe (rows past the length may hold NaN / Inf: zeros)
 #pragma unroll
       for (int u = 0; u < NV; ++u) {
+        // (SWA edge tiles: their invisible rows are keys of this sequence in a page it still uses — finite, and their scores are
+        // masked below; only rows past the length may hold anything)
         const bool vrow_ok = full || (t0 + DECM_TILE * ss + RPI * u + vr) < tok_end;
         V8 z = {};
         *reinterpret_cast<V8*>(v_img + ss * (16 * ROWB) + w_off[u]) = vrow_ok ? t.v[ss][u] : z;
@@ -263,12 +281,15 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
         x[ss][i] = (own + oth) * a.scale_log2;
       }
     }
-    if (!full) {
+    if (!full || any_edge) {
 #pragma unroll
       for (int ss = 0; ss < NS; ++ss)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (t0 + DECM_TILE * ss + 4 * g4 + i >= tok_end) x[ss][i] = -INFINITY;
+        for (int i = 0; i < 4; ++i) {
+          bool ok = t0 + DECM_TILE * ss + 4 * g4 + i < tok_end;
+          if constexpr (SWA) ok = ok && (!edge[ss] || decode_swa_vis(win, rt[ss] + 4 * g4 + i));
+          if (!ok) x[ss][i] = -INFINITY;
+        }
     }
     float mx = fmaxf(fmaxf(x[0][0], x[0][1]), fmaxf(x[0][2], x[0][3]));
 #pragma unroll
@@ -307,10 +328,12 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   if (has_work) {
     load_tile(ta, tok_begin);
     if (tok_begin + STEP < tok_end) load_tile(tb, tok_begin + STEP);
-    scan_reduce(0);
-    for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
-      scan_issue(base);
-      scan_reduce(base);
+    if constexpr (!SWA) {
+      scan_reduce(0);
+      for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
+        scan_issue(base);
+        scan_reduce(base);
+      }
     }
     for (int t0 = tok_begin; t0 < tok_end; t0 += 3 * STEP) {
       if (t0 + 2 * STEP < tok_end) load_tile(tc, t0 + 2 * STEP);

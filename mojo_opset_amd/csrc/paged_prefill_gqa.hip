@@ -59,6 +59,9 @@ struct PrefillArgs {
   int w64;                   // 1 (experiments build only): prefill_w64_kernel (experiments/paged_prefill_w64.h): one wave per SIMD, 256-row workgroups, n_qb counts blocks of 256 / G positions
   float* ws_o;               // [blocks * ksplit][128 rows][dim]
   float* ws_ml;              // [blocks * ksplit][128 rows][2]   reference maximum (log2 units), row sum
+  // sliding window (the SWA instances only): key j is visible to the row at position p iff j <= p and (j >= p - local_win or
+  // j < global_win).  No local window: local_win = -2^30 (no key qualifies); no global window: global_win = 0.
+  int local_win = -(1 << 30), global_win = 0;
 };
 
 template <typename T> struct pf_mfma;
@@ -111,7 +114,8 @@ constexpr int PF_TILE_BYTES = PF_KEYS * 256; // 16 KiB per K or V tile
 constexpr int PF_TABLE = 1024;                // block-table entries cached in LDS
 constexpr int PF_LDS = 4 * PF_TILE_BYTES + PF_TABLE * 4 + 16;    // K0 V0 K1 V1 | table slice | first negative page
 
-template <typename T, int G /* q heads per kv head */, int DK /* head_dim / 32 */, bool SPLIT = false /* key split, see PrefillArgs */>
+template <typename T, int G /* q heads per kv head */, int DK /* head_dim / 32 */, bool SPLIT = false /* key split, see PrefillArgs */,
+          bool SWA = false /* sliding window, see below */>
 __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   typedef typename pf_mfma<T>::frag frag;
   constexpr int QPB = 128 / G;               // query positions per workgroup
@@ -215,13 +219,40 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   int kv_hi = min(kv_len, offset + pos_hi + 1);          // keys [0, kv_hi) are visible to some row
   if (kv_hi < 1) kv_hi = 1;
   const int n_kb_all = (kv_hi + PF_KEYS - 1) / PF_KEYS;
+  // Sliding window (MojoPagedPrefillSWA).  The rows of the block sit at positions [p_lo, p_hi]; together they see keys
+  // [0, gend) (global window) and [lstart, kv_hi) (local window of the first row onwards).  The block walks the key tiles of
+  // both ranges and skips the gap between them: in range order, tile v is real tile v (v < gt) or v + gap_t.  When the
+  // ranges overlap they collapse into one (gap_t = 0).  Every tile walked holds a key some row sees, so a page outside the
+  // union of the rows' windows is never staged (keys of the gap inside an edge tile are redirected to a visible key of it).
+  // The WALK order puts the n_whole tiles every row sees whole (range order [u0, u0 + n_whole)) first and the masked ones
+  // (window edges, global range, diagonal) behind them, so the key loops are the unwindowed kernel's: fast-staged whole
+  // tiles, whole tiles, masked tiles — one variant per loop (a loop choosing the variant per tile kept the loop invariants of
+  // all three live at once and spilled).  Order only changes rounding: the online softmax is exact in any order.
+  int n_vkb = n_kb_all, gt = 0, gap_t = 0, gend = 0, lstart = 0, u0 = 0, n_whole = 0;
+  const int p_hi_abs = offset + min(q_len, (qb + 1) * QPB) - 1;
+  if constexpr (SWA) {
+    const int p_lo_abs = offset + qb * QPB;
+    gend = min(a.global_win, kv_hi);
+    gt = (gend + PF_KEYS - 1) / PF_KEYS;
+    lstart = max(p_lo_abs - a.local_win, 0);
+    const int lt = min(lstart / PF_KEYS, n_kb_all);
+    if (lt > gt) { gap_t = lt - gt; n_vkb = n_kb_all - gap_t; }
+  }
+  auto rtile = [&](int j) -> int {                       // real key tile of the j-th tile walked
+    if constexpr (SWA) {
+      const int v = j < n_whole ? u0 + j : (j < n_whole + u0 ? j - n_whole : j);    // walk order -> range order
+      return v >= gt ? v + gap_t : v;
+    } else {
+      return j;
+    }
+  };
   // key tiles [kb_lo, n_kb) of the block belong to this workgroup (unsplit: all of them).  The host chose `ksplit` from the
   // CAPACITY of a sequence (it reads no length); the block itself knows how many tiles it walks, and cuts them into no more
   // slices than leave 8 tiles (512 keys) each: a short block in a split launch would otherwise pay partial writes and a merge
   // over slices of one or two tiles.  Surplus slices publish "no keys seen" and leave.
   int eff = 1;
   if constexpr (SPLIT) {
-    eff = n_kb_all / 8;
+    eff = n_vkb / 8;
     eff = eff < 1 ? 1 : (eff > a.ksplit ? a.ksplit : eff);
     if (ks >= eff) {
       if (threadIdx.x < 128) {
@@ -231,8 +262,8 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
       return;
     }
   }
-  const int kb_lo = SPLIT ? static_cast<int>(static_cast<int64_t>(n_kb_all) * ks / eff) : 0;
-  const int n_kb = SPLIT ? static_cast<int>(static_cast<int64_t>(n_kb_all) * (ks + 1) / eff) : n_kb_all;
+  const int kb_lo = SPLIT ? static_cast<int>(static_cast<int64_t>(n_vkb) * ks / eff) : 0;
+  const int n_kb = SPLIT ? static_cast<int>(static_cast<int64_t>(n_vkb) * (ks + 1) / eff) : n_vkb;
 
   // ---- this wave's rows: two 16-row tiles; row -> (head g, query position) -------------------------------
   int row_pos[2], row_head[2];
@@ -279,14 +310,14 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     for (int j = 0; j < PF_TABLE / 256; ++j) {
       const int i = threadIdx.x + j * 256;
       s_table[i] = ids[j];
-      if (ids[j] < 0 && i < p1) atomicMin(s_fn, i);
+      if (!SWA && ids[j] < 0 && i < p1) atomicMin(s_fn, i);    // (SWA: no hole scan — pages outside the window may hold anything)
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const int wfn = *s_fn;
     if (wfn != 0x7fffffff) {
       fn = wfn;
-    } else {
+    } else if (!SWA) {
       for (int base = PF_TABLE; base < p1; base += 64) {   // contexts past the first window (rare, and long enough to amortise it)
         const int idx = base + lane;
         const int v = idx < p1 ? table[idx] : 0;
@@ -307,7 +338,8 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     {  // wave-uniform for the whole workgroup: all waves stage the same key block
       const int k_last = min(kb * PF_KEYS + PF_KEYS - 1, kv_hi - 1);
       const int p_last = a.page_shift >= 0 ? (k_last >> a.page_shift) : k_last / a.page;
-      if (p_last >= win_base + PF_TABLE) {
+      // (the windowed walk may also go back: its whole tiles come first)
+      if (p_last >= win_base + PF_TABLE || (SWA && kb * PF_KEYS < win_base * a.page)) {
         __syncthreads();
         fill_window(a.page_shift >= 0 ? ((kb * PF_KEYS) >> a.page_shift) : (kb * PF_KEYS) / a.page);
       }
@@ -317,6 +349,9 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
       const int kl = wave * 16 + i * 4 + (lane >> 4);                       // key inside the tile
       int key = kb * PF_KEYS + kl;
       if (key >= kv_hi) key = kv_hi - 1;
+      if constexpr (SWA) {
+        if (key >= gend && key < lstart) key = kb * PF_KEYS < gend ? gend - 1 : lstart;
+      }
       const int lp = a.page_shift >= 0 ? (key >> a.page_shift) : key / a.page;
       int phys = s_table[lp - win_base];
       if (phys < 0) phys = 0;                                               // value is masked later
@@ -367,6 +402,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   // fragment reads are requested and the DMA instructions behind them
   auto stage_fast_base = [&](int kb, int phys) -> int64_t {
     const int key_w = kb * PF_KEYS + wave * 16;
+    if constexpr (SWA) phys = max(phys, 0);            // (no hole scan: a negative id inside the window reads page 0)
     return (static_cast<int64_t>(phys) * a.c_blk + static_cast<int64_t>(key_w & (a.page - 1)) * a.c_tok) * static_cast<int64_t>(sizeof(T));
   };
   // piece i of the 8 DMA instructions of a tile: K (even i) or V (odd i) of the 4 keys i/2 of this wave's 16
@@ -418,11 +454,19 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
 
   // leading key blocks that every row of this workgroup sees completely need no masking at all; the diagonal /
   // tail / hole blocks run the masked variant.  Two loops, so neither carries the other's state.
-  const int n_full = min(min(min(kv_len, offset + qb * QPB + 1), first_neg_key) / PF_KEYS, n_kb);
+  if constexpr (SWA) {
+    // whole tiles: in front of the diagonal (and of a hole) and at or after the window start of the block's LAST row —
+    // in range order [u0, u0 + n_whole), all in the local range (tiles of the global range take the masked variant)
+    const int full_end = min(min(kv_len, offset + qb * QPB + 1), first_neg_key);
+    const int r0 = p_hi_abs - a.local_win <= 0 ? 0 : (p_hi_abs - a.local_win + PF_KEYS - 1) / PF_KEYS;   // (no local window: huge)
+    u0 = min(max(r0 - gap_t, 0), n_vkb);
+    n_whole = min(max(full_end / PF_KEYS - gap_t, u0), n_vkb) - u0;
+  }
+  const int n_full = SWA ? min(n_whole, n_kb) : min(min(min(kv_len, offset + qb * QPB + 1), first_neg_key) / PF_KEYS, n_kb);
   const int n_fast = a.fast_stage ? n_full : 0;          // tiles [0, n_fast) may be staged the fast way
 
-  if (kb_lo < n_kb) stage(kb_lo, kb_lo & 1);
-  int phys_next = a.fast_stage ? page_of_tile(kb_lo + 1) : 0;    // page id for the NEXT stage, loaded a tile ahead
+  if (kb_lo < n_kb) stage(rtile(kb_lo), kb_lo & 1);
+  int phys_next = a.fast_stage ? page_of_tile(rtile(kb_lo + 1)) : 0;    // page id for the NEXT stage, loaded a tile ahead
   // q * scale * log2(e), rounded once to the storage type: the scores leave the MFMA chain in log2 units
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
@@ -451,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     const char* stage_v = nullptr;
     if constexpr (FAST) {
       page_ready(phys_next);
-      stage_base = stage_fast_base(kb + 1, phys_next);
+      stage_base = stage_fast_base(rtile(kb + 1), phys_next);
       asm volatile("" : "+s"(stage_base));               // computed here, not sunk behind the reads
       stage_k = reinterpret_cast<const char*>(kbase) + stage_base;
       stage_v = reinterpret_cast<const char*>(vbase) + stage_base;
@@ -503,7 +547,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     // instruction at a time between the softmax's vector instructions, where a piece costs a third of what it costs
     // next to LDS reads.
     if constexpr (!FAST) {
-      if (kb + 1 < n_kb) stage(kb + 1, buf ^ 1);
+      if (kb + 1 < n_kb) stage(rtile(kb + 1), buf ^ 1);
     }
     auto dma_piece = [&](int i) {
       if constexpr (FAST) {
@@ -594,8 +638,8 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
       }
     };
     // lane holds, for query column l15 of each q tile, keys  kb*64 + 16t + 4*grp + r
-    const int key0 = kb * PF_KEYS + 4 * grp;
-    const bool has_hole = MASKED && (kb + 1) * PF_KEYS > first_neg_key;
+    const int key0 = rtile(kb) * PF_KEYS + 4 * grp;
+    const bool has_hole = MASKED && (SWA ? rtile(kb) + 1 : kb + 1) * PF_KEYS > first_neg_key;   // (SWA: the real tile)
     frag pf[2][2];                                                                   // [q tile][32-key step]
     // p = 2^s, ONE vector instruction per element ahead of the conversion: Q was multiplied by scale * log2(e) when it was
     // loaded and the accumulators of S were seeded with -m, so s arrives as (q.k * scale - m) * log2(e) (a lone wave hides
@@ -617,6 +661,9 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
             const int key = key0 + 16 * t + r;
             if (has_hole && key >= first_neg_key) sc[t][r] = seed[qt];   // zero K rows: score 0 (relative to the reference)
             if (key > offset + row_pos[qt] || key >= kv_len) sc[t][r] = -INFINITY;
+            if constexpr (SWA) {
+              if (key >= a.global_win && key < offset + row_pos[qt] - a.local_win) sc[t][r] = -INFINITY;
+            }
           }
       }
       // lane maximum of its 16 scores as a CHAIN max(max(m, x), y): hipcc folds each link into one v_max3 (8 instructions; a
@@ -676,7 +723,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     // the page id of tile kb + 2 (a whole tile ahead of its use).  Requested HERE, behind the QK^T MFMAs: a scalar load in flight
     // makes every LDS wait an lgkmcnt(0) (scalar loads return out of order), and in front of the K fragment reads that meant
     // the first MFMA waited for all sixteen of them instead of the first four.
-    if constexpr (FAST) phys_next = page_of_tile(kb + 2);
+    if constexpr (FAST) phys_next = page_of_tile(rtile(kb + 2));
     issue_v(vb0, 0);
     softmax_tile(0);
     softmax_tile(1);
@@ -866,12 +913,21 @@ namespace mojo { constexpr int W64_TABLE = 0; }
 #endif
 namespace mojo {
 
-template <typename T, int G, int DK>
+template <typename T, int G, int DK, bool SWA>
 static void launch_pf(const PrefillArgs& a, dim3 grid, hipStream_t s) {
   static std::atomic<uint64_t> attr_set{0};
   if (first_call_on_device(attr_set)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, false, SWA>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, true, SWA>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
+  }
+  if constexpr (SWA) {                                   // (the experiments-build kernels take no window)
+    if (a.ksplit > 1) {
+      hipLaunchKernelGGL((prefill_kernel<T, G, DK, true, true>), grid, dim3(256), PF_LDS, s, a);
+      hipLaunchKernelGGL((prefill_merge_kernel<T, G>), dim3(static_cast<unsigned>(a.n_qb * a.hkv * a.batch * PF_MERGE_SPLIT)), dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((prefill_kernel<T, G, DK, false, true>), grid, dim3(256), PF_LDS, s, a);
+    }
+    return;
   }
 #ifdef MOJO_HIP_BUILD_EXPERIMENTS
   if (a.pp) {
@@ -919,16 +975,17 @@ static void launch_pf(const PrefillArgs& a, dim3 grid, hipStream_t s) {
   }
 }
 
-template <typename T, int G>
+template <typename T, int G, bool SWA>
 static int dispatch_dk(const PrefillArgs& a, dim3 grid, hipStream_t s) {
   switch (a.dim) {
-    case 64: launch_pf<T, G, 2>(a, grid, s); break;
-    case 96: launch_pf<T, G, 3>(a, grid, s); break;
-    case 128: launch_pf<T, G, 4>(a, grid, s); break;
+    case 64: launch_pf<T, G, 2, SWA>(a, grid, s); break;
+    case 96: launch_pf<T, G, 3, SWA>(a, grid, s); break;
+    case 128: launch_pf<T, G, 4, SWA>(a, grid, s); break;
     default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_prefill_gqa: head_dim %d (64, 96, 128)", a.dim);
   }
   MOJO_CHECK_LAUNCH("paged_prefill_gqa");
-  note_launch("prefill:%s:%s:ksplit%d", a.pp ? "pp" : a.w64 ? "w64" : a.m32 ? "m32" : "default", a.fast_stage ? "fast_stage" : "general_stage", a.ksplit);
+  note_launch(SWA ? "prefill:%s:%s:ksplit%d:swa" : "prefill:%s:%s:ksplit%d", a.pp ? "pp" : a.w64 ? "w64" : a.m32 ? "m32" : "default",
+              a.fast_stage ? "fast_stage" : "general_stage", a.ksplit);
   return MOJO_OK;
 }
 
@@ -957,14 +1014,14 @@ static bool prefill_use_pp(int64_t max_q) {
   return false;
 }
 
-template <typename T>
+template <typename T, bool SWA>
 static int dispatch_g(PrefillArgs a, int G, int64_t batch, int64_t max_q, hipStream_t s) {
   // Experiments build only: the phase-alternating kernel takes unsplit launches over pages it can stage with scalar page
   // ids when MOJO_HIP_PREFILL_PP=1.
-  a.pp = (a.ksplit == 1 && a.fast_stage && a.max_pages <= PP_TABLE && prefill_use_pp(max_q)) ? 1 : 0;
-  a.w64 = (!a.pp && a.ksplit == 1 && a.fast_stage && a.dim == 128 && a.max_pages <= W64_TABLE - 16 &&
+  a.pp = (!SWA && a.ksplit == 1 && a.fast_stage && a.max_pages <= PP_TABLE && prefill_use_pp(max_q)) ? 1 : 0;
+  a.w64 = (!SWA && !a.pp && a.ksplit == 1 && a.fast_stage && a.dim == 128 && a.max_pages <= W64_TABLE - 16 &&
            prefill_use_w64(max_q, batch, a.hkv, G)) ? 1 : 0;
-  a.m32 = (!a.pp && !a.w64 && a.dim == 128 && prefill_use_m32()) ? 1 : 0;
+  a.m32 = (!SWA && !a.pp && !a.w64 && a.dim == 128 && prefill_use_m32()) ? 1 : 0;
   const int qpb = ((a.pp || a.w64) ? 256 : 128) / G;
   const int64_t n_qb = ceil_div(max_q, qpb);
   const int64_t n_zero = ceil_div(a.total_tokens, static_cast<int64_t>(PF_ZERO_TOKENS));
@@ -977,10 +1034,10 @@ static int dispatch_g(PrefillArgs a, int G, int64_t batch, int64_t max_q, hipStr
 #endif
   dim3 grid(static_cast<unsigned>((n_qb * a.hkv * batch + n_zero) * a.ksplit));
   switch (G) {
-    case 1: return dispatch_dk<T, 1>(a, grid, s);
-    case 2: return dispatch_dk<T, 2>(a, grid, s);
-    case 4: return dispatch_dk<T, 4>(a, grid, s);
-    case 8: return dispatch_dk<T, 8>(a, grid, s);
+    case 1: return dispatch_dk<T, 1, SWA>(a, grid, s);
+    case 2: return dispatch_dk<T, 2, SWA>(a, grid, s);
+    case 4: return dispatch_dk<T, 4, SWA>(a, grid, s);
+    case 8: return dispatch_dk<T, 8, SWA>(a, grid, s);
     default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_prefill_gqa: group size %d (1, 2, 4, 8)", G);
   }
 }
@@ -1001,12 +1058,18 @@ static int prefill_ksplit(int64_t blocks, int64_t kv_cap) {
 }
 
 static void prefill_plan(int64_t total_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t block_size,
-                         int64_t max_blocks_per_seq, int64_t max_q_len_hint, int64_t max_kv_len_hint, int64_t& n_qb, int& ksplit) {
+                         int64_t max_blocks_per_seq, int64_t max_q_len_hint, int64_t max_kv_len_hint, int64_t& n_qb, int& ksplit,
+                         int64_t local_window = -1, int64_t global_window = 0) {
   const int G = static_cast<int>(q_heads / kv_heads);
   const int64_t max_q = (max_q_len_hint > 0 && max_q_len_hint < total_tokens) ? max_q_len_hint : total_tokens;
   n_qb = ceil_div(max_q, 128 / (G > 0 ? G : 1));
   int64_t kv_cap = block_size * max_blocks_per_seq;
   if (max_kv_len_hint > 0 && max_kv_len_hint < kv_cap) kv_cap = max_kv_len_hint;
+  if (local_window >= 0 || global_window > 0) {          // sliding window: the keys one block can see, not the table's capacity
+    int64_t span = global_window > 0 ? global_window : 0;
+    if (local_window >= 0) span += local_window + 128 / (G > 0 ? G : 1);
+    if (span < kv_cap) kv_cap = span;
+  }
   ksplit = prefill_ksplit(n_qb * kv_heads * batch, kv_cap);
 }
 
@@ -1014,27 +1077,27 @@ static void prefill_plan(int64_t total_tokens, int64_t batch, int64_t q_heads, i
 
 using namespace mojo;
 
-extern "C" int64_t mojo_hip_paged_prefill_gqa_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
-                                                              int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                                                              int64_t max_blocks_per_seq, int64_t max_q_len_hint,
-                                                              int64_t max_kv_len_hint) {
+static int64_t prefill_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                                       int64_t block_size, int64_t max_blocks_per_seq, int64_t max_q_len_hint,
+                                       int64_t max_kv_len_hint, int64_t local_window, int64_t global_window) {
   if (total_tokens <= 0 || batch <= 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return 0;
   int64_t n_qb;
   int ks;
-  prefill_plan(total_tokens, batch, q_heads, kv_heads, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint, n_qb, ks);
+  prefill_plan(total_tokens, batch, q_heads, kv_heads, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint, n_qb, ks,
+               local_window, global_window);
   if (ks <= 1) return 0;
   return n_qb * kv_heads * batch * ks * 128 * (head_dim + 2) * static_cast<int64_t>(sizeof(float)) + 64;
 }
 
-extern "C" int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cache, const void* value_cache,
-                                          const int32_t* cu_q_lens, const int32_t* cu_total_seq_lens,
-                                          const int32_t* block_tables, void* out, int64_t total_tokens, int64_t batch,
-                                          int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                                          int64_t max_blocks_per_seq, int64_t block_table_stride,
-                                          int64_t cache_block_stride, int64_t cache_head_stride,
-                                          int64_t cache_token_stride, int64_t max_q_len_hint, int64_t max_kv_len_hint,
-                                          float softmax_scale, int layout_abab, int dtype, void* workspace,
-                                          int64_t workspace_bytes, mojo_stream_t stream) {
+// The GQA and SWA entry points share one body (SWA: the windowed kernel instances, key split sized on the visible keys).
+template <bool SWA>
+static int paged_prefill(const void* query, const void* key_cache, const void* value_cache, const int32_t* cu_q_lens,
+                         const int32_t* cu_total_seq_lens, const int32_t* block_tables, void* out, int64_t total_tokens,
+                         int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                         int64_t max_blocks_per_seq, int64_t block_table_stride, int64_t cache_block_stride,
+                         int64_t cache_head_stride, int64_t cache_token_stride, int64_t max_q_len_hint,
+                         int64_t max_kv_len_hint, float softmax_scale, int layout_abab, int dtype, void* workspace,
+                         int64_t workspace_bytes, int64_t local_window, int64_t global_window, mojo_stream_t stream) {
   if (total_tokens == 0) return MOJO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   MOJO_REQUIRE(query && key_cache && value_cache && cu_q_lens && block_tables && out, MOJO_EINVAL,
@@ -1065,6 +1128,16 @@ extern "C" int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cac
   a.max_pages = static_cast<int>(max_blocks_per_seq);
   a.scale_log2 = softmax_scale * 1.4426950408889634f;
   a.abab = layout_abab ? 1 : 0;
+  if constexpr (SWA) {
+    MOJO_REQUIRE(local_window < (int64_t{1} << 29) && global_window < (int64_t{1} << 29) &&
+                     block_size * max_blocks_per_seq < (int64_t{1} << 29),
+                 MOJO_EUNSUPPORTED, "paged_prefill_swa: lengths and windows must stay below 2^29");
+    a.local_win = local_window >= 0 ? static_cast<int>(local_window) : -(1 << 30);
+    a.global_win = global_window > 0 ? static_cast<int>(global_window) : 0;
+  } else {
+    local_window = -1;
+    global_window = 0;
+  }
   const bool no_fs = MOJO_SWITCH("MOJO_HIP_PREFILL_FAST_STAGE", 1) == 0;        // 0: general staging everywhere (tests)
   a.fast_stage = (a.page_shift >= 4 && cache_token_stride * 16 * 2 + 256 < (int64_t{1} << 31) && !no_fs) ? 1 : 0;
   int64_t max_q = (max_q_len_hint > 0 && max_q_len_hint < total_tokens) ? max_q_len_hint : total_tokens;
@@ -1072,7 +1145,8 @@ extern "C" int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cac
   {
     int64_t n_qb;
     int ks;
-    prefill_plan(total_tokens, batch, q_heads, kv_heads, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint, n_qb, ks);
+    prefill_plan(total_tokens, batch, q_heads, kv_heads, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint, n_qb, ks,
+                 local_window, global_window);
     const int64_t rows = n_qb * kv_heads * batch * ks * 128;
     const int64_t need = rows * (head_dim + 2) * static_cast<int64_t>(sizeof(float));
     if (ks > 1 && !(workspace && workspace_bytes >= need && aligned_to(workspace, 16))) ks = 1;   // no workspace: run unsplit
@@ -1080,7 +1154,60 @@ extern "C" int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cac
     a.ws_o = ks > 1 ? static_cast<float*>(workspace) : nullptr;
     a.ws_ml = ks > 1 ? a.ws_o + rows * head_dim : nullptr;
   }
-  return dtype == MOJO_BF16 ? dispatch_g<bf16_t>(a, G, batch, max_q, s) : dispatch_g<f16_t>(a, G, batch, max_q, s);
+  return dtype == MOJO_BF16 ? dispatch_g<bf16_t, SWA>(a, G, batch, max_q, s) : dispatch_g<f16_t, SWA>(a, G, batch, max_q, s);
+}
+
+extern "C" int64_t mojo_hip_paged_prefill_gqa_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
+                                                              int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                                              int64_t max_blocks_per_seq, int64_t max_q_len_hint,
+                                                              int64_t max_kv_len_hint) {
+  return prefill_workspace_bytes(total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
+                                 max_kv_len_hint, -1, 0);
+}
+
+extern "C" int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cache, const void* value_cache,
+                                          const int32_t* cu_q_lens, const int32_t* cu_total_seq_lens,
+                                          const int32_t* block_tables, void* out, int64_t total_tokens, int64_t batch,
+                                          int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                          int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                          int64_t cache_block_stride, int64_t cache_head_stride,
+                                          int64_t cache_token_stride, int64_t max_q_len_hint, int64_t max_kv_len_hint,
+                                          float softmax_scale, int layout_abab, int dtype, void* workspace,
+                                          int64_t workspace_bytes, mojo_stream_t stream) {
+  return paged_prefill<false>(query, key_cache, value_cache, cu_q_lens, cu_total_seq_lens, block_tables, out, total_tokens, batch,
+                              q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride, cache_block_stride,
+                              cache_head_stride, cache_token_stride, max_q_len_hint, max_kv_len_hint, softmax_scale, layout_abab,
+                              dtype, workspace, workspace_bytes, -1, 0, stream);
+}
+
+extern "C" int64_t mojo_hip_paged_prefill_swa_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
+                                                              int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                                              int64_t max_blocks_per_seq, int64_t max_q_len_hint,
+                                                              int64_t max_kv_len_hint, int64_t local_window,
+                                                              int64_t global_window) {
+  return prefill_workspace_bytes(total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
+                                 max_kv_len_hint, local_window, global_window);
+}
+
+extern "C" int mojo_hip_paged_prefill_swa(const void* query, const void* key_cache, const void* value_cache,
+                                          const int32_t* cu_q_lens, const int32_t* cu_total_seq_lens,
+                                          const int32_t* block_tables, void* out, int64_t total_tokens, int64_t batch,
+                                          int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                          int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                          int64_t cache_block_stride, int64_t cache_head_stride,
+                                          int64_t cache_token_stride, int64_t max_q_len_hint, int64_t max_kv_len_hint,
+                                          float softmax_scale, int layout_abab, int dtype, void* workspace,
+                                          int64_t workspace_bytes, int64_t local_window, int64_t global_window,
+                                          mojo_stream_t stream) {
+  if (local_window < 0 && global_window <= 0)            // no window: the GQA op itself
+    return paged_prefill<false>(query, key_cache, value_cache, cu_q_lens, cu_total_seq_lens, block_tables, out, total_tokens,
+                                batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                                cache_block_stride, cache_head_stride, cache_token_stride, max_q_len_hint, max_kv_len_hint,
+                                softmax_scale, layout_abab, dtype, workspace, workspace_bytes, -1, 0, stream);
+  return paged_prefill<true>(query, key_cache, value_cache, cu_q_lens, cu_total_seq_lens, block_tables, out, total_tokens, batch,
+                             q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride, cache_block_stride,
+                             cache_head_stride, cache_token_stride, max_q_len_hint, max_kv_len_hint, softmax_scale, layout_abab,
+                             dtype, workspace, workspace_bytes, local_window, global_window, stream);
 }
 
 #if defined(PF_STAMPS) || defined(PF_WG_STAMPS)
