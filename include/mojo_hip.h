@@ -362,6 +362,73 @@ int mojo_hip_paged_prefill_swa(const void* query, const void* key_cache, const v
                                int layout_abab, int dtype, void* workspace, int64_t workspace_bytes,
                                int64_t local_window, int64_t global_window, mojo_stream_t stream);
 
+/* ---- int8 paged KV cache with per-channel scales ("C8"; experimental/operators/kv_cache.py:109-184,
+ *      experimental/operators/attention.py:461-800).  Caches are int8 [N, Hkv, page, D] (strides in elements = bytes, 16-byte
+ *      rows), scales [Hkv, D] dense, scale_dtype one of MOJO_BF16 / MOJO_F16 / MOJO_F32, taken as given (no cast launch).
+ *      store: per element round(state / scale).clamp(-128, 127) under torch's type promotion, bit for bit — fp32 division,
+ *      the quotient rounded to the state dtype first when state and scale share a 16-bit dtype, round half to even.  States
+ *      bf16 / fp16 (state_dtype), strides in elements; plan and legacy forms, refusals and padded rows as
+ *      mojo_hip_store_paged_kv_plan / _layout.
+ *      decode: q' = q * key_scale (rounded to fp16), S = softmax_scale * q' K8^T, O = value_scale * (P V8) / l; both
+ *      contractions on the matrix cores in fp16 whatever the query dtype (int8 -> fp16 is exact), outputs in the query dtype
+ *      (`dtype`: MOJO_BF16 / MOJO_F16).  head_dim 64 / 80 / 96 / 128, pages of a multiple of 16 tokens, groups of 1..16 query
+ *      heads; hints, workspace, leave_empty_rows, holes, empty rows and truncation as mojo_hip_paged_decode_gqa.
+ *      prefill: one dequantising gather (the pages inside each sequence's length -> 16-bit scratch pages holding K8 * key_scale
+ *      and V8 * value_scale rounded to the query dtype, and a scratch block table) followed by the code path of
+ *      mojo_hip_paged_prefill_gqa on the scratch; envelope of that entry point (groups 1 / 2 / 4 / 8; head_dim 64 / 96 / 128).
+ *      The workspace (256-byte aligned) holds batch * ceil(min(max_kv_len_hint, page * max_blocks_per_seq) / page) scratch
+ *      pages of K and of V: without the hint a wide table is paid for at its capacity.  max_kv_len_hint, when > 0, MUST be
+ *      an upper bound of every sequence's kv length (it sizes the scratch: keys past it are not gathered and read as zero
+ *      keys; in the 16-bit entry point the hint only steers planning).  num_blocks bounds the page ids (an id outside
+ *      [0, num_blocks) reads as zeros).  decode: q' is fp16 also for bf16 queries, so |q * key_scale| saturates at 65504 and
+ *      is subnormal below 6.1e-5.  The decode entry point obeys MOJO_HIP_DECODE_FUSE, MOJO_HIP_DECODE_CHUNK and
+ *      MOJO_HIP_STREAM_NT; the prefill one the prefill switches, through the code path it shares.                          */
+int mojo_hip_store_paged_kv_c8_plan(const void* key_states, const void* value_states, void* key_cache,
+                                    void* value_cache, const void* key_scale, const void* value_scale,
+                                    const int32_t* plan, int64_t num_chunks, int64_t num_tokens,
+                                    int64_t num_kv_heads, int64_t head_dim, int64_t num_blocks,
+                                    int64_t block_size, int state_dtype, int scale_dtype,
+                                    int64_t src_token_stride, int64_t src_head_stride,
+                                    int64_t cache_block_stride, int64_t cache_head_stride,
+                                    int64_t cache_token_stride, mojo_stream_t stream);
+int mojo_hip_store_paged_kv_c8_layout(const void* key_states, const void* value_states, void* key_cache,
+                                      void* value_cache, const void* key_scale, const void* value_scale,
+                                      const int32_t* block_table, int64_t block_table_stride,
+                                      int64_t max_blocks_per_seq, const int32_t* cu_q_lens,
+                                      const int32_t* context_kv_lens, int64_t batch, int64_t num_tokens,
+                                      int64_t num_kv_heads, int64_t head_dim, int64_t num_blocks,
+                                      int64_t block_size, int state_dtype, int scale_dtype,
+                                      int64_t src_token_stride, int64_t src_head_stride,
+                                      int64_t cache_block_stride, int64_t cache_head_stride,
+                                      int64_t cache_token_stride, mojo_stream_t stream);
+int64_t mojo_hip_paged_decode_gqa_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                      int64_t head_dim, int64_t block_size,
+                                                      int64_t max_blocks_per_seq, int64_t max_seq_len_hint);
+int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                  const void* value_cache, const void* value_scale,
+                                  const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                  void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                  int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                  int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                  int64_t cache_block_stride, int64_t cache_head_stride,
+                                  int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                  int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
+                                  mojo_stream_t stream);
+int64_t mojo_hip_paged_prefill_gqa_kv8_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
+                                                       int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                                       int64_t max_blocks_per_seq, int64_t max_q_len_hint,
+                                                       int64_t max_kv_len_hint);
+int mojo_hip_paged_prefill_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                   const void* value_cache, const void* value_scale, const int32_t* cu_q_lens,
+                                   const int32_t* cu_total_seq_lens, const int32_t* block_tables, void* out,
+                                   int64_t total_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                   int64_t head_dim, int64_t num_blocks, int64_t block_size,
+                                   int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                   int64_t cache_block_stride, int64_t cache_head_stride,
+                                   int64_t cache_token_stride, int64_t max_q_len_hint, int64_t max_kv_len_hint,
+                                   float softmax_scale, int layout_abab, int dtype, int scale_dtype,
+                                   void* workspace, int64_t workspace_bytes, mojo_stream_t stream);
+
 /* ---- MoE routing either side of the grouped GEMM (core/operators/moe.py).
  *      gating (:299-316): softmax(hidden.float() @ gate_weight [hidden, E] fp32) over all experts, top-k in descending
  *      order (ties: lowest expert id), gates renormalised to sum 1.  top_k <= min(E, 64), E <= 1024.  With many

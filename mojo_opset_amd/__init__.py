@@ -8,11 +8,15 @@ registers the ``HIP<Op>`` backend classes.  Backend selection follows the refere
 ``__all__`` is the SURVEY §8 set, whose torch goldens live in the repo-level ``oracle/`` package.  Ops beyond §8
 (``EXTENDED_OPS``: the sliding-window pair ``MojoPagedDecodeSWA`` / ``MojoPagedPrefillSWA``) are package attributes
 too, but not in ``__all__``; their goldens are test infrastructure under ``tests/`` (``tests/swa_golden.py``).
-``plugin.rebase_hip_backend`` registers both sets into the reference.
+So are the ops of the int8 paged KV cache (``KV_INT8_OPS``: ``MojoStorePagedKVCacheC8``,
+``MojoPagedDecodeGQAWithKVDequant``, ``MojoPagedPrefillGQAWithKVDequant``; goldens in ``tests/kv_int8_golden.py``).
+``plugin.rebase_hip_backend`` registers all three sets into the reference.
 """
 from .core import *  # noqa: F401,F403
 from .core import __all__ as _core_all
 from .core import EXTENDED_OPS, MojoPagedDecodeSWA, MojoPagedPrefillSWA  # noqa: F401
+from .core import (KV_INT8_OPS, MojoPagedDecodeGQAWithKVDequant, MojoPagedPrefillGQAWithKVDequant,  # noqa: F401
+                   MojoStorePagedKVCacheC8)
 from . import backends  # noqa: F401  (registers HIP<Op> classes)
 from .paged_cache import PagedDummyCache  # noqa: E402  device-side block allocator (SURVEY §8 f4)
 

@@ -4,6 +4,7 @@ On a host without a ROCm GPU the classes still import (so their signatures can b
 the registry ignores them; on a ROCm host they are the first-priority backend.
 """
 from .operators.attention import *  # noqa: F401,F403
+from .operators.kv_int8 import *  # noqa: F401,F403
 from .operators.streaming import *  # noqa: F401,F403
 from .operators.gemm import HIPGemm, HIPGroupGemm, HIPQuantGemm, HIPSwiGLUMLP  # noqa: F401
 from .operators.mla import HIPPagedDecodeMLA, HIPPagedPrefillMLA  # noqa: F401

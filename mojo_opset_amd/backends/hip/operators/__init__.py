@@ -1,4 +1,5 @@
 from .attention import *  # noqa: F401,F403
+from .kv_int8 import *  # noqa: F401,F403
 from .gemm import HIPGemm, HIPGroupGemm, HIPQuantGemm, HIPSwiGLUMLP  # noqa: F401
 from .streaming import *  # noqa: F401,F403
 from .mla import *  # noqa: F401,F403

@@ -1,8 +1,10 @@
 from .activation import MojoSwiGLU
-from .attention import MojoPagedDecodeGQA, MojoPagedDecodeSWA, MojoPagedPrefillGQA, MojoPagedPrefillSWA
+from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeSWA, MojoPagedPrefillGQA,
+                        MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
-from .kv_cache import MojoStorePagedKVCache, MojoStorePagedMLAKVCache, build_paged_kv_chunk_metadata
+from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
+                       build_paged_kv_chunk_metadata)
 from .mla import MojoPagedDecodeMLA, MojoPagedPrefillMLA
 from .mlp import MojoSwiGLUMLP
 from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating
@@ -22,3 +24,5 @@ __all__ = [
 # Ops beyond the SURVEY §8 set: importable, but not in `__all__` (whose goldens live in the repo-level `oracle/`); their
 # goldens are test infrastructure under `tests/`.
 EXTENDED_OPS = ("MojoPagedDecodeSWA", "MojoPagedPrefillSWA")
+# The int8 paged KV cache with per-channel scales (the reference's experimental "C8" path): same standing as EXTENDED_OPS.
+KV_INT8_OPS = ("MojoStorePagedKVCacheC8", "MojoPagedDecodeGQAWithKVDequant", "MojoPagedPrefillGQAWithKVDequant")

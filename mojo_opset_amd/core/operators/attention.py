@@ -125,3 +125,59 @@ class MojoPagedPrefillSWA(_PagedSWABase, MojoOperator):
                  local_window_size: Optional[int] = None):
         super().__init__()
         self._init_swa(is_causal, gqa_layout, global_window_size, local_window_size)
+
+
+class _PagedGQAKVDequantBase:
+    """Constructor of the int8-cache pair (`mojo_opset/experimental/operators/attention.py:464-499`, :638-681): the
+    attributes ``is_causal``, ``gqa_layout``, ``query_dtype``, ``context_dtype``, ``compute_dtype`` (and ``qmax`` /
+    ``qmin`` with ``compute_dtype=torch.int8``) are all a backend may read."""
+
+    def _init_kv_dequant(self, is_causal, gqa_layout, query_dtype, context_dtype, compute_dtype) -> None:
+        if gqa_layout not in _GQA_LAYOUTS:
+            raise ValueError(f"gqa_layout must be one of ['ABAB', 'AABB'], got {gqa_layout}")
+        self.is_causal = is_causal
+        self.gqa_layout = gqa_layout
+        self.query_dtype = query_dtype
+        self.context_dtype = context_dtype
+        self.compute_dtype = compute_dtype
+        assert self.query_dtype in (torch.bfloat16, torch.int8), f"Unsupported query dtype {self.query_dtype}"
+        if self.query_dtype == torch.int8:
+            raise NotImplementedError("Quantized query is not implemented")
+        assert self.context_dtype == torch.int8, f"Quant attention support int8 context only, but got {self.context_dtype}"
+        assert self.compute_dtype in (torch.bfloat16, torch.int8), f"Unsupported compute dtype {self.compute_dtype}"
+        if self.compute_dtype == torch.int8:
+            self.qmax = 127
+            self.qmin = -128
+
+    def extra_repr(self) -> str:
+        return (f"is_causal={self.is_causal!r}, gqa_layout={self.gqa_layout!r}, query_dtype={self.query_dtype!r}, "
+                f"context_dtype={self.context_dtype!r}, compute_dtype={self.compute_dtype!r}")
+
+
+class MojoPagedDecodeGQAWithKVDequant(_PagedGQAKVDequantBase, MojoOperator):
+    """`MojoPagedDecodeGQA` over an int8 K/V cache with per-channel scales.
+
+    forward(query [B,Hq,D], query_scale (None: the query is not quantised), key_cache [N,Hkv,page,D] int8,
+            key_scale [Hkv,D], value_cache int8, value_scale [Hkv,D], total_seq_lens [B] i32, block_tables [B,nb] i32,
+            softmax_scale=None, mask=None, *, max_total_seq_len=None) -> [B,Hq,D]; rows of length 0 are zeros.
+    A key is ``K8 * key_scale``, a value ``V8 * value_scale``.
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", query_dtype: torch.dtype = torch.bfloat16,
+                 context_dtype: torch.dtype = torch.int8, compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        self._init_kv_dequant(is_causal, gqa_layout, query_dtype, context_dtype, compute_dtype)
+
+
+class MojoPagedPrefillGQAWithKVDequant(_PagedGQAKVDequantBase, MojoOperator):
+    """`MojoPagedPrefillGQA` over an int8 K/V cache with per-channel scales.
+
+    forward(query [T,Hq,D], query_scale (None), key_cache int8, key_scale [Hkv,D], value_cache int8, value_scale [Hkv,D],
+            cu_q_lens [B+1] i32, block_tables [B,nb] i32, softmax_scale=None, cu_total_seq_lens=None, mask=None,
+            max_q_len=None, max_total_seq_len=None) -> [T,Hq,D]
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", query_dtype: torch.dtype = torch.bfloat16,
+                 context_dtype: torch.dtype = torch.int8, compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        self._init_kv_dequant(is_causal, gqa_layout, query_dtype, context_dtype, compute_dtype)

@@ -107,3 +107,17 @@ class MojoStorePagedMLAKVCache(MojoOperator):
 
     def __init__(self):
         super().__init__()
+
+
+class MojoStorePagedKVCacheC8(MojoOperator):
+    """forward(key_states, value_states [T,Hkv,D], key_cache, value_cache [N,Hkv,page,D] int8, key_scale, value_scale
+    [Hkv,D], block_table=None, cu_q_lens=None, context_kv_lens=None, *, chunk_metadata=None)
+    -> (key_cache, value_cache), written **in place** with ``round(state / scale).clamp(-128, 127)`` as int8.
+
+    Follows `mojo_opset/experimental/operators/kv_cache.py:109-184`; arguments and plan rows as `MojoStorePagedKVCache`.
+    """
+
+    def __init__(self):
+        super().__init__()
+
+    check_call_contract = staticmethod(MojoStorePagedKVCache.check_call_contract)

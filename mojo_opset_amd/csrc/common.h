@@ -215,6 +215,30 @@ __device__ __forceinline__ T round_with_bias(float acc, T bias, bool fused) {
 template <typename T, int N> struct vec_of { typedef T type __attribute__((ext_vector_type(N))); };
 template <typename T> struct vec_of<T, 1> { typedef T type; };
 
+// The per-channel scales of the int8 KV cache ops (and their 16-bit queries) are taken in the caller's dtype, named by a run-time
+// code (MOJO_F32 / MOJO_F16 / anything else: MOJO_BF16), without a cast launch.
+// N (4 or 8) consecutive elements from element i on, with vector loads: i a multiple of N and the tensor 16-byte aligned
+template <int N>
+__device__ __forceinline__ void load_coded_f32_vec(const void* p, int code, int64_t i, float (&out)[N]) {
+  static_assert(N == 4 || N == 8, "4 or 8 elements");
+  if (code == MOJO_F32) {
+#pragma unroll
+    for (int k = 0; k < N / 4; ++k) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(static_cast<const float*>(p) + i + 4 * k);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) out[4 * k + e] = v[e];
+    }
+    return;
+  }
+  typedef unsigned int words_t __attribute__((ext_vector_type(N / 2)));
+  const words_t w = *reinterpret_cast<const words_t*>(static_cast<const unsigned short*>(p) + i);
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    const unsigned short bits = static_cast<unsigned short>(w[e >> 1] >> ((e & 1) * 16));
+    out[e] = code == MOJO_F16 ? static_cast<float>(__builtin_bit_cast(f16_t, bits)) : __builtin_bit_cast(float, static_cast<unsigned>(bits) << 16);
+  }
+}
+
 template <typename T, int N>
 __device__ __forceinline__ typename vec_of<T, N>::type load_vec(const T* p) {
   return *reinterpret_cast<const typename vec_of<T, N>::type*>(p);

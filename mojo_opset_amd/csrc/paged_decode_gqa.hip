@@ -897,3 +897,5 @@ extern "C" int mojo_hip_paged_decode_swa(const void* query, const void* key_cach
                             cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
                             layout_abab, leave_empty_rows, dtype, local_window, global_window, stream);
 }
+
+#include "paged_decode_kv8.h"

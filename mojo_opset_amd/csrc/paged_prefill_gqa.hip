@@ -1216,3 +1216,5 @@ extern "C" int mojo_hip_debug_prefill_stamps(unsigned* host_out, int64_t count) 
   return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(mojo::g_pf_stamps), static_cast<size_t>(count) * 4) == hipSuccess ? MOJO_OK : MOJO_ELAUNCH;
 }
 #endif
+
+#include "paged_prefill_kv8.h"
