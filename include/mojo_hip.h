@@ -471,6 +471,27 @@ int mojo_hip_residual_add_rmsnorm_quant(const void* hidden, const void* residual
                                         float* out_scale, int64_t rows, int64_t dim, int dtype, int quant_dtype,
                                         float q_min, float eps, mojo_stream_t stream);
 
+/* ---- MojoQuantExperts / MojoMoEDynamicQuant (core/operators/moe.py:452-667, quantize.py:178-247): W8A8 experts.
+ *      group_quant_gemm: out[rows of g] = round_out( float(A8[rows of g] @ W8[g]^T) * weight_scale[g][n] * input_scale[m] )
+ *      — the column scale FIRST (the experts' order; MojoQuantGemm's is row first, and with two fp32 roundings the bits
+ *      differ).  input int8 [m_total, K]; weight int8 [G, N, K] (trans_weight != 0, the experts' layout; [G, K, N] returns
+ *      MOJO_EUNSUPPORTED); input_scale fp32 [m_total]; weight_scale bf16 [G, N]; out_dtype in {f32, f16, bf16}; group_list
+ *      int32 / int64 row counts on the device, prefix-summed on the device.  Rows [sum(counts), m_total) of out are
+ *      written as zeros.  int32 accumulation: every kernel form, tile shape and K split gives the same bits.
+ *      moe_dynamic_quant: the arithmetic of dynamic_quant with inv_smooth_scale fp32 [E, dim] selected by the row's
+ *      expert (rows sorted by expert; token_count int32 / int64 [E] on the device, scanned inside the kernel).  glu != 0:
+ *      input is the dequantised first projection [rows, 2 * dim] = [gate | up] and y = silu(float(gate)) * float(up)
+ *      * inv_smooth_scale[e], all in fp32.  Rows at or past sum(token_count): int8 zeros, scale 1.  out_q int8
+ *      [rows, dim], out_scale fp32 [rows]; input dtype in {f32, f16, bf16}; at most 1024 experts.                       */
+int64_t mojo_hip_group_quant_gemm_workspace_bytes(int64_t m_total, int64_t k, int64_t n, int64_t num_groups);
+int mojo_hip_group_quant_gemm(const void* input, const void* weight, const float* input_scale,
+                              const void* weight_scale, void* out, const void* group_list, int group_list_is_i64,
+                              int64_t m_total, int64_t k, int64_t n, int64_t num_groups, int trans_weight,
+                              int out_dtype, void* workspace, int64_t workspace_bytes, mojo_stream_t stream);
+int mojo_hip_moe_dynamic_quant(const void* input, const float* inv_smooth_scale, const void* token_count,
+                               int token_count_is_i64, void* out_q, float* out_scale, int64_t rows, int64_t dim,
+                               int64_t num_experts, int glu, int dtype, mojo_stream_t stream);
+
 /* ---- MojoStorePagedMLAKVCache (experimental/operators/kv_cache.py:13-106): bit-exact copy of the new latent
  *      tokens compressed_kv_states [T, r] and k_pe_states [T, rope] into compressed_kv_cache [N,1,page,r] and
  *      k_pe_cache [N,1,page,rope] at positions context_kv_lens[b].. (cu_q_lens == NULL: one token per sequence).

@@ -10,5 +10,6 @@ from .operators.gemm import HIPGemm, HIPGroupGemm, HIPQuantGemm, HIPSwiGLUMLP  #
 from .operators.mla import HIPPagedDecodeMLA, HIPPagedPrefillMLA  # noqa: F401
 from .operators.compute_with_comm import (HIPAllGatherGemm, HIPGemmAll2All, HIPGemmAllReduce,  # noqa: F401
                                           HIPGemmReduceScatter)
-from .operators.moe import HIPExperts, HIPMoE, HIPMoECombine, HIPMoEDispatch, HIPMoEGating  # noqa: F401
-from .operators.quantize import HIPDynamicQuant, HIPResidualAddRMSNormQuant  # noqa: F401
+from .operators.moe import (HIPExperts, HIPMoE, HIPMoECombine, HIPMoEDispatch, HIPMoEGating, HIPQuantExperts,  # noqa: F401
+                            HIPQuantMoE)
+from .operators.quantize import HIPDynamicQuant, HIPMoEDynamicQuant, HIPResidualAddRMSNormQuant  # noqa: F401

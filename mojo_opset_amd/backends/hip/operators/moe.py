@@ -3,9 +3,11 @@ No host synchronisation anywhere: token counts stay on the device and feed the g
 
 import torch
 
-from ....core.operators.moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating
+from ....core.operators.moe import (MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts,
+                                    MojoQuantMoE)
 from .... import switches
 from .. import lib as L
+from .quantize import moe_dynamic_quant
 
 _ROCM = ["rocm"]
 
@@ -157,4 +159,70 @@ class HIPMoE(MojoMoE):
         return MojoMoE.compose_forward(self, hidden_states)
 
 
-__all__ = ["HIPMoEGating", "HIPMoEDispatch", "HIPMoECombine", "HIPExperts", "HIPMoE"]
+class HIPQuantExperts(MojoQuantExperts):
+    """W8A8 experts in four launches (+ the grouped GEMMs' prefix launches): smooth + quantise, grouped int8 GEMM with the
+    dequantising epilogue, dequantised fc1 -> SwiGLU -> smooth -> quantise in one kernel (the fp32 ``[M, I]`` activation never
+    reaches HBM), grouped int8 GEMM.  Nothing synchronises with the host (no ``.item()`` / ``.tolist()``), so the call can be
+    captured in a HIP graph.  ``tokens_per_expert`` stays on the device and is NOT validated (the reference's quantiser checks
+    its sum on the host): rows at or past ``sum(tokens_per_expert)`` come back as zeros, negative counts read as zero.
+
+    int4 weights and group scales (``*_quant_group_size > 0``) are not implemented: construction raises NotImplementedError."""
+
+    supported_platforms_list = _ROCM
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._refuse_unsupported()
+
+    def _refuse_unsupported(self):
+        if self.up_weight_dtype != torch.int8 or self.down_weight_dtype != torch.int8:
+            raise NotImplementedError("HIPQuantExperts: int4 expert weights are not implemented (int8 only)")
+        if self.up_quant_group_size > 0 or self.down_quant_group_size > 0:
+            raise NotImplementedError("HIPQuantExperts: group-wise weight scales are not implemented (per-channel only)")
+
+    @staticmethod
+    def _group_quant_gemm(x8, x_scale, w8, w_scale, counts, out_dtype):
+        m, k = x8.shape
+        groups, n = w8.shape[0], w8.shape[1]
+        if w8.dtype != torch.int8 or w8.shape[2] != k:
+            raise NotImplementedError(f"HIPQuantExperts: int8 [E, N, {k}] weights expected, got {w8.dtype} {tuple(w8.shape)}")
+        if w_scale.dtype != torch.bfloat16 or tuple(w_scale.shape) != (groups, n):
+            raise NotImplementedError(f"HIPQuantExperts: bf16 [{groups}, {n}] weight scales expected, got {w_scale.dtype} {tuple(w_scale.shape)}")
+        out = torch.empty(m, n, dtype=out_dtype, device=x8.device)
+        lib = L.load()
+        ws = torch.empty(lib.mojo_hip_group_quant_gemm_workspace_bytes(m, k, n, groups), dtype=torch.uint8, device=x8.device)
+        L.check(lib.mojo_hip_group_quant_gemm(L.ptr(x8), L.ptr(w8), L.ptr(x_scale), L.ptr(w_scale), L.ptr(out), L.ptr(counts),
+                                              1 if counts.dtype == torch.int64 else 0, m, k, n, groups, 1, L.dtype_code(out_dtype),
+                                              L.ptr(ws), ws.numel(), L.stream_of(x8)), "HIPQuantExperts gemm")
+        return out
+
+    def forward(self, sorted_hidden_states: torch.Tensor, tokens_per_expert: torch.Tensor) -> torch.Tensor:
+        self._refuse_unsupported()
+        up_w, down_w = self.up_proj_weight, self.down_proj_weight
+        up_s, down_s = self.up_proj_weight_scale.detach(), self.down_proj_weight_scale.detach()
+        up_inv, down_inv = self.up_proj_quantize.inv_smooth_scale.detach(), self.down_proj_quantize.inv_smooth_scale.detach()
+        if sorted_hidden_states.dtype not in (torch.bfloat16, torch.float16) or sorted_hidden_states.dim() != 2:
+            raise NotImplementedError("HIPQuantExperts: bf16 / fp16 activations [M, hidden] expected")
+        if tokens_per_expert.dtype not in (torch.int32, torch.int64):
+            raise NotImplementedError("HIPQuantExperts: tokens_per_expert must be int32 or int64")
+        L.require_cuda(sorted_hidden_states, up_w, down_w, up_s, down_s, up_inv, down_inv)
+        x = _dense(sorted_hidden_states)
+        counts = _dense(tokens_per_expert.to(x.device, non_blocking=True))
+        assert counts.numel() == up_w.shape[0]
+        hidden, inter = x.shape[1], down_w.shape[2]
+        x8, x_scale = moe_dynamic_quant(x, _dense(up_inv), counts, hidden, False, "HIPQuantExperts quantise")
+        fc1 = self._group_quant_gemm(x8, x_scale, _dense(up_w), _dense(up_s), counts, x.dtype)      # [M, 2I] = [gate | up]
+        y8, y_scale = moe_dynamic_quant(fc1, _dense(down_inv), counts, inter, True, "HIPQuantExperts swiglu + quantise")
+        return self._group_quant_gemm(y8, y_scale, _dense(down_w), _dense(down_s), counts, x.dtype)
+
+
+class HIPQuantMoE(MojoQuantMoE):
+    """Routing on the HIP operators, experts on `HIPQuantExperts`; with ``ep_size == 1`` nothing synchronises with the host."""
+
+    supported_platforms_list = _ROCM
+
+    def forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
+        return MojoMoE.compose_forward(self, hidden_states)      # (through the class: see HIPMoE.forward)
+
+
+__all__ = ["HIPMoEGating", "HIPMoEDispatch", "HIPMoECombine", "HIPExperts", "HIPMoE", "HIPQuantExperts", "HIPQuantMoE"]

@@ -3,7 +3,7 @@ from typing import Optional
 
 import torch
 
-from ....core.operators.quantize import MojoDynamicQuant, MojoResidualAddRMSNormQuant
+from ....core.operators.quantize import MojoDynamicQuant, MojoMoEDynamicQuant, MojoResidualAddRMSNormQuant
 from .. import lib as L
 
 _ROCM = ["rocm"]
@@ -42,6 +42,48 @@ class HIPDynamicQuant(MojoDynamicQuant):
         return out, scale
 
 
+def moe_dynamic_quant(x: torch.Tensor, inv_smooth: torch.Tensor, counts: torch.Tensor, dim: int, glu: bool, what: str):
+    """One launch of ``mojo_hip_moe_dynamic_quant`` on a dense ``x [rows, dim]`` (``glu``: ``[rows, 2 * dim]`` = [gate | up]):
+    returns ``(int8 [rows, dim], fp32 scale [rows, 1])``."""
+    if inv_smooth.dtype != torch.float32:
+        raise NotImplementedError(f"{what}: inv_smooth_scale must be float32 (the reference pins it with force_dtype), got {inv_smooth.dtype}")
+    if inv_smooth.dim() != 2 or inv_smooth.shape[1] != dim or inv_smooth.shape[0] != counts.numel():
+        raise ValueError(f"{what}: inv_smooth_scale {tuple(inv_smooth.shape)} does not match {counts.numel()} experts x {dim}")
+    rows = x.shape[0]
+    out = torch.empty(rows, dim, dtype=torch.int8, device=x.device)
+    scale = torch.empty(rows, 1, dtype=torch.float32, device=x.device)
+    L.check(L.load().mojo_hip_moe_dynamic_quant(L.ptr(x), L.ptr(inv_smooth), L.ptr(counts), 1 if counts.dtype == torch.int64 else 0,
+                                                L.ptr(out), L.ptr(scale), rows, dim, counts.numel(), 1 if glu else 0,
+                                                L.dtype_code(x.dtype), L.stream_of(x)), what)
+    return out, scale
+
+
+class HIPMoEDynamicQuant(MojoMoEDynamicQuant):
+    """The expert of a row is found on the device from ``token_count``; nothing synchronises with the host.  The reference
+    validates ``token_count`` on the host (non-negative, summing to the row count); this class does NOT: negative counts
+    read as zero, and rows at or past ``sum(token_count)`` come back as int8 zeros with scale 1."""
+
+    supported_platforms_list = _ROCM
+
+    def forward(self, input: torch.Tensor, token_count: torch.Tensor):
+        # (the reference's own shape / dtype checks, spelled out so the body also binds to the reference's class)
+        if input.dim() < 2:
+            raise ValueError(f"input must have at least 2 dimensions for MoE dynamic quant, got {input.dim()}.")
+        if token_count.dim() != 1:
+            raise ValueError(f"token_count must be 1D, got shape {tuple(token_count.shape)}.")
+        if token_count.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"token_count must be int32 or int64, got {token_count.dtype}.")
+        if input.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"HIPMoEDynamicQuant: input dtype {input.dtype}")
+        inv = self.inv_smooth_scale.detach()
+        L.require_cuda(input, inv)
+        x = _dense(input)
+        dim = x.shape[-1]
+        counts = _dense(token_count.to(x.device, non_blocking=True))
+        out, scale = moe_dynamic_quant(x.reshape(-1, dim), _dense(inv), counts, dim, False, "HIPMoEDynamicQuant")
+        return out.reshape(x.shape), scale.reshape(*x.shape[:-1], 1)
+
+
 class HIPResidualAddRMSNormQuant(MojoResidualAddRMSNormQuant):
     supported_platforms_list = _ROCM
 
@@ -67,4 +109,4 @@ class HIPResidualAddRMSNormQuant(MojoResidualAddRMSNormQuant):
         return out, (summed if pre else normed), scale
 
 
-__all__ = ["HIPDynamicQuant", "HIPResidualAddRMSNormQuant"]
+__all__ = ["HIPDynamicQuant", "HIPMoEDynamicQuant", "HIPResidualAddRMSNormQuant"]

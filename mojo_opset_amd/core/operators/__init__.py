@@ -7,10 +7,10 @@ from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStore
                        build_paged_kv_chunk_metadata)
 from .mla import MojoPagedDecodeMLA, MojoPagedPrefillMLA
 from .mlp import MojoSwiGLUMLP
-from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating
+from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts, MojoQuantMoE
 from .normalization import MojoResidualAddRMSNorm, MojoRMSNorm, MojoRMSNormInplace
 from .position_embedding import MojoApplyRoPE, MojoRotaryEmbedding
-from .quantize import MojoDynamicQuant, MojoResidualAddRMSNormQuant
+from .quantize import MojoDynamicQuant, MojoMoEDynamicQuant, MojoResidualAddRMSNormQuant
 
 __all__ = [
     "MojoSwiGLU", "MojoPagedDecodeGQA", "MojoPagedPrefillGQA", "MojoAllGatherGemm", "MojoGemmAll2All",
@@ -26,3 +26,6 @@ __all__ = [
 EXTENDED_OPS = ("MojoPagedDecodeSWA", "MojoPagedPrefillSWA")
 # The int8 paged KV cache with per-channel scales (the reference's experimental "C8" path): same standing as EXTENDED_OPS.
 KV_INT8_OPS = ("MojoStorePagedKVCacheC8", "MojoPagedDecodeGQAWithKVDequant", "MojoPagedPrefillGQAWithKVDequant")
+# W8A8 MoE experts (the reference's quantised MoE: per-expert smooth quantiser, int8 experts, the layer): same standing again;
+# goldens in tests/quant_moe_golden.py.
+QUANT_MOE_OPS = ("MojoMoEDynamicQuant", "MojoQuantExperts", "MojoQuantMoE")

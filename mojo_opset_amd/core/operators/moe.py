@@ -1,12 +1,16 @@
 """API classes of the MoE routing ops either side of `MojoGroupGemm`.
 
 Follows `mojo_opset/core/operators/moe.py`: `MojoMoEGating` (:277-321), `MojoMoEDispatch` (:327-400),
-`MojoExperts` (:402-449), `MojoMoECombine` (:670-716).  Constructor signatures, parameter names
+`MojoExperts` (:402-449), `MojoMoECombine` (:670-716), and the W8A8 pair `MojoQuantExperts` (:452-667) /
+`MojoQuantMoE` (:132-274).  Constructor signatures, parameter names
 and shapes, dtype asserts and return order are the reference's; the forward is abstract here.
 """
+from typing import Union
+
 import torch
 
 from ..operator import MojoOperator
+from .quantize import MojoMoEDynamicQuant
 
 
 class MojoMoEGating(MojoOperator):
@@ -143,6 +147,94 @@ class MojoMoE(MojoOperator):
             else:
                 dist.all_reduce(out, op=dist.ReduceOp.SUM, group=self.ep_group)
         return out
+
+
+class MojoQuantExperts(MojoOperator):
+    """forward(sorted_hidden_states [M, hidden] bf16 / fp16, tokens_per_expert [E]) -> [M, hidden]: W8A8 experts.
+
+    Per expert: smooth + per-token int8 quantisation (``up_proj_quantize``), ``fc1 = round_T(acc * weight_scale *
+    input_scale)`` against ``up_proj_weight int8 [E, 2I, H]``, ``silu(gate) * up`` in fp32 (gate = first half), the second
+    quantiser (``down_proj_quantize``), ``fc2`` against ``down_proj_weight int8 [E, H, I]``.  ``*_weight_dtype == "int4"``
+    packs two signed nibbles per byte along the output dimension (``[E, N / 2, K]``); ``*_quant_group_size > 0`` gives the
+    weight scales a trailing dimension of K groups.  Weight scales are bf16 parameters."""
+
+    def __init__(self, num_experts: int, hidden_size: int, intermediate_size: int, activation: str = "swiglu",
+                 quant_dtype: torch.dtype = torch.int8, up_quant_group_size: int = -1,
+                 up_weight_dtype: Union[torch.dtype, str] = torch.int8, down_quant_group_size: int = -1,
+                 down_weight_dtype: Union[torch.dtype, str] = torch.int8, **kwargs):
+        super().__init__(**kwargs)
+        if activation != "swiglu":
+            raise NotImplementedError(f"MojoQuantExperts: Activation {activation} is not supported.")
+        if quant_dtype != torch.int8:
+            raise ValueError(f"MojoQuantExperts: quant_dtype must be 'int8', got {quant_dtype}.")
+        if up_weight_dtype not in ("int4", torch.int8) or down_weight_dtype not in ("int4", torch.int8):
+            raise NotImplementedError("MojoQuantExperts currently only supports w4 or w8.")
+        if "int4" in (up_weight_dtype, down_weight_dtype) and (hidden_size % 2 != 0 or intermediate_size % 2 != 0):
+            raise ValueError("MojoQuantExperts requires even hidden_size and intermediate_size for int4 packing.")
+        self.activation = activation
+        self.quant_dtype = quant_dtype
+        self.up_quant_group_size, self.up_weight_dtype = up_quant_group_size, up_weight_dtype
+        self.down_quant_group_size, self.down_weight_dtype = down_quant_group_size, down_weight_dtype
+        self.qmax, self.qmin = 127, -128
+        self.num_experts, self.hidden_size, self.intermediate_size = num_experts, hidden_size, intermediate_size
+        quantiser = MojoMoEDynamicQuant.get_registry().get(self._backend)          # sub-operators of the same backend
+        self.up_proj_quantize = quantiser(num_experts, hidden_size)
+        self.down_proj_quantize = quantiser(num_experts, intermediate_size)
+        up_rows = intermediate_size * 2 if up_weight_dtype == torch.int8 else intermediate_size
+        down_rows = hidden_size if down_weight_dtype == torch.int8 else hidden_size // 2
+        self.register_buffer("up_proj_weight", torch.empty((num_experts, up_rows, hidden_size), dtype=torch.int8))
+        self.register_buffer("down_proj_weight", torch.empty((num_experts, down_rows, intermediate_size), dtype=torch.int8))
+        up_shape, down_shape = (num_experts, intermediate_size * 2), (num_experts, hidden_size)
+        if up_quant_group_size > 0:
+            up_shape += ((hidden_size + up_quant_group_size - 1) // up_quant_group_size,)
+        if down_quant_group_size > 0:
+            down_shape += ((intermediate_size + down_quant_group_size - 1) // down_quant_group_size,)
+        self.up_proj_weight_scale = torch.nn.Parameter(torch.empty(up_shape, dtype=torch.bfloat16))
+        self.down_proj_weight_scale = torch.nn.Parameter(torch.empty(down_shape, dtype=torch.bfloat16))
+
+    def extra_repr(self) -> str:
+        return (f"{self.num_experts=}, {self.intermediate_size=}, {self.hidden_size=}, {self.quant_dtype=}, "
+                f"{self.up_quant_group_size=}, {self.up_weight_dtype=}, {self.down_quant_group_size=}, "
+                f"{self.down_weight_dtype=}").replace("self.", "")
+
+
+class MojoQuantMoE(MojoOperator):
+    """`MojoMoE` with `MojoQuantExperts` in the experts' place (reference `MojoQuantMoE`): the same routing operators, the same
+    expert-parallel wiring, and the same forward — `MojoMoE.compose_forward`, which every backend binds."""
+
+    _use_fused_moe = False
+
+    def __init__(self, num_experts, top_k, hidden_size, intermediate_size=None, activation: str = "swiglu",
+                 quant_dtype: torch.dtype = torch.int8, up_quant_group_size: int = -1,
+                 up_weight_dtype: Union[torch.dtype, str] = torch.int8, down_quant_group_size: int = -1,
+                 down_weight_dtype: Union[torch.dtype, str] = torch.int8, ep_size: int = 1, ep_rank: int = 0, ep_group=None,
+                 dp_input: bool = False, **kwargs):
+        super().__init__()
+        if activation != "swiglu":
+            raise NotImplementedError(f"MojoQuantMoE: Activation {activation} is not supported.")
+        if quant_dtype != torch.int8:
+            raise NotImplementedError(f"MojoQuantMoE: quant_dtype must be 'int8', got {quant_dtype}.")
+        if up_weight_dtype not in ("int4", torch.int8) or down_weight_dtype not in ("int4", torch.int8):
+            raise ValueError("MojoQuantMoE: weight must be w4 or w8")
+        if intermediate_size is None:
+            raise ValueError("MojoQuantMoE: intermediate_size must be provided.")
+        self.num_experts, self.top_k, self.hidden_size, self.intermediate_size = num_experts, top_k, hidden_size, intermediate_size
+        self.quant_dtype = quant_dtype
+        self.up_quant_group_size, self.up_weight_dtype = up_quant_group_size, up_weight_dtype
+        self.down_quant_group_size, self.down_weight_dtype = down_quant_group_size, down_weight_dtype
+        self.ep_size, self.ep_rank, self.ep_group, self.dp_input = ep_size, ep_rank, ep_group, dp_input
+        base, rem = divmod(num_experts, ep_size)
+        self.num_experts_local = base + 1 if ep_rank < rem else base
+        self.ep_start = base * ep_rank + min(ep_rank, rem)
+        self.ep_end = self.ep_start + self.num_experts_local
+        pick = lambda core: core.get_registry().get(self._backend)      # noqa: E731  sub-operators of the same backend
+        self.gating = pick(MojoMoEGating)(hidden_size=hidden_size, num_experts=num_experts, top_k=top_k, **kwargs)
+        self.dispatch = pick(MojoMoEDispatch)(num_experts=num_experts, **kwargs)
+        self.experts = pick(MojoQuantExperts)(
+            num_experts=self.num_experts_local, hidden_size=hidden_size, intermediate_size=intermediate_size, activation=activation,
+            quant_dtype=quant_dtype, up_quant_group_size=up_quant_group_size, up_weight_dtype=up_weight_dtype,
+            down_quant_group_size=down_quant_group_size, down_weight_dtype=down_weight_dtype, **kwargs)
+        self.combine = pick(MojoMoECombine)(multiply_by_gates=True, **kwargs)
 
 
 __all__ = ["MojoMoEGating", "MojoMoEDispatch", "MojoExperts", "MojoMoECombine", "MojoMoE", "count_expert_tokens"]

@@ -1,6 +1,6 @@
 """API classes of the activation quantisers that feed `MojoQuantGemm`.
 
-Follows `mojo_opset/core/operators/quantize.py:120-172` (`MojoDynamicQuant`) and
+Follows `mojo_opset/core/operators/quantize.py:120-172` (`MojoDynamicQuant`), `:178-247` (`MojoMoEDynamicQuant`) and
 `mojo_opset/core/operators/normalization.py:434-533` (`MojoResidualAddRMSNormQuant`).
 """
 from typing import Optional
@@ -31,6 +31,36 @@ class MojoDynamicQuant(MojoOperator):
 
     def extra_repr(self) -> str:
         return f"input_size={self.input_size}, quant_dtype={self.quant_dtype}"
+
+
+class MojoMoEDynamicQuant(MojoOperator):
+    """forward(input [*, K], token_count int32 | int64 [E]) -> (int8 like input, fp32 scale input.shape[:-1] + (1,)):
+    `MojoDynamicQuant`'s arithmetic with the smooth scale of the row's expert.  The rows arrive sorted by expert,
+    ``token_count[e]`` of them for expert ``e``; ``inv_smooth_scale [expert_num, input_size]`` is fp32 (``force_dtype``)."""
+
+    def __init__(self, expert_num: int, input_size: int, quant_dtype: torch.dtype = torch.int8, **kwargs):
+        super().__init__(**kwargs)
+        self.expert_num = expert_num
+        self.input_size = input_size
+        self.inv_smooth_scale = torch.nn.Parameter(torch.empty((expert_num, input_size), **self.tensor_factory_kwargs))
+        setattr(self.inv_smooth_scale, "force_dtype", torch.float32)
+        self.quant_dtype = quant_dtype
+        if quant_dtype != torch.int8:
+            raise NotImplementedError(f"Unsupported quant_dtype: {quant_dtype}, expected torch.int8.")
+        self.q_max = 127
+        self.q_min = -128
+
+    def check_call_contract(self, input, token_count):
+        """The reference's shape and dtype checks (:223-228); what needs the VALUES of ``token_count`` is the backend's call."""
+        if input.dim() < 2:
+            raise ValueError(f"input must have at least 2 dimensions for MoE dynamic quant, got {input.dim()}.")
+        if token_count.dim() != 1:
+            raise ValueError(f"token_count must be 1D, got shape {tuple(token_count.shape)}.")
+        if token_count.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"token_count must be int32 or int64, got {token_count.dtype}.")
+
+    def extra_repr(self) -> str:
+        return f"expert_num={self.expert_num}, input_size={self.input_size}, quant_dtype={self.quant_dtype}"
 
 
 class MojoResidualAddRMSNormQuant(MojoOperator):
@@ -72,4 +102,4 @@ class MojoResidualAddRMSNormQuant(MojoOperator):
         )
 
 
-__all__ = ["MojoDynamicQuant", "MojoResidualAddRMSNormQuant"]
+__all__ = ["MojoDynamicQuant", "MojoResidualAddRMSNormQuant"]      # (MojoMoEDynamicQuant: QUANT_MOE_OPS, core/operators/__init__.py)

@@ -85,6 +85,7 @@ struct EpiloguePlain {       // C = round_T(acc) (+ bias after the rounding: the
   // tile through the direct 8-byte stores with the bias fetched in the epilogue: + 18-25 % on a prefill-sized projection with a
   // bias (8192 x 4096 x 6144: 281 -> 332 us), + 59 % at K 1024.
   static constexpr bool kLdsScales = sizeof(T) == 2;
+  static constexpr bool kGrouped = false;              // (EpilogueGroupDequant: the kernel tells the epilogue its tile's group)
   __host__ __device__ __forceinline__ bool lds_values() const { return bias != nullptr; }   // (no bias: the epilogue as before)
   __device__ __forceinline__ float scale_for_thread(int t, int, int, int n0, int n_limit) const {
     return (bias && t >= 256) ? static_cast<float>(bias[min(n0 + t - 256, n_limit - 1)]) : 0.f;
@@ -153,6 +154,7 @@ struct EpiloguePlain {       // C = round_T(acc) (+ bias after the rounding: the
 struct EpilogueF32 {         // C (fp32) = acc, or C += acc: two-pass products (x @ w_hi, then + x @ w_lo) of the MoE router
   static constexpr bool kRowStaged = false;
   static constexpr bool kLdsScales = false;
+  static constexpr bool kGrouped = false;
   __host__ __device__ __forceinline__ bool lds_values() const { return false; }
   float* C; int64_t ldc; int accumulate;
   __device__ __forceinline__ void row_begin(int) {}
@@ -176,6 +178,7 @@ struct EpilogueDequant {     // C = round_TO( float(acc) * row_scale[m] * col_sc
   // inside the epilogue they were an exposed memory latency per tile: 3.4 % of the M 4096 x 7168 x 36864 product, 9 % at K 4096
   // (scripts/probes/quant_headline_scales.py: the same kernel with constants in place of the fetches).
   static constexpr bool kLdsScales = sizeof(TO) == 2;
+  static constexpr bool kGrouped = false;
   __host__ __device__ __forceinline__ bool lds_values() const { return true; }
   typedef TO out_t;
   TO* C; int64_t ldc; const float* row_scale; const bf16_t* col_scale;
@@ -362,6 +365,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs a, Epi epi) {
       }
     }
     gemm_locate_tile(a, mi, BM, g, m0, m_end);
+    if constexpr (Epi::kGrouped) epi.set_group(g);
     n0 = a.glu ? ni * 128 : ni * BN;
     kt0 = static_cast<int>(static_cast<int64_t>(nkt_all) * kslice / a.splitk);
     nkt = static_cast<int>(static_cast<int64_t>(nkt_all) * (kslice + 1) / a.splitk) - kt0;   // K-tiles of this slice

@@ -108,6 +108,7 @@ __global__ __launch_bounds__(128 * NWN, 2) void gemm128_kernel(GemmArgs a, Epi e
   }
   int grp_i, m0, m_end;                              // group, first row and end row (exclusive) of this m-tile
   gemm_locate_tile(a, mi, BM, grp_i, m0, m_end);
+  if constexpr (Epi::kGrouped) epi.set_group(grp_i);
   const int n0 = ni * BN;
   const char* const W_g = static_cast<const char*>(a.W) + static_cast<int64_t>(grp_i) * a.w_group * EB;
   const int nkt_all = a.K / BK;

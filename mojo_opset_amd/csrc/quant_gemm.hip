@@ -8,6 +8,7 @@
 // Algorithmic FLOPs: 2*M*K*N (MFMA-bound for M >= 128); bytes: K*N (weight stream) + M*K + M*N*out.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "gemm256_core.h"
@@ -104,11 +105,15 @@ __global__ __launch_bounds__(256) void quant_finalize_kernel(const ACC* __restri
 // NW = waves per workgroup (16 columns each; round 4): chosen with the K split so that the wave units divide evenly over the CUs
 // (quant_skinny_plan) — the stream is per-CU bound, and N = 7168 in 64-column workgroups is 112 tiles x 2 slices = 224
 // workgroups on 256 CUs.  A wave past the last column tile streams the last one again and stores nothing.
-template <typename TO, bool FP8, int MT, bool NT /* weights read once: non-temporal loads */, int NW = 4>
+// RAGGED (the int8 experts of a decode step, mojo_hip_group_quant_gemm): blockIdx.z walks the MT * 16-row tiles of ragged groups
+// (prefix arrays built for that tile height); a tile streams the weights and reads the column scales of ITS group, a group
+// without rows streams nothing, and the scales are applied in the experts' order, acc * weight_scale * input_scale.
+template <typename TO, bool FP8, int MT, bool NT /* weights read once: non-temporal loads */, int NW = 4, bool RAGGED = false>
 __global__ __launch_bounds__(NW * 64) void quant_skinny_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ W,
                                                            const float* __restrict__ rs, const bf16_t* __restrict__ cs,
                                                            TO* __restrict__ C, void* __restrict__ slab, int M, int K, int N,
-                                                           int splitk, int sk_slot) {
+                                                           int splitk, int sk_slot, const int32_t* __restrict__ row_start = nullptr,
+                                                           const int32_t* __restrict__ tile_start = nullptr, int G = 1) {
   typedef typename std::conditional<FP8, f32x4, i32x4>::type acc_t;
   constexpr int ROW = 272;                                   // padded LDS row of a 256-byte K block
   constexpr int NTH = NW * 64;                               // threads
@@ -123,7 +128,20 @@ __global__ __launch_bounds__(NW * 64) void quant_skinny_kernel(const uint8_t* __
   const bool unit_live = unit_raw < N / 16;
   const int n0 = (unit_live ? unit_raw : N / 16 - 1) * 16;
   const int slice = blockIdx.y;
-  const int m0 = blockIdx.z * (MT * 16);                     // row block (grid.z > 1: more than MT * 16 rows)
+  int m0 = blockIdx.z * (MT * 16);                           // row block (grid.z > 1: more than MT * 16 rows)
+  if constexpr (RAGGED) {
+    const int mi = blockIdx.z;
+    if (mi >= tile_start[G]) return;                         // (grid.z is an upper bound; uniform over the workgroup)
+    int lo = 0, hi = G;                                      // largest group with tile_start[group] <= mi
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (tile_start[mid] <= mi) lo = mid; else hi = mid;
+    }
+    m0 = row_start[lo] + (mi - tile_start[lo]) * (MT * 16);
+    M = row_start[lo + 1];                                   // rows past the group: a valid row re-read, never stored
+    W += static_cast<int64_t>(lo) * N * K;
+    cs += static_cast<int64_t>(lo) * N;
+  }
   const int nkb = K / 256;
   const int kb0 = static_cast<int>(static_cast<int64_t>(nkb) * slice / splitk);
   const int kb1 = static_cast<int>(static_cast<int64_t>(nkb) * (slice + 1) / splitk);
@@ -236,7 +254,8 @@ __global__ __launch_bounds__(NW * 64) void quant_skinny_kernel(const uint8_t* __
     V4 o;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float x = __fmul_rn(__fmul_rn(static_cast<float>(v[q]), r), static_cast<float>(cs[n + q]));
+      float x = RAGGED ? __fmul_rn(__fmul_rn(static_cast<float>(v[q]), static_cast<float>(cs[n + q])), r)
+                       : __fmul_rn(__fmul_rn(static_cast<float>(v[q]), r), static_cast<float>(cs[n + q]));
       asm volatile("" : "+v"(x));
       o[q] = elt<TO>::from_f(x);
     }
@@ -633,6 +652,239 @@ static int run_quant(GemmArgs a, const float* rs, const bf16_t* cs, int64_t m, i
   return MOJO_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------
+// MojoQuantExperts' grouped product (mojo_hip_group_quant_gemm): ragged groups of int8 rows against int8 [G, N, K] weights,
+//   out[m][n] = round_TO( float(acc) * weight_scale[g][n] * input_scale[m] )        (the experts' golden: column scale FIRST;
+// two fp32 roundings, so this is not EpilogueDequant's acc * row * col), on the kernels above with an epilogue that knows its
+// group.  int32 accumulation is exact and associative: every form, tile shape and K split gives the same bits.
+template <typename TO>
+struct EpilogueGroupDequant {
+  static constexpr bool kRowStaged = sizeof(TO) == 2;
+  static constexpr bool kLdsScales = sizeof(TO) == 2;      // row / column scales parked in LDS before the K loop (EpilogueDequant's mechanism)
+  static constexpr bool kGrouped = true;                   // the kernels call set_group() once the tile is located
+  typedef TO out_t;
+  typedef i32x4 ACC;
+  TO* C; int64_t ldc; const float* row_scale; const bf16_t* col_scale /* [G, n_cols] */; int n_cols;
+  bool vec4;                 // store(): four outputs in one store where they fit (ldc % 4 == 0 and an aligned C)
+  const bf16_t* cs = nullptr;                              // the tile's group: col_scale + g * n_cols
+  float rs = 0.f;
+  __host__ __device__ __forceinline__ bool lds_values() const { return true; }
+  __host__ __device__ __forceinline__ bool has_bias() const { return false; }
+  __device__ __forceinline__ void set_group(int g) { cs = col_scale + static_cast<int64_t>(g) * n_cols; }
+  static __device__ __forceinline__ float deq(int acc, float col, float row) {
+    float v = __fmul_rn(__fmul_rn(static_cast<float>(acc), col), row);
+    asm volatile("" : "+v"(v));                            // the fp32 product is a value of its own (no multiply + narrow fusion)
+    return v;
+  }
+  __device__ __forceinline__ void row_begin(int m) { rs = row_scale[m]; }
+  __device__ __forceinline__ typename vec_of<TO, 4>::type to4(int n, ACC acc) const {   // full tiles only: n + 4 <= N
+    typename vec_of<TO, 4>::type o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = elt<TO>::from_f(deq(acc[e], static_cast<float>(cs[n + e]), rs));
+    return o;
+  }
+  __device__ __forceinline__ float scale_for_thread(int t, int m0, int m_limit, int n0, int n_limit) const {
+    return t < 256 ? row_scale[min(m0 + t, m_limit - 1)] : static_cast<float>(cs[min(n0 + t - 256, n_limit - 1)]);
+  }
+  __device__ __forceinline__ typename vec_of<TO, 4>::type to4_scaled(ACC acc, float row, f32x4 col) const {
+    typename vec_of<TO, 4>::type o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = elt<TO>::from_f(deq(acc[e], col[e], row));
+    return o;
+  }
+  struct Pre { float rs[4]; float cs[4][4]; };             // gemm_tile128_core.h: requested before the K loop
+  __device__ __forceinline__ void preload(Pre& p, int m_first, int m_limit, int n_first, int n_limit) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) p.rs[i] = row_scale[min(m_first + i * 16, m_limit - 1)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) p.cs[j][e] = static_cast<float>(cs[min(n_first + j * 16 + e, n_limit - 1)]);
+  }
+  __device__ __forceinline__ void store_pre(const Pre& p, int i, int j, int m, int n, int n_limit, ACC acc) const {
+    TO* dst = C + static_cast<int64_t>(m) * ldc + n;
+    typename vec_of<TO, 4>::type o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = elt<TO>::from_f(deq(acc[e], p.cs[j][e], p.rs[i]));
+    if (vec4 && n + 4 <= n_limit) {
+      *reinterpret_cast<typename vec_of<TO, 4>::type*>(dst) = o;
+    } else {
+      for (int e = 0; e < 4 && n + e < n_limit; ++e) dst[e] = o[e];
+    }
+  }
+  __device__ __forceinline__ void store(int m, int n, int n_limit, ACC acc) const {
+    TO* dst = C + static_cast<int64_t>(m) * ldc + n;
+    if (vec4 && n + 4 <= n_limit) {
+      *reinterpret_cast<typename vec_of<TO, 4>::type*>(dst) = to4(n, acc);
+      return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (n + e < n_limit) dst[e] = elt<TO>::from_f(deq(acc[e], static_cast<float>(cs[n + e]), rs));
+  }
+};
+
+// group of row m: the largest g with row_start[g] <= m (rows at or past row_start[G] belong to no group: the caller skips them)
+__device__ __forceinline__ int group_of_row(const int32_t* __restrict__ row_start, int G, int m) {
+  int lo = 0, hi = G;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (row_start[mid] <= m) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// K-split finalize of the grouped product: slices summed in index order, scales in the experts' order
+template <typename TO>
+__global__ __launch_bounds__(256) void group_quant_finalize_kernel(const int* __restrict__ slab, int splitk, int64_t M, int N,
+                                                                   const int32_t* __restrict__ row_start, int G,
+                                                                   const float* __restrict__ rs, const bf16_t* __restrict__ cs,
+                                                                   TO* __restrict__ C) {
+  const int64_t total = M * N;                            // N % 4 == 0 (the split's precondition)
+  typedef typename vec_of<TO, 4>::type O4;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total / 4; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t m = (i * 4) / N;
+    if (m >= row_start[G]) return;                        // the tail was zeroed by the prefix kernel (i only grows)
+    const int n = static_cast<int>(i * 4 - m * N);
+    i32x4 acc = {0, 0, 0, 0};
+    for (int sidx = 0; sidx < splitk; ++sidx) acc += reinterpret_cast<const i32x4*>(slab + static_cast<int64_t>(sidx) * total)[i];
+    const bf16_t* c = cs + static_cast<int64_t>(group_of_row(row_start, G, static_cast<int>(m))) * N + n;
+    const float r = rs[m];
+    O4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = elt<TO>::from_f(EpilogueGroupDequant<TO>::deq(acc[e], static_cast<float>(c[e]), r));
+    if ((reinterpret_cast<uintptr_t>(C) & (4 * sizeof(TO) - 1)) == 0) {
+      reinterpret_cast<O4*>(C)[i] = o;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) C[i * 4 + e] = o[e];
+    }
+  }
+}
+
+// any K / N / alignment: one output per thread
+template <typename TO>
+__global__ __launch_bounds__(256) void group_quant_generic_kernel(const int8_t* __restrict__ A, const int8_t* __restrict__ W,
+                                                                  const float* __restrict__ rs, const bf16_t* __restrict__ cs,
+                                                                  TO* __restrict__ C, int64_t M, int K, int N,
+                                                                  const int32_t* __restrict__ row_start, int G) {
+  const int64_t total = M * N;
+  for (int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; idx < total;
+       idx += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t m = idx / N;
+    if (m >= row_start[G]) return;
+    const int n = static_cast<int>(idx - m * N);
+    const int g = group_of_row(row_start, G, static_cast<int>(m));
+    const int8_t* a = A + m * K;
+    const int8_t* w = W + (static_cast<int64_t>(g) * N + n) * K;
+    int acc = 0;
+    for (int k = 0; k < K; ++k) acc += static_cast<int>(a[k]) * static_cast<int>(w[k]);
+    C[idx] = elt<TO>::from_f(EpilogueGroupDequant<TO>::deq(acc, static_cast<float>(cs[static_cast<int64_t>(g) * N + n]), rs[m]));
+  }
+}
+
+// The ragged weight stream: groups of at most 64 rows on average (a decode step's experts), [N,K] weights, whole 256-byte K
+// blocks.  Tile height by the mean rows per group: a group of up to MT * 16 rows streams its weights once.
+static bool group_quant_ragged_ok(const GemmArgs& a, int64_t m_total) {
+  return a.G > 1 && m_total <= 64LL * a.G && a.K % 256 == 0 && a.N % 64 == 0 && aligned_to(a.A, 16) && aligned_to(a.W, 16) &&
+         aligned_to(a.C, 8) && m_total / 16 + a.G < 65535;
+}
+static int group_quant_ragged_mt(int64_t m_total, int groups) {
+  const int64_t mean = ceil_div(m_total, groups);
+  return mean <= 16 ? 1 : (mean <= 32 ? 2 : 4);
+}
+template <typename TO>
+static int launch_group_quant_ragged(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m_total, hipStream_t s) {
+  const int mt = group_quant_ragged_mt(m_total, a.G);
+  const dim3 grid(static_cast<unsigned>(a.N / 64), 1u, static_cast<unsigned>(m_total / (mt * 16) + a.G));   // z: an upper bound on the tiles
+  const uint8_t* A = static_cast<const uint8_t*>(a.A);
+  const uint8_t* W = static_cast<const uint8_t*>(a.W);
+  TO* C = static_cast<TO*>(a.C);
+#define RAGGED(MT_) hipLaunchKernelGGL((quant_skinny_kernel<TO, false, MT_, true, 4, true>), grid, dim3(256), 0, s, A, W, rs, cs, C, nullptr, 0, a.K, a.N, 1, -1, a.row_start, a.tile_start, a.G)
+  if (mt == 1) RAGGED(1); else if (mt == 2) RAGGED(2); else RAGGED(4);
+#undef RAGGED
+  MOJO_CHECK_LAUNCH("group_quant_gemm(ragged)");
+  note_launch("group_quant_ragged:rows%d", mt * 16);
+  return MOJO_OK;
+}
+
+// 128-row tiles for few / small groups (gemm_tile128_group_ok's regime).  Not yet fitted on a sweep of its own: the rule is the
+// padding argument of the 16-bit grouped product — a mean of at most 128 rows per group leaves a 256-row tile half empty, and
+// fewer than 128 tiles of 256 x 256 leave half the chip idle.
+static bool group_quant_tile128_ok(const GemmArgs& a, int out_elt_bytes) {
+  return a.K >= 128 && a.K % 128 == 0 && a.w_group % 16 == 0 && a.ldc % 4 == 0 && aligned_to(a.A, 16) && aligned_to(a.W, 16) &&
+         aligned_to(a.C, 4 * out_elt_bytes);
+}
+static bool group_quant_prefers_tile128(int64_t m_total, int64_t n, int64_t groups) {
+  const int64_t rows = std::max<int64_t>(1, m_total / groups);
+  return rows <= 128 || groups * ceil_div(rows, 256) * ceil_div(n, 256) < 128;
+}
+// K split of the grouped 256 x 256 launch: QuantGemm's rule on the total rows; a forced split (MOJO_HIP_GEMM_SPLITK) is cut to what
+// the slabs' 16-byte stores (N % 4 == 0) and the K-tiles there are allow.
+static int group_quant_splitk(int64_t m_total, int k, int n) {
+  if (m_total <= 0 || n % 4 != 0 || k < 128) return 1;
+  const int sk = quant_splitk(m_total, k, n), nkt = k / 128;
+  return sk > nkt ? nkt : sk;
+}
+
+static int64_t group_quant_prefix_bytes(int64_t groups) { return (GEMM_WS_INTS(static_cast<int>(groups)) * 4 + 64 + 15) / 16 * 16; }
+
+template <typename TO>
+static int run_group_quant(GemmArgs a, const float* rs, const bf16_t* cs, const void* counts, int counts_i64, int64_t m, void* slab_ws,
+                           int32_t* ws, hipStream_t s) {
+  GemmTail tail;
+  tail.C = a.C; tail.ld_bytes = a.ldc * static_cast<long long>(sizeof(TO)); tail.row_bytes = a.N * static_cast<long long>(sizeof(TO));
+  auto prefix = [&](int bm) { return launch_group_prefix(counts, counts_i64, a.G, bm, m, ws, ws + (a.G + 1), s, tail); };
+  if (group_quant_ragged_ok(a, m) && (gemm_skinny_mask() & SKINNY_RAGGED)) {
+    if (const int rc = prefix(group_quant_ragged_mt(m, a.G) * 16)) return rc;
+    return launch_group_quant_ragged<TO>(a, rs, cs, m, s);
+  }
+  if (group_quant_tile128_ok(a, sizeof(TO))) {
+    const int f = g128::forced_choice();
+    if (f < 0 ? group_quant_prefers_tile128(m, a.N, a.G) : f == 1) {
+      if (const int rc = prefix(128)) return rc;
+      EpilogueGroupDequant<TO> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, a.N, true};
+      const int rc = g128::launch<g256::PolI8>(a, epi, m, s);
+      if (!rc) {
+        char shape[160];                                   // (the core's own note: "gemm128:128x128:NK")
+        snprintf(shape, sizeof(shape), "%s", mojo_hip_last_launch());
+        note_launch("group_quant_tile128:%s", shape);
+      }
+      return rc;
+    }
+  }
+  if (g256::gemm256_layout_ok(a, 1)) {
+    if (const int rc = prefix(256)) return rc;
+    const int sk = group_quant_splitk(m, a.K, a.N);
+    const bool vec4 = a.ldc % 4 == 0 && aligned_to(a.C, 4 * sizeof(TO));
+    EpilogueGroupDequant<TO> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, a.N, vec4};
+    if (sk > 1) {
+      a.splitk = sk; a.slab = slab_ws; a.slab_rows = static_cast<int>(m);
+      if (const int rc = g256::gemm256_launch<g256::PolI8>(a, epi, m, s)) return rc;
+      int64_t blocks = ceil_div(m * a.N / 4, 256);
+      if (blocks > 256 * 8) blocks = 256 * 8;
+      hipLaunchKernelGGL((group_quant_finalize_kernel<TO>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, static_cast<const int*>(slab_ws), sk, m,
+                         a.N, a.row_start, a.G, rs, cs, static_cast<TO*>(a.C));
+      MOJO_CHECK_LAUNCH("group_quant_gemm(finalize)");
+      note_launch("group_quant256:splitk%d", sk);
+      return MOJO_OK;
+    }
+    a.stage_rows = (MOJO_SWITCH("MOJO_HIP_GEMM_STAGE_ROWS", 1) != 0 && sizeof(TO) == 2 && a.ldc % 8 == 0 && aligned_to(a.C, 16)) ? 1 : 0;
+    const int rc = g256::gemm256_launch<g256::PolI8>(a, epi, m, s);
+    if (!rc) note_launch("group_quant256:%s", a.stage_rows ? "staged" : "direct");
+    return rc;
+  }
+  if (const int rc = prefix(256)) return rc;
+  int64_t blocks = ceil_div(m * a.N, 256);
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  hipLaunchKernelGGL((group_quant_generic_kernel<TO>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, static_cast<const int8_t*>(a.A),
+                     static_cast<const int8_t*>(a.W), rs, cs, static_cast<TO*>(a.C), m, a.K, a.N, a.row_start, a.G);
+  MOJO_CHECK_LAUNCH("group_quant_gemm(generic)");
+  note_launch("group_quant_generic");
+  return MOJO_OK;
+}
+
 }  // namespace mojo
 
 using namespace mojo;
@@ -683,5 +935,41 @@ extern "C" int mojo_hip_quant_gemm(const void* input, const void* weight, const 
     case MOJO_F32: return run_quant<float>(a, input_scale, cs, m, quant_dtype, slab_ws, s);
     case MOJO_F16: return run_quant<f16_t>(a, input_scale, cs, m, quant_dtype, slab_ws, s);
     default: return run_quant<bf16_t>(a, input_scale, cs, m, quant_dtype, slab_ws, s);
+  }
+}
+
+extern "C" int64_t mojo_hip_group_quant_gemm_workspace_bytes(int64_t m_total, int64_t k, int64_t n, int64_t num_groups) {
+  if (num_groups < 1) num_groups = 1;
+  const int sk = (k > 0 && k % 128 == 0) ? group_quant_splitk(m_total, static_cast<int>(k), static_cast<int>(n)) : 1;
+  return group_quant_prefix_bytes(num_groups) + (sk > 1 ? static_cast<int64_t>(sk) * m_total * n * 4 : 0);
+}
+
+extern "C" int mojo_hip_group_quant_gemm(const void* input, const void* weight, const float* input_scale, const void* weight_scale,
+                                         void* out, const void* group_list, int group_list_is_i64, int64_t m_total, int64_t k,
+                                         int64_t n, int64_t num_groups, int trans_weight, int out_dtype, void* workspace,
+                                         int64_t workspace_bytes, mojo_stream_t stream) {
+  MOJO_REQUIRE(num_groups > 0 && k > 0 && n > 0 && m_total >= 0, MOJO_EINVAL, "group_quant_gemm: bad shape");
+  if (m_total == 0) return MOJO_OK;
+  MOJO_REQUIRE(input && weight && input_scale && weight_scale && out && group_list, MOJO_EINVAL, "group_quant_gemm: null pointer");
+  MOJO_REQUIRE(trans_weight, MOJO_EUNSUPPORTED, "group_quant_gemm: [G, K, N] weights (the experts keep [G, N, K])");
+  MOJO_REQUIRE(out_dtype == MOJO_F32 || out_dtype == MOJO_F16 || out_dtype == MOJO_BF16, MOJO_EUNSUPPORTED,
+               "group_quant_gemm: output dtype %d", out_dtype);
+  MOJO_REQUIRE(m_total < (1LL << 31) && k < (1LL << 31) && n < (1LL << 31) && num_groups < (1 << 20) && m_total * n < (1LL << 40),
+               MOJO_EUNSUPPORTED, "group_quant_gemm: dimension too large");
+  MOJO_REQUIRE(workspace && workspace_bytes >= mojo_hip_group_quant_gemm_workspace_bytes(m_total, k, n, num_groups) && aligned_to(workspace, 16),
+               MOJO_EWORKSPACE, "group_quant_gemm: workspace too small");
+  GemmArgs a;
+  a.A = input; a.W = weight; a.C = out; a.bias = nullptr;
+  a.lda = k; a.ldc = n; a.w_group = k * n; a.w_k = 1; a.w_n = k;
+  a.K = static_cast<int>(k); a.N = static_cast<int>(n); a.G = static_cast<int>(num_groups);
+  int32_t* ws = static_cast<int32_t*>(workspace);
+  a.row_start = ws; a.tile_start = ws + (num_groups + 1);
+  void* slab_ws = static_cast<char*>(workspace) + group_quant_prefix_bytes(num_groups);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bf16_t* cs = static_cast<const bf16_t*>(weight_scale);
+  switch (out_dtype) {
+    case MOJO_F32: return run_group_quant<float>(a, input_scale, cs, group_list, group_list_is_i64, m_total, slab_ws, ws, s);
+    case MOJO_F16: return run_group_quant<f16_t>(a, input_scale, cs, group_list, group_list_is_i64, m_total, slab_ws, ws, s);
+    default: return run_group_quant<bf16_t>(a, input_scale, cs, group_list, group_list_is_i64, m_total, slab_ws, ws, s);
   }
 }
