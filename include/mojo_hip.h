@@ -589,6 +589,47 @@ int mojo_hip_peer_pull(void* const* peer_data, void* const* peer_flags, int64_t 
                        int64_t flag_chunk, uint32_t epoch, int64_t src_offset_bytes, int64_t bytes, void* dst,
                        int64_t dst_stride_bytes, int include_self, mojo_stream_t stream);
 
+/* ---- The sampling step (core/operators/sampling.py: MojoTopKSampling, MojoTopPSampling, MojoTopPFilter,
+ *      MojoApplyPenaltiesTempurate, MojoRejectSampling, MojoJoinProbRejectSampling).
+ *      Top-K stage: the K largest of each row of logits [rows, vocab] (f32 / f16 / bf16, dense, read once) in descending
+ *      order; among equal values the lower index first, a tie across position K keeps the lower indices.  Exact and
+ *      deterministic; k <= vocab and k <= sampling_max_k (MOJO_EUNSUPPORTED above).  -inf is legal, NaN / +inf are not.
+ *      Nucleus mask over the K sorted values v: p = softmax(v); over = running_sum(p) > top_p; the first
+ *      min_tokens_to_keep - 1 positions of `over` cleared; removed = over moved one position right, position 0 kept; removed
+ *      positions take filter_value (it may be finite); final = softmax of the result.
+ *      top_p_filter writes final (in `dtype`) and the int64 indices, both [rows, k].
+ *      sample_with_uniforms picks per row the first position whose running sum of final exceeds uniforms[row] * total
+ *      (fp32 uniforms in [0, 1)), held to the last position of non-zero probability, and writes its probability (fp32 [rows])
+ *      and token (int64 [rows]); nucleus == 0: final is the plain softmax of the K values (top_p, min_tokens_to_keep and
+ *      filter_value unused).  Two launches, no host synchronisation, nothing allocated: capturable in a graph.
+ *      `slices`: workgroups per row of the first pass, 0 = the library chooses; every count gives the same bits.  The
+ *      workspace query (host only) takes the same count; the workspace must be 8-byte aligned.
+ *      apply_penalties: one elementwise launch over [rows, vocab] (rows < 65536), out may be logits itself.  row_table is a
+ *      device array of rows x 32 bytes: float frequency, presence, repetition, temperature; int32 flags (1 frequency, 2
+ *      presence, 4 repetition, 8 temperature: which steps run); int32 padding; the 64-bit device address of the row's
+ *      frequency vector [vocab] (unused without flags 1 | 2 | 4).  freq_kind: 0 int32, 1 int64, 2 fp32, one for all rows.
+ *      Per element in fp32, each operation rounded on its own: l -= frequency * f; l -= presence * (f > 0); by the sign of
+ *      l * f: l * repetition (negative) or l / repetition (positive); l /= temperature.
+ *      reject_sampling: target_probs [batch, steps + 1, vocab] and draft_probs [batch, steps] in `dtype`, draft_tokens int64
+ *      [batch, steps], fp32 uniforms [batch] (joint == 0) or [batch, steps] (joint != 0).  next_tokens int64
+ *      [batch, steps + 1] = [draft_tokens | 0].  joint == 0: accepted_len int64 [batch], the first j with target / draft < u,
+ *      else steps.  joint != 0: accepted_len int32 [batch], one past the last j where NOT cumprod(clamp(target / draft, 0, 1))
+ *      [j] < cumprod(u)[j], else 0.  One launch, one thread per row, products left to right.                             */
+int64_t mojo_hip_sampling_max_k(void);
+int64_t mojo_hip_sampling_workspace_bytes(int64_t rows, int64_t vocab, int64_t k, int64_t slices);
+int mojo_hip_top_p_filter(const void* logits, void* probs, int64_t* indices, int64_t rows, int64_t vocab, int64_t k,
+                          float top_p, int64_t min_tokens_to_keep, float filter_value, int64_t slices, int dtype,
+                          void* workspace, int64_t workspace_bytes, mojo_stream_t stream);
+int mojo_hip_sample_with_uniforms(const void* logits, const float* uniforms, float* next_probs, int64_t* next_tokens,
+                                  int64_t rows, int64_t vocab, int64_t k, int nucleus, float top_p,
+                                  int64_t min_tokens_to_keep, float filter_value, int64_t slices, int dtype,
+                                  void* workspace, int64_t workspace_bytes, mojo_stream_t stream);
+int mojo_hip_apply_penalties(const void* logits, void* out, const void* row_table, int64_t rows, int64_t vocab, int dtype,
+                             int freq_kind, mojo_stream_t stream);
+int mojo_hip_reject_sampling(const void* target_probs, const int64_t* draft_tokens, const void* draft_probs,
+                             const float* uniforms, int64_t* next_tokens, void* accepted_len, int64_t batch,
+                             int64_t steps, int64_t vocab, int joint, int dtype, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,3 +13,5 @@ from .operators.compute_with_comm import (HIPAllGatherGemm, HIPGemmAll2All, HIPG
 from .operators.moe import (HIPExperts, HIPMoE, HIPMoECombine, HIPMoEDispatch, HIPMoEGating, HIPQuantExperts,  # noqa: F401
                             HIPQuantMoE)
 from .operators.quantize import HIPDynamicQuant, HIPMoEDynamicQuant, HIPResidualAddRMSNormQuant  # noqa: F401
+from .operators.sampling import (HIPApplyPenaltiesTempurate, HIPJoinProbRejectSampling, HIPRejectSampling,  # noqa: F401
+                                 HIPTopKSampling, HIPTopPFilter, HIPTopPSampling)

@@ -114,6 +114,12 @@ SIGNATURES = {
     "mojo_hip_group_quant_gemm_workspace_bytes": (c_int64, [_I, _I, _I, _I]),
     "mojo_hip_group_quant_gemm": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _I, _I, _I, _I, c_int, c_int, _P, _I, _P]),
     "mojo_hip_moe_dynamic_quant": (c_int, [_P, _P, _P, c_int, _P, _P, _I, _I, _I, c_int, c_int, _P]),
+    "mojo_hip_sampling_max_k": (c_int64, []),
+    "mojo_hip_sampling_workspace_bytes": (c_int64, [_I, _I, _I, _I]),
+    "mojo_hip_top_p_filter": (c_int, [_P, _P, _P, _I, _I, _I, c_float, _I, c_float, _I, c_int, _P, _I, _P]),
+    "mojo_hip_sample_with_uniforms": (c_int, [_P, _P, _P, _P, _I, _I, _I, c_int, c_float, _I, c_float, _I, c_int, _P, _I, _P]),
+    "mojo_hip_apply_penalties": (c_int, [_P, _P, _P, _I, _I, c_int, c_int, _P]),
+    "mojo_hip_reject_sampling": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, c_int, c_int, _P]),
 }
 
 _lock = threading.Lock()

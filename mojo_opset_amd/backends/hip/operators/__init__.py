@@ -6,3 +6,5 @@ from .mla import *  # noqa: F401,F403
 from .compute_with_comm import *  # noqa: F401,F403
 from .moe import *  # noqa: F401,F403
 from .quantize import *  # noqa: F401,F403
+from .sampling import (HIPApplyPenaltiesTempurate, HIPJoinProbRejectSampling, HIPRejectSampling, HIPTopKSampling,  # noqa: F401
+                       HIPTopPFilter, HIPTopPSampling)

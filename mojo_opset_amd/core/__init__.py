@@ -7,6 +7,8 @@ from .operators import EXTENDED_OPS, MojoPagedDecodeSWA, MojoPagedPrefillSWA  # 
 from .operators import (KV_INT8_OPS, MojoPagedDecodeGQAWithKVDequant, MojoPagedPrefillGQAWithKVDequant,  # noqa: F401
                         MojoStorePagedKVCacheC8)
 from .operators import QUANT_MOE_OPS, MojoMoEDynamicQuant, MojoQuantExperts, MojoQuantMoE  # noqa: F401
+from .operators import (SAMPLING_OPS, MojoApplyPenaltiesTempurate, MojoJoinProbRejectSampling, MojoRejectSampling,  # noqa: F401
+                        MojoTopKSampling, MojoTopPFilter, MojoTopPSampling)
 from .platform import get_dist_backend, get_platform, get_torch_device
 
 __all__ = ["MojoOperator", "MojoBackendRegistry", "check_tol_diff", "get_platform", "get_torch_device",

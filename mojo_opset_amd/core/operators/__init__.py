@@ -11,6 +11,8 @@ from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEG
 from .normalization import MojoResidualAddRMSNorm, MojoRMSNorm, MojoRMSNormInplace
 from .position_embedding import MojoApplyRoPE, MojoRotaryEmbedding
 from .quantize import MojoDynamicQuant, MojoMoEDynamicQuant, MojoResidualAddRMSNormQuant
+from .sampling import (MojoApplyPenaltiesTempurate, MojoJoinProbRejectSampling, MojoRejectSampling, MojoTopKSampling,
+                       MojoTopPFilter, MojoTopPSampling)
 
 __all__ = [
     "MojoSwiGLU", "MojoPagedDecodeGQA", "MojoPagedPrefillGQA", "MojoAllGatherGemm", "MojoGemmAll2All",
@@ -29,3 +31,7 @@ KV_INT8_OPS = ("MojoStorePagedKVCacheC8", "MojoPagedDecodeGQAWithKVDequant", "Mo
 # W8A8 MoE experts (the reference's quantised MoE: per-expert smooth quantiser, int8 experts, the layer): same standing again;
 # goldens in tests/quant_moe_golden.py.
 QUANT_MOE_OPS = ("MojoMoEDynamicQuant", "MojoQuantExperts", "MojoQuantMoE")
+# The sampling step (top-k / top-p over the vocabulary, speculative acceptance, penalties): same standing once more; goldens
+# in tests/sampling_golden.py.
+SAMPLING_OPS = ("MojoTopKSampling", "MojoTopPSampling", "MojoTopPFilter", "MojoRejectSampling", "MojoJoinProbRejectSampling",
+                "MojoApplyPenaltiesTempurate")

@@ -1,0 +1,146 @@
+"""Torch goldens of the sampling ops (`SAMPLING_OPS`): top-k / top-p samplers, the nucleus filter, the two speculative
+acceptance steps and the penalties.
+
+Ops beyond the SURVEY §8 set carry their goldens here, in the tests.  Importing this module registers ``Torch<Op>`` as the
+``torch`` backend of each of the six API classes.  Semantics restate `mojo_opset/core/operators/sampling.py`;
+`tests/golden/sampling.pt` pins them to the reference's recorded outputs bit for bit.
+
+* `topk_sorted`: the reference calls ``torch.topk``, which leaves the order among equal values open.  Here it is pinned: a
+  STABLE descending sort, so among equal values the lower index comes first and a tie that straddles position K keeps the
+  lower indices.  On tie-free input that is ``torch.topk`` bit for bit (the fixture generator asserts its inputs tie-free).
+* `nucleus`: softmax, cumulative sum, ``cum > top_p``, the ``min_tokens_to_keep - 1`` leading positions cleared, the mask
+  moved one position right with position 0 kept, ``filter_value`` written (it may be finite), second softmax.
+* samplers: ``torch.multinomial`` draws, as in the reference; the draw itself is not part of any recorded output.
+* reject samplers: ``uniforms=`` injects the random numbers (a GPU test draws them on the device and hands them over);
+  without it they are drawn with ``torch.rand`` on the inputs' device after the optional reseed, as the reference does.
+* penalties: the reference's per-row sequence of torch operations, so every rounding point is the same.
+"""
+import torch
+
+from mojo_opset_amd.core.operators import sampling as _core
+
+_CPU = ["rocm", "cpu"]
+
+
+def topk_sorted(logits32: torch.Tensor, k: int):
+    """(values fp32 [..., k] descending, indices int64 [..., k]); equal values in ascending index order."""
+    values, indices = torch.sort(logits32, dim=-1, descending=True, stable=True)
+    return values[..., :k].contiguous(), indices[..., :k].contiguous()
+
+
+def removed_mask(cumulative: torch.Tensor, top_p: float, min_tokens_to_keep: int) -> torch.Tensor:
+    """The positions that take ``filter_value``, from the running sum of the first softmax."""
+    over = cumulative > top_p
+    if min_tokens_to_keep > 1:
+        over[..., : min_tokens_to_keep - 1] = False
+    removed = torch.zeros_like(over)
+    removed[..., 1:] = over[..., :-1]
+    return removed
+
+
+def nucleus(values: torch.Tensor, top_p: float, min_tokens_to_keep: int, filter_value: float) -> torch.Tensor:
+    """``final_probs_dist`` fp32 over the sorted top-k ``values``."""
+    cumulative = values.softmax(dim=-1).cumsum(dim=-1)
+    removed = removed_mask(cumulative, top_p, min_tokens_to_keep)
+    return torch.softmax(values.masked_fill(removed, filter_value), dim=-1)
+
+
+def top_p_filter(logits, top_p, min_tokens_to_keep, rand_top_k, filter_value):
+    """(final_probs_dist fp32, indices, sorted values): the filter before its cast back to the input dtype."""
+    x = logits.to(torch.float32)
+    values, indices = topk_sorted(x, min(rand_top_k, x.size(-1)))
+    return nucleus(values, top_p, min_tokens_to_keep, filter_value), indices, values
+
+
+def draw(final_probs_dist: torch.Tensor, indices: torch.Tensor):
+    pick = torch.multinomial(final_probs_dist, num_samples=1)
+    return torch.gather(final_probs_dist, -1, pick), torch.gather(indices, -1, pick)
+
+
+def gathered_target(target_probs, draft_tokens, steps):
+    return torch.gather(target_probs[:, :steps, :], -1, draft_tokens.unsqueeze(-1)).squeeze(-1)
+
+
+def with_sentinel(draft_tokens):
+    zero = torch.zeros((draft_tokens.shape[0], 1), dtype=torch.long, device=draft_tokens.device)
+    return torch.cat([draft_tokens, zero], dim=-1)
+
+
+class TorchTopKSampling(_core.MojoTopKSampling):
+    supported_platforms_list = _CPU
+
+    def forward(self, logits: torch.Tensor):
+        x = logits.to(torch.float32)
+        values, indices = topk_sorted(x, self.effective_k(x.size(-1)))
+        return draw(torch.softmax(values, dim=-1), indices)
+
+
+class TorchTopPSampling(_core.MojoTopPSampling):
+    supported_platforms_list = _CPU
+
+    def forward(self, logits: torch.Tensor):
+        probs, indices, _ = top_p_filter(logits, self.top_p, self.min_tokens_to_keep, self.rand_top_k, self.filter_value)
+        return draw(probs, indices)
+
+
+class TorchTopPFilter(_core.MojoTopPFilter):
+    supported_platforms_list = _CPU
+
+    def forward(self, logits: torch.Tensor, top_p: float, min_tokens_to_keep: int, rand_top_k: int):
+        probs, indices, _ = top_p_filter(logits, top_p, min_tokens_to_keep, rand_top_k, self.filter_value)
+        return probs.to(logits.dtype), indices
+
+
+class TorchRejectSampling(_core.MojoRejectSampling):
+    supported_platforms_list = _CPU
+
+    def forward(self, target_probs, draft_tokens, draft_probs, random_seed=None, uniforms=None):
+        rows, steps = target_probs.shape[0], draft_probs.shape[1]
+        device = target_probs.device
+        if random_seed is not None:
+            torch.manual_seed(random_seed)
+        u = torch.rand(rows, 1, device=device) if uniforms is None else uniforms.reshape(rows, 1).to(device)
+        rejected = (gathered_target(target_probs, draft_tokens, steps) / draft_probs) < u
+        # the first rejected position, `steps` when none: the first maximum of [rejected | 1]
+        flags = torch.cat([rejected.int(), torch.ones((rows, 1), device=device)], dim=1)
+        return with_sentinel(draft_tokens), torch.argmax(flags, dim=1)
+
+
+class TorchJoinProbRejectSampling(_core.MojoJoinProbRejectSampling):
+    supported_platforms_list = _CPU
+
+    def forward(self, target_probs, draft_tokens, draft_probs, random_seed=None, uniforms=None):
+        rows, steps = target_probs.shape[0], draft_probs.shape[1]
+        device = target_probs.device
+        accept = torch.cumprod(torch.clamp(gathered_target(target_probs, draft_tokens, steps) / draft_probs, 0, 1), dim=1)
+        if random_seed is not None:
+            torch.manual_seed(random_seed)
+        u = torch.rand(rows, steps, device=device) if uniforms is None else uniforms.reshape(rows, steps).to(device)
+        rejected = accept < torch.cumprod(u, dim=1)
+        # one past the last position that is not rejected: the first minimum of [0 | rejected] read from the right
+        flags = torch.cat([torch.zeros((rows, 1), device=device), rejected.int()], dim=1)
+        accepted = steps - flags.flip(dims=[1]).argmin(dim=1).int()
+        return with_sentinel(draft_tokens), accepted.int()
+
+
+class TorchApplyPenaltiesTempurate(_core.MojoApplyPenaltiesTempurate):
+    supported_platforms_list = _CPU
+
+    def forward(self, logits, token_freqs, presence_penalties, frequency_penalties, repetition_penalties, temps=None):
+        self.check_call_contract(logits, token_freqs, presence_penalties, frequency_penalties, repetition_penalties, temps)
+        dtype = logits.dtype
+        x = logits.to(torch.float32)                       # the same tensor for an fp32 input: updated in place
+        for i, freq in enumerate(token_freqs):
+            if freq is not None:
+                f = freq.to(x.device, non_blocking=True)
+                if frequency_penalties[i] != 0.0:
+                    x[i] -= frequency_penalties[i] * f
+                if presence_penalties[i] != 0.0:
+                    x[i] -= presence_penalties[i] * (f > 0)
+                if repetition_penalties[i] != 1.0:
+                    sign = x[i] * f
+                    x[i] = torch.where(sign < 0, x[i] * repetition_penalties[i],
+                                       torch.where(sign > 0, x[i] / repetition_penalties[i], x[i]))
+            if temps is not None and temps[i] is not None:
+                x[i] /= temps[i]
+        return x.to(dtype)
