@@ -31,6 +31,98 @@ def _check_cache_layout(key_cache, value_cache, what):
         raise NotImplementedError(f"{what}: key/value caches must share strides and be dense in head_dim")
 
 
+def _paged_decode(op, what, symbols, query, key_cache, value_cache, total_seq_lens, block_tables, softmax_scale,
+                 max_total_seq_len, leave_empty_rows, scales=None, windows=()):
+    """The host path of every paged decode op, from the opt-in table check to the launch.  ``what``: the class name in
+    messages; ``symbols``: the C workspace query and entry point; ``scales``: (key_scale, value_scale) of the int8 cache,
+    dense; ``windows``: (local, global) of the SWA ABI.  The caller has checked its own contract and envelope."""
+    batch, hq, dim = query.shape
+    hkv, page = key_cache.shape[1], key_cache.shape[2]
+    if _validate_tables() and batch > 0 and block_tables.shape[1] > 0:
+        if bool(((total_seq_lens > 0) & (block_tables[:, 0] < 0)).any()):
+            raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
+        if max_total_seq_len is not None and int(total_seq_lens.max()) > int(max_total_seq_len):
+            raise ValueError(f"{what}: a total_seq_lens entry exceeds max_total_seq_len")
+    q = query if query.is_contiguous() else query.contiguous()
+    tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
+    lens = total_seq_lens if total_seq_lens.is_contiguous() else total_seq_lens.contiguous()
+    scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
+    hint = int(max_total_seq_len) if max_total_seq_len is not None else 0
+    out = torch.empty_like(q)
+    lib = L.load()
+    ws_bytes = getattr(lib, symbols[0])(batch, hq, hkv, dim, page, tables.shape[1], hint, *windows)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    if scales is None:
+        caches, extra = (L.ptr(key_cache), L.ptr(value_cache)), windows
+    else:
+        caches = (L.ptr(key_cache), L.ptr(scales[0]), L.ptr(value_cache), L.ptr(scales[1]))
+        extra = (L.dtype_code(scales[0].dtype),)
+    L.check(getattr(lib, symbols[1])(
+        L.ptr(q), *caches, L.ptr(lens), L.ptr(tables), L.ptr(out), L.ptr(ws),
+        ws.numel(), batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
+        key_cache.stride(1), key_cache.stride(2), hint, scale, 1 if op.gqa_layout == "ABAB" else 0,
+        # replay contract of padded rows (seq_len <= 0): untouched while a graph is being captured, zeros eagerly
+        1 if (_capturing(q) if leave_empty_rows is None else leave_empty_rows) else 0,
+        L.dtype_code(q.dtype), *extra, L.stream_of(q)), what)
+    return out
+
+
+def _paged_prefill(op, what, symbols, query, key_cache, value_cache, cu_q_lens, block_tables, softmax_scale,
+                  cu_total_seq_lens, max_q_len, max_total_seq_len, scales=None, windows=()):
+    """The host path of every paged prefill op (arguments as `_paged_decode`).  The int8 op's workspace holds its scratch
+    pages, so it is never absent, and its hint is checked as the upper bound it must be there."""
+    tokens, hq, dim = query.shape
+    n_blocks, hkv, page = key_cache.shape[:3]
+    batch = cu_q_lens.shape[0] - 1
+    if _validate_tables() and batch > 0 and block_tables.shape[1] > 0:
+        q_lens = cu_q_lens[1:] - cu_q_lens[:-1]
+        kv_lens = q_lens if cu_total_seq_lens is None else cu_total_seq_lens[1:] - cu_total_seq_lens[:-1]
+        if bool(((q_lens > 0) & (kv_lens > 0) & (block_tables[:, 0] < 0)).any()):
+            raise ValueError("Paged prefill requires a valid block table for rows with kv lens > 0.")
+        if scales is not None and max_total_seq_len and int(kv_lens.max()) > int(max_total_seq_len):
+            raise ValueError(f"{what}: a sequence's kv length exceeds max_total_seq_len (the hint sizes the scratch "
+                             f"pages: it must be an upper bound)")
+    q = query if query.is_contiguous() else query.contiguous()
+    tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
+    cu_q = cu_q_lens.contiguous()
+    cu_kv = None if cu_total_seq_lens is None else cu_total_seq_lens.contiguous()
+    scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
+    out = torch.empty_like(q)
+    lib = L.load()
+    hint_q = int(max_q_len) if max_q_len else 0
+    hint_kv = int(max_total_seq_len) if max_total_seq_len else 0
+    # few, long blocks (a chunked prefill against a long cache) are cut along the keys: fp32 partials + a merge launch
+    ws_bytes = getattr(lib, symbols[0])(tokens, batch, hq, hkv, dim, page, tables.shape[1], hint_q, hint_kv, *windows)
+    if scales is None:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes > 0 else None
+        caches, pool, extra = (L.ptr(key_cache), L.ptr(value_cache)), (), ()
+    else:
+        ws_bytes = max(ws_bytes, 256)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)   # (the allocator aligns to >= 256 bytes)
+        caches = (L.ptr(key_cache), L.ptr(scales[0]), L.ptr(value_cache), L.ptr(scales[1]))
+        pool, extra = (n_blocks,), (L.dtype_code(scales[0].dtype),)
+    L.check(getattr(lib, symbols[1])(
+        L.ptr(q), *caches, L.ptr(cu_q), L.ptr(cu_kv), L.ptr(tables), L.ptr(out),
+        tokens, batch, hq, hkv, dim, *pool, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
+        key_cache.stride(1), key_cache.stride(2), hint_q, hint_kv, scale,
+        1 if op.gqa_layout == "ABAB" else 0, L.dtype_code(q.dtype), *extra, L.ptr(ws), ws_bytes, *windows, L.stream_of(q)), what)
+    return out
+
+
+def _check_16bit_caches(what, query, key_cache, value_cache):
+    hq, dim = query.shape[1:]
+    n_blocks, hkv, page, dim_c = key_cache.shape
+    assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
+    assert query.dtype == key_cache.dtype == value_cache.dtype
+    _check_cache_layout(key_cache, value_cache, what)
+
+
+_DECODE_GQA = ("mojo_hip_paged_decode_gqa_workspace_bytes", "mojo_hip_paged_decode_gqa")
+_DECODE_SWA = ("mojo_hip_paged_decode_swa_workspace_bytes", "mojo_hip_paged_decode_swa")
+_PREFILL_GQA = ("mojo_hip_paged_prefill_gqa_workspace_bytes", "mojo_hip_paged_prefill_gqa")
+_PREFILL_SWA = ("mojo_hip_paged_prefill_swa_workspace_bytes", "mojo_hip_paged_prefill_swa")
+
+
 class HIPPagedDecodeGQA(MojoPagedDecodeGQA):
     supported_platforms_list = _ROCM
 
@@ -41,33 +133,9 @@ class HIPPagedDecodeGQA(MojoPagedDecodeGQA):
         if not self.is_causal or mask is not None:
             raise NotImplementedError("HIPPagedDecodeGQA supports causal attention without an explicit mask only")
         L.require_cuda(query, key_cache, value_cache, total_seq_lens, block_tables)
-        batch, hq, dim = query.shape
-        n_blocks, hkv, page, dim_c = key_cache.shape
-        assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
-        assert query.dtype == key_cache.dtype == value_cache.dtype
-        _check_cache_layout(key_cache, value_cache, "HIPPagedDecodeGQA")
-        if _validate_tables() and batch > 0 and block_tables.shape[1] > 0:
-            if bool(((total_seq_lens > 0) & (block_tables[:, 0] < 0)).any()):
-                raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
-            if max_total_seq_len is not None and int(total_seq_lens.max()) > int(max_total_seq_len):
-                raise ValueError("HIPPagedDecodeGQA: a total_seq_lens entry exceeds max_total_seq_len")
-        q = query if query.is_contiguous() else query.contiguous()
-        tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
-        lens = total_seq_lens if total_seq_lens.is_contiguous() else total_seq_lens.contiguous()
-        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
-        hint = int(max_total_seq_len) if max_total_seq_len is not None else 0
-        out = torch.empty_like(q)
-        lib = L.load()
-        ws_bytes = lib.mojo_hip_paged_decode_gqa_workspace_bytes(batch, hq, hkv, dim, page, tables.shape[1], hint)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
-        L.check(lib.mojo_hip_paged_decode_gqa(
-            L.ptr(q), L.ptr(key_cache), L.ptr(value_cache), L.ptr(lens), L.ptr(tables), L.ptr(out), L.ptr(ws),
-            ws.numel(), batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
-            key_cache.stride(1), key_cache.stride(2), hint, scale, 1 if self.gqa_layout == "ABAB" else 0,
-            # replay contract of padded rows (seq_len <= 0): untouched while a graph is being captured, zeros eagerly
-            1 if (_capturing(q) if leave_empty_rows is None else leave_empty_rows) else 0,
-            L.dtype_code(q.dtype), L.stream_of(q)), "HIPPagedDecodeGQA")
-        return out
+        _check_16bit_caches("HIPPagedDecodeGQA", query, key_cache, value_cache)
+        return _paged_decode(self, "HIPPagedDecodeGQA", _DECODE_GQA, query, key_cache, value_cache, total_seq_lens,
+                             block_tables, softmax_scale, max_total_seq_len, leave_empty_rows)
 
 
 class HIPPagedPrefillGQA(MojoPagedPrefillGQA):
@@ -80,35 +148,9 @@ class HIPPagedPrefillGQA(MojoPagedPrefillGQA):
         if not self.is_causal or mask is not None:
             raise NotImplementedError("HIPPagedPrefillGQA supports causal attention without an explicit mask only")
         L.require_cuda(query, key_cache, value_cache, cu_q_lens, block_tables, cu_total_seq_lens)
-        tokens, hq, dim = query.shape
-        n_blocks, hkv, page, dim_c = key_cache.shape
-        assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
-        assert query.dtype == key_cache.dtype == value_cache.dtype
-        _check_cache_layout(key_cache, value_cache, "HIPPagedPrefillGQA")
-        batch = cu_q_lens.shape[0] - 1
-        if _validate_tables() and batch > 0 and block_tables.shape[1] > 0:
-            q_lens = cu_q_lens[1:] - cu_q_lens[:-1]
-            kv_lens = q_lens if cu_total_seq_lens is None else cu_total_seq_lens[1:] - cu_total_seq_lens[:-1]
-            if bool(((q_lens > 0) & (kv_lens > 0) & (block_tables[:, 0] < 0)).any()):
-                raise ValueError("Paged prefill requires a valid block table for rows with kv lens > 0.")
-        q = query if query.is_contiguous() else query.contiguous()
-        tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
-        cu_q = cu_q_lens.contiguous()
-        cu_kv = None if cu_total_seq_lens is None else cu_total_seq_lens.contiguous()
-        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
-        out = torch.empty_like(q)
-        lib = L.load()
-        hint_q = int(max_q_len) if max_q_len else 0
-        hint_kv = int(max_total_seq_len) if max_total_seq_len else 0
-        # few, long blocks (a chunked prefill against a long cache) are cut along the keys: fp32 partials + a merge launch
-        ws_bytes = lib.mojo_hip_paged_prefill_gqa_workspace_bytes(tokens, batch, hq, hkv, dim, page, tables.shape[1], hint_q, hint_kv)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes > 0 else None
-        L.check(lib.mojo_hip_paged_prefill_gqa(
-            L.ptr(q), L.ptr(key_cache), L.ptr(value_cache), L.ptr(cu_q), L.ptr(cu_kv), L.ptr(tables), L.ptr(out),
-            tokens, batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
-            key_cache.stride(1), key_cache.stride(2), hint_q, hint_kv, scale,
-            1 if self.gqa_layout == "ABAB" else 0, L.dtype_code(q.dtype), L.ptr(ws), ws_bytes, L.stream_of(q)), "HIPPagedPrefillGQA")
-        return out
+        _check_16bit_caches("HIPPagedPrefillGQA", query, key_cache, value_cache)
+        return _paged_prefill(self, "HIPPagedPrefillGQA", _PREFILL_GQA, query, key_cache, value_cache, cu_q_lens,
+                              block_tables, softmax_scale, cu_total_seq_lens, max_q_len, max_total_seq_len)
 
 
 def _swa_windows(op, what):
@@ -126,53 +168,24 @@ def _swa_windows(op, what):
 
 class HIPPagedDecodeSWA(MojoPagedDecodeSWA):
     """Sliding-window paged decode: the GQA decode kernels walking only the tiles of the global and local ranges (DESIGN
-    §4.10).  With no window, or ``is_causal=False`` (no mask at all), it is `HIPPagedDecodeGQA`'s entry point."""
+    §4.10).  With no window, or ``is_causal=False`` (no mask at all), its entry point runs the GQA op itself, bit for bit."""
     supported_platforms_list = _ROCM
 
     def forward(self, query, key_cache, value_cache, total_seq_lens, block_table, softmax_scale: Optional[float] = None,
                 *, max_total_seq_len: Optional[int] = None, leave_empty_rows: Optional[bool] = None):
         assert_paged_decode_contract(block_table, total_seq_lens)
-        local, glob = _swa_windows(self, "HIPPagedDecodeSWA")
+        windows = _swa_windows(self, "HIPPagedDecodeSWA")
         if not self.is_causal:
-            local, glob = -1, 0
+            windows = (-1, 0)
         L.require_cuda(query, key_cache, value_cache, total_seq_lens, block_table)
-        batch, hq, dim = query.shape
-        n_blocks, hkv, page, dim_c = key_cache.shape
-        assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
-        assert query.dtype == key_cache.dtype == value_cache.dtype
-        _check_cache_layout(key_cache, value_cache, "HIPPagedDecodeSWA")
-        if _validate_tables() and batch > 0 and block_table.shape[1] > 0:
-            if bool(((total_seq_lens > 0) & (block_table[:, 0] < 0)).any()):
-                raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
-            if max_total_seq_len is not None and int(total_seq_lens.max()) > int(max_total_seq_len):
-                raise ValueError("HIPPagedDecodeSWA: a total_seq_lens entry exceeds max_total_seq_len")
-        q = query if query.is_contiguous() else query.contiguous()
-        tables = block_table if block_table.stride(1) == 1 else block_table.contiguous()
-        lens = total_seq_lens if total_seq_lens.is_contiguous() else total_seq_lens.contiguous()
-        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
-        hint = int(max_total_seq_len) if max_total_seq_len is not None else 0
-        out = torch.empty_like(q)
-        lib = L.load()
-        gqa = local < 0 and glob <= 0                     # no window: the GQA op itself, bit for bit
-        geometry = (batch, hq, hkv, dim, page, tables.shape[1], hint)
-        ws_bytes = (lib.mojo_hip_paged_decode_gqa_workspace_bytes(*geometry) if gqa else
-                    lib.mojo_hip_paged_decode_swa_workspace_bytes(*geometry, local, glob))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
-        args = [L.ptr(q), L.ptr(key_cache), L.ptr(value_cache), L.ptr(lens), L.ptr(tables), L.ptr(out), L.ptr(ws),
-                ws.numel(), batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
-                key_cache.stride(1), key_cache.stride(2), hint, scale, 1 if self.gqa_layout == "ABAB" else 0,
-                # replay contract of padded rows (seq_len <= 0): untouched while a graph is being captured, zeros eagerly
-                1 if (_capturing(q) if leave_empty_rows is None else leave_empty_rows) else 0, L.dtype_code(q.dtype)]
-        if gqa:
-            L.check(lib.mojo_hip_paged_decode_gqa(*args, L.stream_of(q)), "HIPPagedDecodeSWA")
-        else:
-            L.check(lib.mojo_hip_paged_decode_swa(*args, local, glob, L.stream_of(q)), "HIPPagedDecodeSWA")
-        return out
+        _check_16bit_caches("HIPPagedDecodeSWA", query, key_cache, value_cache)
+        return _paged_decode(self, "HIPPagedDecodeSWA", _DECODE_SWA, query, key_cache, value_cache, total_seq_lens,
+                             block_table, softmax_scale, max_total_seq_len, leave_empty_rows, windows=windows)
 
 
 class HIPPagedPrefillSWA(MojoPagedPrefillSWA):
     """Sliding-window paged prefill: the GQA prefill kernel walking the key tiles of the global range and of the block's
-    local range only.  With no window it is `HIPPagedPrefillGQA`'s entry point."""
+    local range only.  With no window its entry point runs the GQA op itself, bit for bit."""
     supported_platforms_list = _ROCM
 
     def forward(self, query, key_cache, value_cache, cu_q_lens, block_table, softmax_scale: Optional[float] = None,
@@ -181,39 +194,8 @@ class HIPPagedPrefillSWA(MojoPagedPrefillSWA):
         assert_paged_prefill_contract(cu_q_lens, block_table, cu_total_seq_lens)
         if not self.is_causal:
             raise NotImplementedError("HIPPagedPrefillSWA supports causal attention only")
-        local, glob = _swa_windows(self, "HIPPagedPrefillSWA")
+        windows = _swa_windows(self, "HIPPagedPrefillSWA")
         L.require_cuda(query, key_cache, value_cache, cu_q_lens, block_table, cu_total_seq_lens)
-        tokens, hq, dim = query.shape
-        n_blocks, hkv, page, dim_c = key_cache.shape
-        assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
-        assert query.dtype == key_cache.dtype == value_cache.dtype
-        _check_cache_layout(key_cache, value_cache, "HIPPagedPrefillSWA")
-        batch = cu_q_lens.shape[0] - 1
-        if _validate_tables() and batch > 0 and block_table.shape[1] > 0:
-            q_lens = cu_q_lens[1:] - cu_q_lens[:-1]
-            kv_lens = q_lens if cu_total_seq_lens is None else cu_total_seq_lens[1:] - cu_total_seq_lens[:-1]
-            if bool(((q_lens > 0) & (kv_lens > 0) & (block_table[:, 0] < 0)).any()):
-                raise ValueError("Paged prefill requires a valid block table for rows with kv lens > 0.")
-        q = query if query.is_contiguous() else query.contiguous()
-        tables = block_table if block_table.stride(1) == 1 else block_table.contiguous()
-        cu_q = cu_q_lens.contiguous()
-        cu_kv = None if cu_total_seq_lens is None else cu_total_seq_lens.contiguous()
-        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
-        out = torch.empty_like(q)
-        lib = L.load()
-        hint_q = int(max_q_len) if max_q_len else 0
-        hint_kv = int(max_total_seq_len) if max_total_seq_len else 0
-        gqa = local < 0 and glob <= 0                     # no window: the GQA op itself, bit for bit
-        geometry = (tokens, batch, hq, hkv, dim, page, tables.shape[1], hint_q, hint_kv)
-        ws_bytes = (lib.mojo_hip_paged_prefill_gqa_workspace_bytes(*geometry) if gqa else
-                    lib.mojo_hip_paged_prefill_swa_workspace_bytes(*geometry, local, glob))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes > 0 else None
-        args = [L.ptr(q), L.ptr(key_cache), L.ptr(value_cache), L.ptr(cu_q), L.ptr(cu_kv), L.ptr(tables), L.ptr(out),
-                tokens, batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),
-                key_cache.stride(1), key_cache.stride(2), hint_q, hint_kv, scale,
-                1 if self.gqa_layout == "ABAB" else 0, L.dtype_code(q.dtype), L.ptr(ws), ws_bytes]
-        if gqa:
-            L.check(lib.mojo_hip_paged_prefill_gqa(*args, L.stream_of(q)), "HIPPagedPrefillSWA")
-        else:
-            L.check(lib.mojo_hip_paged_prefill_swa(*args, local, glob, L.stream_of(q)), "HIPPagedPrefillSWA")
-        return out
+        _check_16bit_caches("HIPPagedPrefillSWA", query, key_cache, value_cache)
+        return _paged_prefill(self, "HIPPagedPrefillSWA", _PREFILL_SWA, query, key_cache, value_cache, cu_q_lens,
+                              block_table, softmax_scale, cu_total_seq_lens, max_q_len, max_total_seq_len, windows=windows)

@@ -1,7 +1,6 @@
 """HIP<Op> classes of the int8 paged KV cache with per-channel scales: the quantising store and the decode / prefill
 GQA that read it.  Everything that is not built raises ``NotImplementedError`` on the host, before any
 device work."""
-import math
 from typing import Optional
 
 import torch
@@ -10,7 +9,7 @@ from ....core.operators.attention import (MojoPagedDecodeGQAWithKVDequant, MojoP
                                           assert_paged_decode_contract, assert_paged_prefill_contract)
 from ....core.operators.kv_cache import MojoStorePagedKVCacheC8, assert_paged_kv_layout_contract
 from .. import lib as L
-from .attention import _capturing, _validate_tables
+from .attention import _paged_decode, _paged_prefill
 
 __all__ = ["HIPStorePagedKVCacheC8", "HIPPagedDecodeGQAWithKVDequant", "HIPPagedPrefillGQAWithKVDequant"]
 
@@ -18,6 +17,8 @@ _ROCM = ["rocm"]
 _SCALE_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 _DECODE_DIMS = (64, 80, 96, 128)
 _PREFILL_DIMS = (64, 96, 128)
+_DECODE_KV8 = ("mojo_hip_paged_decode_gqa_kv8_workspace_bytes", "mojo_hip_paged_decode_gqa_kv8")
+_PREFILL_KV8 = ("mojo_hip_paged_prefill_gqa_kv8_workspace_bytes", "mojo_hip_paged_prefill_gqa_kv8")
 
 
 def _dense(t):
@@ -114,30 +115,8 @@ class HIPPagedDecodeGQAWithKVDequant(MojoPagedDecodeGQAWithKVDequant):
         if any(s % 16 for s in key_cache.stride()[:3]):
             raise NotImplementedError(f"{what}: cache strides must be multiples of 16 bytes")
         L.require_cuda(query, key_cache, value_cache, key_scale, value_scale, total_seq_lens, block_tables)
-        if _validate_tables() and batch > 0 and block_tables.shape[1] > 0:
-            if bool(((total_seq_lens > 0) & (block_tables[:, 0] < 0)).any()):
-                raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
-            if max_total_seq_len is not None and int(total_seq_lens.max()) > int(max_total_seq_len):
-                raise ValueError(f"{what}: a total_seq_lens entry exceeds max_total_seq_len")
-        q = _dense(query)
-        tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
-        lens = _dense(total_seq_lens)
-        key_scale, value_scale = _dense(key_scale), _dense(value_scale)
-        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
-        hint = int(max_total_seq_len) if max_total_seq_len is not None else 0
-        out = torch.empty_like(q)
-        lib = L.load()
-        ws_bytes = lib.mojo_hip_paged_decode_gqa_kv8_workspace_bytes(batch, hq, hkv, dim, page, tables.shape[1], hint)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
-        L.check(lib.mojo_hip_paged_decode_gqa_kv8(
-            L.ptr(q), L.ptr(key_cache), L.ptr(key_scale), L.ptr(value_cache), L.ptr(value_scale), L.ptr(lens),
-            L.ptr(tables), L.ptr(out), L.ptr(ws), ws.numel(), batch, hq, hkv, dim, page, tables.shape[1],
-            tables.stride(0), key_cache.stride(0), key_cache.stride(1), key_cache.stride(2), hint, scale,
-            1 if self.gqa_layout == "ABAB" else 0,
-            # replay contract of padded rows (seq_len <= 0): untouched while a graph is being captured, zeros eagerly
-            1 if (_capturing(q) if leave_empty_rows is None else leave_empty_rows) else 0,
-            L.dtype_code(q.dtype), L.dtype_code(key_scale.dtype), L.stream_of(q)), what)
-        return out
+        return _paged_decode(self, what, _DECODE_KV8, query, key_cache, value_cache, total_seq_lens, block_tables,
+                             softmax_scale, max_total_seq_len, leave_empty_rows, scales=(_dense(key_scale), _dense(value_scale)))
 
 
 class HIPPagedPrefillGQAWithKVDequant(MojoPagedPrefillGQAWithKVDequant):
@@ -166,32 +145,5 @@ class HIPPagedPrefillGQAWithKVDequant(MojoPagedPrefillGQAWithKVDequant):
         if any(s % 16 for s in key_cache.stride()[:3]):
             raise NotImplementedError(f"{what}: cache strides must be multiples of 16 bytes")
         L.require_cuda(query, key_cache, value_cache, key_scale, value_scale, cu_q_lens, block_tables, cu_total_seq_lens)
-        batch = cu_q_lens.shape[0] - 1
-        if _validate_tables() and batch > 0 and block_tables.shape[1] > 0:
-            q_lens = cu_q_lens[1:] - cu_q_lens[:-1]
-            kv_lens = q_lens if cu_total_seq_lens is None else cu_total_seq_lens[1:] - cu_total_seq_lens[:-1]
-            if bool(((q_lens > 0) & (kv_lens > 0) & (block_tables[:, 0] < 0)).any()):
-                raise ValueError("Paged prefill requires a valid block table for rows with kv lens > 0.")
-            if max_total_seq_len and int(kv_lens.max()) > int(max_total_seq_len):
-                raise ValueError(f"{what}: a sequence's kv length exceeds max_total_seq_len (the hint sizes the scratch "
-                                 f"pages: it must be an upper bound)")
-        q = _dense(query)
-        tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
-        cu_q = cu_q_lens.contiguous()
-        cu_kv = None if cu_total_seq_lens is None else cu_total_seq_lens.contiguous()
-        key_scale, value_scale = _dense(key_scale), _dense(value_scale)
-        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
-        out = torch.empty_like(q)
-        lib = L.load()
-        hint_q = int(max_q_len) if max_q_len else 0
-        hint_kv = int(max_total_seq_len) if max_total_seq_len else 0
-        ws_bytes = lib.mojo_hip_paged_prefill_gqa_kv8_workspace_bytes(tokens, batch, hq, hkv, dim, page, tables.shape[1],
-                                                                      hint_q, hint_kv)
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=q.device)   # (the allocator aligns to >= 256 bytes)
-        L.check(lib.mojo_hip_paged_prefill_gqa_kv8(
-            L.ptr(q), L.ptr(key_cache), L.ptr(key_scale), L.ptr(value_cache), L.ptr(value_scale), L.ptr(cu_q),
-            L.ptr(cu_kv), L.ptr(tables), L.ptr(out), tokens, batch, hq, hkv, dim, n_blocks, page, tables.shape[1],
-            tables.stride(0), key_cache.stride(0), key_cache.stride(1), key_cache.stride(2), hint_q, hint_kv, scale,
-            1 if self.gqa_layout == "ABAB" else 0, L.dtype_code(q.dtype), L.dtype_code(key_scale.dtype), L.ptr(ws),
-            ws.numel(), L.stream_of(q)), what)
-        return out
+        return _paged_prefill(self, what, _PREFILL_KV8, query, key_cache, value_cache, cu_q_lens, block_tables, softmax_scale,
+                              cu_total_seq_lens, max_q_len, max_total_seq_len, scales=(_dense(key_scale), _dense(value_scale)))

@@ -577,23 +577,6 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(DecodeArgs a, int G) 
   *reinterpret_cast<V4*>(dst) = o;
 }
 
-// The grouped form (DecodeArgs::fuse_group; matrix-core kernel only: the same conditions as decode_use_mfma, which the
-// workspace sizing cannot call) — MOJO_HIP_DECODE_GROUPED=0 restores the split + merge form.
-static bool decode_grouped(int64_t G, int64_t head_dim, int64_t page) {
-  // Measured (scripts/probes/decode_grouped_ab.py, profiles/r4_decode_grouped_ab.txt; split + merge form -> grouped form, graph
-  // replay): 8 q / 1 kv heads B 64 ctx 4096 (Llama-3-70B under TP 8) 33.6 -> 28.1 us, B 16 ctx 16384 38.2 -> 29.8 us; 32 / 8 heads
-  // B 8 ctx 4096 31.3 -> 27.5 us; 64 / 8 heads B 8 ctx 8192 56.1 -> 49.8 us; head_dim 64 B 8 ctx 8192 33.7 -> 28.6 us.
-  // (the grouped launch exists in the fused form only: without MOJO_HIP_DECODE_FUSE the chunks are sized, written and merged
-  // one by one — ADVICE r4: the merge kernel divided the chunk count by the group size although every chunk had its partial)
-  if (MOJO_SWITCH("MOJO_HIP_DECODE_GROUPED", 1) == 0 || MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) == 0) return false;
-  const bool pow2 = page > 0 && (page & (page - 1)) == 0;
-  if (!pow2 || page < 16 || (head_dim != 64 && head_dim != 128) || G > 16) return false;
-  const long long m = MOJO_SWITCH("MOJO_HIP_DECODE_MFMA", -1);
-  if (m == 0) return false;
-  if (m == 1) return true;
-  return G >= 4 || head_dim == 64 || (G != 1 && G != 2);
-}
-
 static int decode_chunk_tokens(int64_t batch, int64_t kv_heads, int64_t max_len, bool grouped = false) {
   {                                                            // tuning override
     const int v = static_cast<int>(MOJO_SWITCH("MOJO_HIP_DECODE_CHUNK", 0));
@@ -638,18 +621,86 @@ static int64_t decode_swa_cap(int64_t max_len, int64_t local_window, int64_t glo
   return span < max_len ? span : max_len;
 }
 
-// The matrix-core kernel (paged_decode_mfma.h): pages of a multiple of 16 tokens, head_dim 64 / 128, groups of <= 16 heads.
+// The matrix-core kernel (paged_decode_mfma.h): power-of-two pages of >= 16 tokens, head_dim 64 / 128, groups of <= 16 heads.
 // MOJO_HIP_DECODE_MFMA: unset = where it measured faster (B 64, ctx 4096, page 16, graph replay, vector-unit -> matrix-core):
 // groups of 8 heads (Llama-3-70B 64 / 8: 356 -> 170 us; 8 / 1: 79 -> 39 us), head_dim 64 (149 -> 99 us), groups of 4 at
 // head_dim 128 (headline 179 -> 169 us, ctx 1024 51 -> 47 us, ragged 150 -> 139 us; B 8: 34.5 -> 32.6 us with the chunk rule
 // of decode_chunk_tokens), and the group sizes the vector-unit kernel has no instance for.  Groups of 1 and 2 heads at head_dim 128
 // stay on the vector-unit kernel (163 vs 168 us, 167 vs 169 us).  1 = wherever it applies, 0 = never.
-static bool decode_use_mfma(const DecodeArgs& a, int G) {
-  if (a.page_shift < 4 || (a.dim != 64 && a.dim != 128) || G > 16) return false;
+static bool decode_use_mfma(int64_t G, int64_t head_dim, int64_t page) {
+  const bool pow2 = page > 0 && (page & (page - 1)) == 0;
+  if (!pow2 || page < 16 || (head_dim != 64 && head_dim != 128) || G > 16) return false;
   const long long e = MOJO_SWITCH("MOJO_HIP_DECODE_MFMA", -1);
   if (e == 0) return false;
   if (e == 1) return true;
-  return G >= 4 || a.dim == 64 || (G != 1 && G != 2);
+  return G >= 4 || head_dim == 64 || (G != 1 && G != 2);
+}
+
+// What a decode launch is sized on: the shapes alone (no pointers), so the workspace queries and the launchers plan alike.
+// A window makes the op the SWA one; none (local < 0 and global <= 0) leaves the GQA op, whichever entry point was called.
+struct DecodeGeom {
+  int64_t batch = 0, q_heads = 0, kv_heads = 0, head_dim = 0, page = 0, max_pages = 0, len_hint = 0;
+  int64_t local_window = -1, global_window = 0;
+  bool kv8 = false;                 // the int8-cache op (paged_decode_kv8.h): its own kernel, never grouped, halved or windowed
+};
+
+struct DecodePlan {
+  bool swa = false;                 // the windowed instances run
+  bool mfma = false;                // the 16-bit matrix-core kernel runs (decode_use_mfma)
+  int64_t capacity = 0;             // tokens of a row the launch can address: the hint, or page * table width
+  int64_t max_len = 0;              // tokens of a row the launch walks: the capacity, or what a window leaves visible of it
+  int chunk_tokens = 0, n_chunks = 0, fuse_group = 0;   // (DecodeArgs)
+  int hshift = 0, grid_kv_heads = 0, G = 0;             // kv heads the grid sees (= kv_heads << hshift) and query heads per grid kv head
+  int64_t slots = 0;                // partials the launch may write: batch * grid_kv_heads * n_chunks * G
+  int64_t bytes = 0;                // workspace the launch needs
+  int64_t query_bytes = 0;          // what the workspace query answers (0: degenerate geometry)
+};
+
+static DecodePlan decode_plan(const DecodeGeom& g) {
+  DecodePlan p;
+  p.swa = !g.kv8 && (g.local_window >= 0 || g.global_window > 0);
+  if (g.batch <= 0 || g.kv_heads <= 0 || g.q_heads <= 0) return p;
+  p.capacity = decode_max_len(g.page, g.max_pages, g.len_hint);
+  p.max_len = p.swa ? decode_swa_cap(p.capacity, g.local_window, g.global_window) : p.capacity;
+  const int64_t heads = g.q_heads / g.kv_heads;
+  // One form of the launch: the heads of a kv head together (hshift 0) or as two halves on twice the grid heads (hshift 1).
+  auto form = [&](int hshift, DecodePlan& f) {
+    f.hshift = hshift;
+    f.grid_kv_heads = static_cast<int>(g.kv_heads << hshift);
+    f.G = static_cast<int>(heads >> hshift);
+    f.mfma = !g.kv8 && decode_use_mfma(f.G, g.head_dim, g.page);
+    // The grouped form (DecodeArgs::fuse_group; matrix-core kernel only) — MOJO_HIP_DECODE_GROUPED=0 restores the split + merge form.
+    // Measured (scripts/probes/decode_grouped_ab.py, profiles/r4_decode_grouped_ab.txt; split + merge form -> grouped form, graph
+    // replay): 8 q / 1 kv heads B 64 ctx 4096 (Llama-3-70B under TP 8) 33.6 -> 28.1 us, B 16 ctx 16384 38.2 -> 29.8 us; 32 / 8 heads
+    // B 8 ctx 4096 31.3 -> 27.5 us; 64 / 8 heads B 8 ctx 8192 56.1 -> 49.8 us; head_dim 64 B 8 ctx 8192 33.7 -> 28.6 us.
+    // (the grouped launch exists in the fused form only: without MOJO_HIP_DECODE_FUSE the chunks are sized, written and merged
+    // one by one — ADVICE r4: the merge kernel divided the chunk count by the group size although every chunk had its partial)
+    const bool grouped = f.mfma && MOJO_SWITCH("MOJO_HIP_DECODE_GROUPED", 1) != 0 && MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) != 0;
+    f.chunk_tokens = decode_chunk_tokens(g.batch, f.grid_kv_heads, p.max_len, grouped);
+    f.n_chunks = static_cast<int>(ceil_div(p.max_len > 0 ? p.max_len : 1, f.chunk_tokens));
+    f.fuse_group = grouped && f.n_chunks > 8 ? 8 : 0;    // (the merge divides by it: set only where the grouped launch is taken)
+    f.slots = g.batch * g.kv_heads * f.n_chunks * heads;
+  };
+  // Groups of 8 query heads per kv head (Llama-3-70B: 64 / 8).  Round 2 ran them as two 4-head halves on twice as many grid
+  // heads (twice the K/V bytes: 360 us at B 64, ctx 4096) because the 8-head instance spilled; the instance now walks its heads
+  // in blocks of four over a two-tile ring with the query slices parked in LDS (232 registers, no spill) and reads K/V once.
+  // MOJO_HIP_DECODE_G8_HALVES=1 selects the halves again (A/B; experiments build only).
+  const bool can_halve = !p.swa && !g.kv8 && heads == 8;
+  int hshift = 0;
+#ifdef MOJO_HIP_BUILD_EXPERIMENTS
+  if (can_halve && MOJO_SWITCH("MOJO_HIP_DECODE_G8_HALVES", 0) == 1) hshift = 1;
+#endif
+  form(hshift, p);
+  const int64_t slot_bytes = (g.head_dim + 2) * static_cast<int64_t>(sizeof(float));
+  p.bytes = p.slots * slot_bytes;
+  int64_t most = p.slots;               // the query sizes for whichever of the two forms cuts the sequences finer
+  if (can_halve) {
+    DecodePlan other;
+    form(1 - hshift, other);
+    if (other.slots > most) most = other.slots;
+  }
+  p.query_bytes = most * slot_bytes + 256;
+  return p;
 }
 
 template <typename T, bool NT, int MODE, bool SWA>
@@ -666,12 +717,14 @@ static void launch_decode_mfma(const DecodeArgs& a, dim3 grid, dim3 block, int G
 }
 
 template <typename T, bool NT, bool SWA>
-static int launch_decode_nt(DecodeArgs& a, int64_t batch, int G, hipStream_t s) {
+static int launch_decode_nt(const DecodeArgs& a, const DecodePlan& p, hipStream_t s) {
+  const int64_t batch = a.batch;
+  const int G = p.G;
   const bool no_fuse = MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) == 0;
   const bool no_pair = MOJO_SWITCH("MOJO_HIP_DECODE_PAIR", 1) == 0;
   const char* nt_tag = NT ? "nt" : "cached";
   const char* swa_tag = SWA ? ":swa" : "";             // (the windowed instances: never the paired form)
-  if (decode_use_mfma(a, G)) {
+  if (p.mfma) {
     if (!SWA && a.n_chunks == 4 && batch >= 2 && batch <= 64 && !no_fuse && !no_pair) {
       launch_decode_mfma<T, NT, DEC_PAIRED, false>(a, dim3(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv)), dim3(512), G, s);
       MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, paired)");
@@ -749,110 +802,100 @@ static int launch_decode_nt(DecodeArgs& a, int64_t batch, int G, hipStream_t s) 
 }
 
 template <typename T, bool SWA>
-static int launch_decode(DecodeArgs& a, int64_t batch, int G, hipStream_t s) {
+static int launch_decode(const DecodeArgs& a, const DecodePlan& p, hipStream_t s) {
   // K/V are read exactly once: non-temporal loads keep them from displacing the block tables and
   // partials in L2/MALL (measured on MI355X, B=64 ctx=4096: 204 -> 190 us).  MOJO_HIP_STREAM_NT=0 disables (the switch of every
   // streaming kernel, common.h stream_nt()).
   const bool nt = MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0;
-  return nt ? launch_decode_nt<T, true, SWA>(a, batch, G, s) : launch_decode_nt<T, false, SWA>(a, batch, G, s);
+  return nt ? launch_decode_nt<T, true, SWA>(a, p, s) : launch_decode_nt<T, false, SWA>(a, p, s);
 }
 
 }  // namespace mojo
 
 using namespace mojo;
 
-// The GQA and SWA entry points share one body: with SWA the launch is planned on the visible capacity (decode_swa_cap), the
-// windowed kernel instances run, and the paired and halved forms are not taken.
-static int64_t decode_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                                      int64_t max_blocks_per_seq, int64_t max_seq_len_hint, bool swa, int64_t local_window,
-                                      int64_t global_window) {
-  if (batch <= 0 || kv_heads <= 0 || q_heads <= 0) return 0;
-  int64_t max_len = decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint);
-  if (swa) max_len = decode_swa_cap(max_len, local_window, global_window);
-  // (groups of 8 query heads can run as two 4-head halves on twice the grid heads — MOJO_HIP_DECODE_G8_HALVES=1 —: size for
-  // whichever form cuts the sequences finer)
-  int64_t slots = 0;
-  for (int64_t mult = 1; mult <= (!swa && q_heads / kv_heads == 8 ? 2 : 1); ++mult) {
-    const int chunk = decode_chunk_tokens(batch, kv_heads * mult, max_len, decode_grouped(q_heads / (kv_heads * mult), head_dim, block_size));
-    const int64_t n_chunks = ceil_div(max_len > 0 ? max_len : 1, chunk);
-    const int64_t sl = batch * kv_heads * n_chunks * (q_heads / kv_heads);
-    if (sl > slots) slots = sl;
-  }
-  return slots * (head_dim + 2) * static_cast<int64_t>(sizeof(float)) + 256;
+// The C arguments the decode entry points share, named: an entry point fills it, the bodies read it.
+struct DecodeCall {
+  const void *query = nullptr, *key_cache = nullptr, *value_cache = nullptr;
+  const int32_t *total_seq_lens = nullptr, *block_tables = nullptr;
+  void *out = nullptr, *workspace = nullptr;
+  DecodeGeom g;
+  int64_t workspace_bytes = 0, block_table_stride = 0, cache_block_stride = 0, cache_head_stride = 0, cache_token_stride = 0;
+  float softmax_scale = 0.f;
+  int layout_abab = 0, leave_empty_rows = 0, dtype = 0;
+  mojo_stream_t stream = nullptr;
+};
+
+// The kernel arguments of a planned call, its workspace bound (`op`: the entry point's name in the messages).
+static int decode_fill_args(DecodeArgs& a, const DecodeCall& c, const DecodePlan& p, const char* op) {
+  const DecodeGeom& g = c.g;
+  a.q = c.query; a.kc = c.key_cache; a.vc = c.value_cache; a.seq_lens = c.total_seq_lens; a.tables = c.block_tables; a.out = c.out;
+  a.hq = static_cast<int>(g.q_heads); a.hkv = p.grid_kv_heads; a.hshift = p.hshift; a.dim = static_cast<int>(g.head_dim);
+  a.page = static_cast<int>(g.page); a.max_pages = static_cast<int>(g.max_pages); a.batch = static_cast<int>(g.batch);
+  a.page_shift = (g.page & (g.page - 1)) == 0 ? __builtin_ctzll(g.page) : -1;
+  a.table_stride = c.block_table_stride; a.c_blk = c.cache_block_stride; a.c_head = c.cache_head_stride; a.c_tok = c.cache_token_stride;
+  a.chunk_tokens = p.chunk_tokens; a.n_chunks = p.n_chunks; a.fuse_group = p.fuse_group;
+  a.scale_log2 = c.softmax_scale * 1.4426950408889634f; a.abab = c.layout_abab ? 1 : 0; a.leave_empty = c.leave_empty_rows ? 1 : 0;
+  MOJO_REQUIRE(c.workspace && c.workspace_bytes >= p.bytes, MOJO_EWORKSPACE, "%s: workspace %lld B < required %lld B", op,
+               (long long)c.workspace_bytes, (long long)p.bytes);
+  MOJO_REQUIRE(aligned_to(c.workspace, 16), MOJO_EINVAL, "%s: workspace must be 16-byte aligned", op);
+  a.ws_acc = static_cast<float*>(c.workspace);
+  a.ws_ml = a.ws_acc + p.slots * g.head_dim;
+  return MOJO_OK;
 }
 
+// The GQA and SWA entry points share one body: with SWA the launch is planned on the visible capacity (decode_swa_cap), the
+// windowed kernel instances run, and the paired and halved forms are not taken.
 template <bool SWA>
-static int paged_decode(const void* query, const void* key_cache, const void* value_cache, const int32_t* total_seq_lens,
-                        const int32_t* block_tables, void* out, void* workspace, int64_t workspace_bytes, int64_t batch,
-                        int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size, int64_t max_blocks_per_seq,
-                        int64_t block_table_stride, int64_t cache_block_stride, int64_t cache_head_stride,
-                        int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale, int layout_abab,
-                        int leave_empty_rows, int dtype, int64_t local_window, int64_t global_window, mojo_stream_t stream) {
-  if (batch == 0) return MOJO_OK;
-  MOJO_REQUIRE(query && key_cache && value_cache && total_seq_lens && block_tables && out, MOJO_EINVAL,
+static int paged_decode_planned(const DecodeCall& c, const DecodePlan& p) {
+  const DecodeGeom& g = c.g;
+  MOJO_REQUIRE(c.query && c.key_cache && c.value_cache && c.total_seq_lens && c.block_tables && c.out, MOJO_EINVAL,
                "paged_decode_gqa: null pointer");
-  MOJO_REQUIRE(batch > 0 && q_heads > 0 && kv_heads > 0 && q_heads % kv_heads == 0, MOJO_EINVAL,
-               "paged_decode_gqa: bad head counts Hq=%lld Hkv=%lld", (long long)q_heads, (long long)kv_heads);
-  MOJO_REQUIRE(dtype == MOJO_BF16 || dtype == MOJO_F16, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa: dtype %d (bf16/fp16 only)", dtype);
-  MOJO_REQUIRE(head_dim % 8 == 0 && head_dim >= 8 && head_dim <= 8 * DEC_LPT, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa: head_dim %lld (multiple of 8, <= %d)", (long long)head_dim, 8 * DEC_LPT);
-  MOJO_REQUIRE(block_size % DEC_TPL == 0, MOJO_EUNSUPPORTED, "paged_decode_gqa: block_size %lld must be a multiple of %d",
-               (long long)block_size, DEC_TPL);
-  MOJO_REQUIRE(cache_token_stride % 8 == 0 && cache_head_stride % 8 == 0 && cache_block_stride % 8 == 0 &&
-                   aligned_to(key_cache, 16) && aligned_to(value_cache, 16) && aligned_to(query, 16) &&
-                   aligned_to(out, 16),
+  MOJO_REQUIRE(g.batch > 0 && g.q_heads > 0 && g.kv_heads > 0 && g.q_heads % g.kv_heads == 0, MOJO_EINVAL,
+               "paged_decode_gqa: bad head counts Hq=%lld Hkv=%lld", (long long)g.q_heads, (long long)g.kv_heads);
+  MOJO_REQUIRE(c.dtype == MOJO_BF16 || c.dtype == MOJO_F16, MOJO_EUNSUPPORTED,
+               "paged_decode_gqa: dtype %d (bf16/fp16 only)", c.dtype);
+  MOJO_REQUIRE(g.head_dim % 8 == 0 && g.head_dim >= 8 && g.head_dim <= 8 * DEC_LPT, MOJO_EUNSUPPORTED,
+               "paged_decode_gqa: head_dim %lld (multiple of 8, <= %d)", (long long)g.head_dim, 8 * DEC_LPT);
+  MOJO_REQUIRE(g.page % DEC_TPL == 0, MOJO_EUNSUPPORTED, "paged_decode_gqa: block_size %lld must be a multiple of %d",
+               (long long)g.page, DEC_TPL);
+  MOJO_REQUIRE(c.cache_token_stride % 8 == 0 && c.cache_head_stride % 8 == 0 && c.cache_block_stride % 8 == 0 &&
+                   aligned_to(c.key_cache, 16) && aligned_to(c.value_cache, 16) && aligned_to(c.query, 16) &&
+                   aligned_to(c.out, 16),
                MOJO_EUNSUPPORTED, "paged_decode_gqa: tensors must be 16-byte aligned with 16-byte row strides");
-  MOJO_REQUIRE(max_blocks_per_seq >= 0 && batch * kv_heads * 2 <= 65535, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa: batch*kv_heads %lld exceeds the grid limit", (long long)(batch * kv_heads));
-
+  MOJO_REQUIRE(g.max_pages >= 0 && g.batch * g.kv_heads * 2 <= 65535, MOJO_EUNSUPPORTED,
+               "paged_decode_gqa: batch*kv_heads %lld exceeds the grid limit", (long long)(g.batch * g.kv_heads));
   DecodeArgs a;
-  a.q = query; a.kc = key_cache; a.vc = value_cache; a.seq_lens = total_seq_lens; a.tables = block_tables; a.out = out;
-  a.hq = static_cast<int>(q_heads); a.hkv = static_cast<int>(kv_heads); a.dim = static_cast<int>(head_dim);
-  a.page = static_cast<int>(block_size); a.max_pages = static_cast<int>(max_blocks_per_seq); a.batch = static_cast<int>(batch);
-  a.page_shift = (block_size & (block_size - 1)) == 0 ? __builtin_ctzll(block_size) : -1;
-  a.table_stride = block_table_stride; a.c_blk = cache_block_stride; a.c_head = cache_head_stride;
-  a.c_tok = cache_token_stride;
-  int64_t max_len = decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint);
   if constexpr (SWA) {
-    MOJO_REQUIRE(max_len < (int64_t{1} << 30) && local_window < (int64_t{1} << 30) && global_window < (int64_t{1} << 30),
+    MOJO_REQUIRE(p.capacity < (int64_t{1} << 30) && g.local_window < (int64_t{1} << 30) && g.global_window < (int64_t{1} << 30),
                  MOJO_EUNSUPPORTED, "paged_decode_swa: lengths and windows must stay below 2^30");
-    a.swa_cap = static_cast<int>(max_len);
-    a.local_win = local_window >= 0 ? static_cast<int>(local_window) : -1;
-    a.global_win = global_window > 0 ? static_cast<int>(global_window) : 0;
-    max_len = decode_swa_cap(max_len, local_window, global_window);
+    a.swa_cap = static_cast<int>(p.capacity);
+    a.local_win = g.local_window >= 0 ? static_cast<int>(g.local_window) : -1;
+    a.global_win = g.global_window > 0 ? static_cast<int>(g.global_window) : 0;
   }
-  // Groups of 8 query heads per kv head (Llama-3-70B: 64 / 8).  Round 2 ran them as two 4-head halves on twice as many grid
-  // heads (twice the K/V bytes: 360 us at B 64, ctx 4096) because the 8-head instance spilled; the instance now walks its heads
-  // in blocks of four over a two-tile ring with the query slices parked in LDS (232 registers, no spill) and reads K/V once.
-  // MOJO_HIP_DECODE_G8_HALVES=1 selects the halves again (A/B; experiments build only).
-  int G = static_cast<int>(q_heads / kv_heads);
-  a.hshift = 0;
-#ifdef MOJO_HIP_BUILD_EXPERIMENTS
-  if (!SWA && G == 8 && MOJO_SWITCH("MOJO_HIP_DECODE_G8_HALVES", 0) == 1) { a.hshift = 1; a.hkv *= 2; G = 4; }
-#endif
-  const bool grouped = decode_grouped(G, head_dim, block_size);
-  a.chunk_tokens = decode_chunk_tokens(batch, a.hkv, max_len, grouped);
-  a.n_chunks = static_cast<int>(ceil_div(max_len > 0 ? max_len : 1, a.chunk_tokens));
-  a.fuse_group = grouped && decode_use_mfma(a, G) && a.n_chunks > 8 ? 8 : 0;   // (the merge divides by it: set only where the grouped launch is taken)
-  a.scale_log2 = softmax_scale * 1.4426950408889634f;
-  a.abab = layout_abab ? 1 : 0;
-  a.leave_empty = leave_empty_rows ? 1 : 0;
-  const int64_t slots = static_cast<int64_t>(batch) * a.hkv * a.n_chunks * G;
-  const int64_t need = slots * (head_dim + 2) * static_cast<int64_t>(sizeof(float));
-  MOJO_REQUIRE(workspace && workspace_bytes >= need, MOJO_EWORKSPACE,
-               "paged_decode_gqa: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-  MOJO_REQUIRE(aligned_to(workspace, 16), MOJO_EINVAL, "paged_decode_gqa: workspace must be 16-byte aligned");
-  a.ws_acc = static_cast<float*>(workspace);
-  a.ws_ml = a.ws_acc + slots * head_dim;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return dtype == MOJO_BF16 ? launch_decode<bf16_t, SWA>(a, batch, G, s) : launch_decode<f16_t, SWA>(a, batch, G, s);
+  if (const int rc = decode_fill_args(a, c, p, "paged_decode_gqa"); rc != MOJO_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(c.stream);
+  return c.dtype == MOJO_BF16 ? launch_decode<bf16_t, SWA>(a, p, s) : launch_decode<f16_t, SWA>(a, p, s);
+}
+
+static int paged_decode(const DecodeCall& c) {
+  if (c.g.batch == 0) return MOJO_OK;
+  const DecodePlan p = decode_plan(c.g);                 // (p.swa: a call without a window is the GQA op itself)
+  return !p.swa ? paged_decode_planned<false>(c, p) : paged_decode_planned<true>(c, p);
 }
 
 extern "C" int64_t mojo_hip_paged_decode_gqa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
                                                              int64_t head_dim, int64_t block_size,
                                                              int64_t max_blocks_per_seq, int64_t max_seq_len_hint) {
-  return decode_workspace_bytes(batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, false, -1, 0);
+  return decode_plan({batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint}).query_bytes;
+}
+
+extern "C" int64_t mojo_hip_paged_decode_swa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                             int64_t head_dim, int64_t block_size,
+                                                             int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                             int64_t local_window, int64_t global_window) {
+  return decode_plan({batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window,
+                      global_window}).query_bytes;
 }
 
 extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cache, const void* value_cache,
@@ -863,19 +906,14 @@ extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cach
                                          int64_t cache_block_stride, int64_t cache_head_stride,
                                          int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
                                          int layout_abab, int leave_empty_rows, int dtype, mojo_stream_t stream) {
-  return paged_decode<false>(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes,
-                             batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
-                             cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
-                             layout_abab, leave_empty_rows, dtype, -1, 0, stream);
-}
-
-extern "C" int64_t mojo_hip_paged_decode_swa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
-                                                             int64_t head_dim, int64_t block_size,
-                                                             int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
-                                                             int64_t local_window, int64_t global_window) {
-  const bool swa = local_window >= 0 || global_window > 0;
-  return decode_workspace_bytes(batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, swa,
-                                local_window, global_window);
+  DecodeCall c;
+  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
+  c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint};
+  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
+  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
+  c.leave_empty_rows = leave_empty_rows; c.dtype = dtype;
+  return paged_decode(c);
 }
 
 extern "C" int mojo_hip_paged_decode_swa(const void* query, const void* key_cache, const void* value_cache,
@@ -887,15 +925,14 @@ extern "C" int mojo_hip_paged_decode_swa(const void* query, const void* key_cach
                                          int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
                                          int layout_abab, int leave_empty_rows, int dtype, int64_t local_window,
                                          int64_t global_window, mojo_stream_t stream) {
-  if (local_window < 0 && global_window <= 0)            // no window: the GQA op itself
-    return paged_decode<false>(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes,
-                               batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
-                               cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
-                               layout_abab, leave_empty_rows, dtype, -1, 0, stream);
-  return paged_decode<true>(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes,
-                            batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
-                            cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
-                            layout_abab, leave_empty_rows, dtype, local_window, global_window, stream);
+  DecodeCall c;
+  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
+  c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window, global_window};
+  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
+  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
+  c.leave_empty_rows = leave_empty_rows; c.dtype = dtype;
+  return paged_decode(c);
 }
 
 #include "paged_decode_kv8.h"

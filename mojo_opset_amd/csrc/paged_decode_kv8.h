@@ -388,20 +388,12 @@ static int launch_decode_kv8(const Kv8Args& ka, int64_t batch, int G, hipStream_
   return MOJO_OK;
 }
 
-static int64_t decode_kv8_chunks(int64_t batch, int64_t kv_heads, int64_t max_len, int& chunk_tokens) {
-  chunk_tokens = decode_chunk_tokens(batch, kv_heads, max_len, false);
-  return ceil_div(max_len > 0 ? max_len : 1, chunk_tokens);
-}
-
 }  // namespace mojo
 
 extern "C" int64_t mojo_hip_paged_decode_gqa_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
                                                                  int64_t head_dim, int64_t block_size,
                                                                  int64_t max_blocks_per_seq, int64_t max_seq_len_hint) {
-  if (batch <= 0 || kv_heads <= 0 || q_heads <= 0) return 0;
-  int chunk;
-  const int64_t n_chunks = mojo::decode_kv8_chunks(batch, kv_heads, mojo::decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint), chunk);
-  return batch * kv_heads * n_chunks * (q_heads / kv_heads) * (head_dim + 2) * static_cast<int64_t>(sizeof(float)) + 256;
+  return mojo::decode_plan({batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, -1, 0, /*kv8=*/true}).query_bytes;
 }
 
 extern "C" int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
@@ -435,28 +427,17 @@ extern "C" int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_
                MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: tensors must be 16-byte aligned with 16-byte row strides");
   MOJO_REQUIRE(max_blocks_per_seq >= 0 && batch * kv_heads <= 65535, MOJO_EUNSUPPORTED,
                "paged_decode_gqa_kv8: batch*kv_heads %lld exceeds the grid limit", (long long)(batch * kv_heads));
+  DecodeCall c;
+  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
+  c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, -1, 0, /*kv8=*/true};
+  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
+  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
+  c.leave_empty_rows = leave_empty_rows;
+  const DecodePlan p = decode_plan(c.g);
   Kv8Args ka{};
-  DecodeArgs& a = ka.a;
-  a.q = query; a.kc = key_cache; a.vc = value_cache; a.seq_lens = total_seq_lens; a.tables = block_tables; a.out = out;
-  a.hq = static_cast<int>(q_heads); a.hkv = static_cast<int>(kv_heads); a.dim = static_cast<int>(head_dim);
-  a.page = static_cast<int>(block_size); a.max_pages = static_cast<int>(max_blocks_per_seq); a.batch = static_cast<int>(batch);
-  a.page_shift = (block_size & (block_size - 1)) == 0 ? __builtin_ctzll(block_size) : -1;
-  a.table_stride = block_table_stride; a.c_blk = cache_block_stride; a.c_head = cache_head_stride; a.c_tok = cache_token_stride;
-  a.hshift = 0;
-  const int G = static_cast<int>(q_heads / kv_heads);
-  a.n_chunks = static_cast<int>(decode_kv8_chunks(batch, kv_heads, decode_max_len(block_size, max_blocks_per_seq, max_seq_len_hint), a.chunk_tokens));
-  a.fuse_group = 0;
-  a.scale_log2 = softmax_scale * 1.4426950408889634f;
-  a.abab = layout_abab ? 1 : 0;
-  a.leave_empty = leave_empty_rows ? 1 : 0;
-  const int64_t slots = batch * kv_heads * a.n_chunks * G;
-  const int64_t need = slots * (head_dim + 2) * static_cast<int64_t>(sizeof(float));
-  MOJO_REQUIRE(workspace && workspace_bytes >= need, MOJO_EWORKSPACE,
-               "paged_decode_gqa_kv8: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-  MOJO_REQUIRE(aligned_to(workspace, 16), MOJO_EINVAL, "paged_decode_gqa_kv8: workspace must be 16-byte aligned");
-  a.ws_acc = static_cast<float*>(workspace);
-  a.ws_ml = a.ws_acc + slots * head_dim;
+  if (const int rc = decode_fill_args(ka.a, c, p, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
   ka.kscale = key_scale; ka.vscale = value_scale; ka.scale_dtype = scale_dtype; ka.q_bf16 = dtype == MOJO_BF16 ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0 ? launch_decode_kv8<true>(ka, batch, G, s) : launch_decode_kv8<false>(ka, batch, G, s);
+  return MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0 ? launch_decode_kv8<true>(ka, batch, p.G, s) : launch_decode_kv8<false>(ka, batch, p.G, s);
 }

@@ -1057,112 +1057,131 @@ static int prefill_ksplit(int64_t blocks, int64_t kv_cap) {
   return ks < 2 ? 1 : static_cast<int>(ks);
 }
 
-static void prefill_plan(int64_t total_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t block_size,
-                         int64_t max_blocks_per_seq, int64_t max_q_len_hint, int64_t max_kv_len_hint, int64_t& n_qb, int& ksplit,
-                         int64_t local_window = -1, int64_t global_window = 0) {
-  const int G = static_cast<int>(q_heads / kv_heads);
-  const int64_t max_q = (max_q_len_hint > 0 && max_q_len_hint < total_tokens) ? max_q_len_hint : total_tokens;
-  n_qb = ceil_div(max_q, 128 / (G > 0 ? G : 1));
-  int64_t kv_cap = block_size * max_blocks_per_seq;
-  if (max_kv_len_hint > 0 && max_kv_len_hint < kv_cap) kv_cap = max_kv_len_hint;
-  if (local_window >= 0 || global_window > 0) {          // sliding window: the keys one block can see, not the table's capacity
-    int64_t span = global_window > 0 ? global_window : 0;
-    if (local_window >= 0) span += local_window + 128 / (G > 0 ? G : 1);
+// What a prefill launch is sized on: the shapes alone.  A window (local >= 0 or global > 0) makes the op the SWA one.
+struct PrefillGeom {
+  int64_t total_tokens = 0, batch = 0, q_heads = 0, kv_heads = 0, head_dim = 0, page = 0, max_pages = 0;
+  int64_t max_q_hint = 0, max_kv_hint = 0, local_window = -1, global_window = 0;
+};
+
+struct PrefillPlan {
+  bool swa = false;
+  int64_t max_q = 0, n_qb = 0;      // longest query run the launch covers, and its 128-row blocks per (sequence, kv head)
+  int ksplit = 1;
+  int64_t rows = 0, bytes = 0;      // key split: the partial rows and the workspace they take (0 unsplit)
+  int64_t query_bytes = 0;          // what the workspace query answers
+};
+
+static PrefillPlan prefill_plan(const PrefillGeom& g) {
+  PrefillPlan p;
+  p.swa = g.local_window >= 0 || g.global_window > 0;
+  if (g.total_tokens <= 0 || g.batch <= 0 || g.q_heads <= 0 || g.kv_heads <= 0 || g.q_heads % g.kv_heads) return p;
+  const int G = static_cast<int>(g.q_heads / g.kv_heads);
+  p.max_q = (g.max_q_hint > 0 && g.max_q_hint < g.total_tokens) ? g.max_q_hint : g.total_tokens;
+  p.n_qb = ceil_div(p.max_q, 128 / G);
+  int64_t kv_cap = g.page * g.max_pages;
+  if (g.max_kv_hint > 0 && g.max_kv_hint < kv_cap) kv_cap = g.max_kv_hint;
+  if (p.swa) {                                           // sliding window: the keys one block can see, not the table's capacity
+    int64_t span = g.global_window > 0 ? g.global_window : 0;
+    if (g.local_window >= 0) span += g.local_window + 128 / G;
     if (span < kv_cap) kv_cap = span;
   }
-  ksplit = prefill_ksplit(n_qb * kv_heads * batch, kv_cap);
+  p.ksplit = prefill_ksplit(p.n_qb * g.kv_heads * g.batch, kv_cap);
+  if (p.ksplit > 1) {
+    p.rows = p.n_qb * g.kv_heads * g.batch * p.ksplit * 128;
+    p.bytes = p.rows * (g.head_dim + 2) * static_cast<int64_t>(sizeof(float));
+    p.query_bytes = p.bytes + 64;
+  }
+  return p;
 }
+
+// The C arguments of a prefill entry point, named: the entry points fill it, the shared body reads it.
+struct PrefillCall {
+  const void *query = nullptr, *key_cache = nullptr, *value_cache = nullptr;
+  const int32_t *cu_q_lens = nullptr, *cu_total_seq_lens = nullptr, *block_tables = nullptr;
+  void *out = nullptr, *workspace = nullptr;
+  PrefillGeom g;
+  int64_t workspace_bytes = 0, block_table_stride = 0, cache_block_stride = 0, cache_head_stride = 0, cache_token_stride = 0;
+  float softmax_scale = 0.f;
+  int layout_abab = 0, dtype = 0;
+  mojo_stream_t stream = nullptr;
+};
 
 }  // namespace mojo
 
 using namespace mojo;
 
-static int64_t prefill_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
-                                       int64_t block_size, int64_t max_blocks_per_seq, int64_t max_q_len_hint,
-                                       int64_t max_kv_len_hint, int64_t local_window, int64_t global_window) {
-  if (total_tokens <= 0 || batch <= 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return 0;
-  int64_t n_qb;
-  int ks;
-  prefill_plan(total_tokens, batch, q_heads, kv_heads, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint, n_qb, ks,
-               local_window, global_window);
-  if (ks <= 1) return 0;
-  return n_qb * kv_heads * batch * ks * 128 * (head_dim + 2) * static_cast<int64_t>(sizeof(float)) + 64;
-}
-
 // The GQA and SWA entry points share one body (SWA: the windowed kernel instances, key split sized on the visible keys).
 template <bool SWA>
-static int paged_prefill(const void* query, const void* key_cache, const void* value_cache, const int32_t* cu_q_lens,
-                         const int32_t* cu_total_seq_lens, const int32_t* block_tables, void* out, int64_t total_tokens,
-                         int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                         int64_t max_blocks_per_seq, int64_t block_table_stride, int64_t cache_block_stride,
-                         int64_t cache_head_stride, int64_t cache_token_stride, int64_t max_q_len_hint,
-                         int64_t max_kv_len_hint, float softmax_scale, int layout_abab, int dtype, void* workspace,
-                         int64_t workspace_bytes, int64_t local_window, int64_t global_window, mojo_stream_t stream) {
-  if (total_tokens == 0) return MOJO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  MOJO_REQUIRE(query && key_cache && value_cache && cu_q_lens && block_tables && out, MOJO_EINVAL,
+static int paged_prefill_planned(const PrefillCall& c, const PrefillPlan& p) {
+  const PrefillGeom& g = c.g;
+  hipStream_t s = static_cast<hipStream_t>(c.stream);
+  MOJO_REQUIRE(c.query && c.key_cache && c.value_cache && c.cu_q_lens && c.block_tables && c.out, MOJO_EINVAL,
                "paged_prefill_gqa: null pointer");
-  MOJO_REQUIRE(q_heads > 0 && kv_heads > 0 && q_heads % kv_heads == 0 && batch >= 0, MOJO_EINVAL,
-               "paged_prefill_gqa: bad head counts Hq=%lld Hkv=%lld", (long long)q_heads, (long long)kv_heads);
-  MOJO_REQUIRE(dtype == MOJO_BF16 || dtype == MOJO_F16, MOJO_EUNSUPPORTED, "paged_prefill_gqa: dtype %d (bf16/fp16 only)", dtype);
-  MOJO_REQUIRE(block_size % 4 == 0, MOJO_EUNSUPPORTED, "paged_prefill_gqa: block_size %lld must be a multiple of 4",
-               (long long)block_size);
-  MOJO_REQUIRE(cache_token_stride % 8 == 0 && cache_head_stride % 8 == 0 && cache_block_stride % 8 == 0 &&
-                   aligned_to(key_cache, 16) && aligned_to(value_cache, 16) && aligned_to(query, 16) && aligned_to(out, 16),
+  MOJO_REQUIRE(g.q_heads > 0 && g.kv_heads > 0 && g.q_heads % g.kv_heads == 0 && g.batch >= 0, MOJO_EINVAL,
+               "paged_prefill_gqa: bad head counts Hq=%lld Hkv=%lld", (long long)g.q_heads, (long long)g.kv_heads);
+  MOJO_REQUIRE(c.dtype == MOJO_BF16 || c.dtype == MOJO_F16, MOJO_EUNSUPPORTED, "paged_prefill_gqa: dtype %d (bf16/fp16 only)", c.dtype);
+  MOJO_REQUIRE(g.page % 4 == 0, MOJO_EUNSUPPORTED, "paged_prefill_gqa: block_size %lld must be a multiple of 4",
+               (long long)g.page);
+  MOJO_REQUIRE(c.cache_token_stride % 8 == 0 && c.cache_head_stride % 8 == 0 && c.cache_block_stride % 8 == 0 &&
+                   aligned_to(c.key_cache, 16) && aligned_to(c.value_cache, 16) && aligned_to(c.query, 16) && aligned_to(c.out, 16),
                MOJO_EUNSUPPORTED, "paged_prefill_gqa: tensors must be 16-byte aligned with 16-byte row strides");
-  if (batch == 0) {                                      // no sequences: every row is padding
-    if (hipMemsetAsync(out, 0, static_cast<size_t>(total_tokens * q_heads * head_dim * 2), s) != hipSuccess) {
+  if (g.batch == 0) {                                    // no sequences: every row is padding
+    if (hipMemsetAsync(c.out, 0, static_cast<size_t>(g.total_tokens * g.q_heads * g.head_dim * 2), s) != hipSuccess) {
       set_error("paged_prefill_gqa: memset failed");
       return MOJO_ELAUNCH;
     }
     return MOJO_OK;
   }
   PrefillArgs a;
-  a.q = query; a.kc = key_cache; a.vc = value_cache; a.out = out; a.cu_q = cu_q_lens; a.cu_kv = cu_total_seq_lens;
-  a.total_tokens = total_tokens;
-  a.tables = block_tables; a.table_stride = block_table_stride; a.c_blk = cache_block_stride;
-  a.c_head = cache_head_stride; a.c_tok = cache_token_stride;
-  a.hq = static_cast<int>(q_heads); a.hkv = static_cast<int>(kv_heads); a.dim = static_cast<int>(head_dim);
-  a.page = static_cast<int>(block_size);
-  a.page_shift = (block_size & (block_size - 1)) == 0 ? __builtin_ctzll(block_size) : -1;
-  a.max_pages = static_cast<int>(max_blocks_per_seq);
-  a.scale_log2 = softmax_scale * 1.4426950408889634f;
-  a.abab = layout_abab ? 1 : 0;
+  a.q = c.query; a.kc = c.key_cache; a.vc = c.value_cache; a.out = c.out; a.cu_q = c.cu_q_lens; a.cu_kv = c.cu_total_seq_lens;
+  a.total_tokens = g.total_tokens;
+  a.tables = c.block_tables; a.table_stride = c.block_table_stride; a.c_blk = c.cache_block_stride;
+  a.c_head = c.cache_head_stride; a.c_tok = c.cache_token_stride;
+  a.hq = static_cast<int>(g.q_heads); a.hkv = static_cast<int>(g.kv_heads); a.dim = static_cast<int>(g.head_dim);
+  a.page = static_cast<int>(g.page);
+  a.page_shift = (g.page & (g.page - 1)) == 0 ? __builtin_ctzll(g.page) : -1;
+  a.max_pages = static_cast<int>(g.max_pages);
+  a.scale_log2 = c.softmax_scale * 1.4426950408889634f;
+  a.abab = c.layout_abab ? 1 : 0;
   if constexpr (SWA) {
-    MOJO_REQUIRE(local_window < (int64_t{1} << 29) && global_window < (int64_t{1} << 29) &&
-                     block_size * max_blocks_per_seq < (int64_t{1} << 29),
+    MOJO_REQUIRE(g.local_window < (int64_t{1} << 29) && g.global_window < (int64_t{1} << 29) &&
+                     g.page * g.max_pages < (int64_t{1} << 29),
                  MOJO_EUNSUPPORTED, "paged_prefill_swa: lengths and windows must stay below 2^29");
-    a.local_win = local_window >= 0 ? static_cast<int>(local_window) : -(1 << 30);
-    a.global_win = global_window > 0 ? static_cast<int>(global_window) : 0;
-  } else {
-    local_window = -1;
-    global_window = 0;
+    a.local_win = g.local_window >= 0 ? static_cast<int>(g.local_window) : -(1 << 30);
+    a.global_win = g.global_window > 0 ? static_cast<int>(g.global_window) : 0;
   }
   const bool no_fs = MOJO_SWITCH("MOJO_HIP_PREFILL_FAST_STAGE", 1) == 0;        // 0: general staging everywhere (tests)
-  a.fast_stage = (a.page_shift >= 4 && cache_token_stride * 16 * 2 + 256 < (int64_t{1} << 31) && !no_fs) ? 1 : 0;
-  int64_t max_q = (max_q_len_hint > 0 && max_q_len_hint < total_tokens) ? max_q_len_hint : total_tokens;
-  const int G = static_cast<int>(q_heads / kv_heads);
-  {
-    int64_t n_qb;
-    int ks;
-    prefill_plan(total_tokens, batch, q_heads, kv_heads, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint, n_qb, ks,
-                 local_window, global_window);
-    const int64_t rows = n_qb * kv_heads * batch * ks * 128;
-    const int64_t need = rows * (head_dim + 2) * static_cast<int64_t>(sizeof(float));
-    if (ks > 1 && !(workspace && workspace_bytes >= need && aligned_to(workspace, 16))) ks = 1;   // no workspace: run unsplit
-    a.ksplit = ks;
-    a.ws_o = ks > 1 ? static_cast<float*>(workspace) : nullptr;
-    a.ws_ml = ks > 1 ? a.ws_o + rows * head_dim : nullptr;
-  }
-  return dtype == MOJO_BF16 ? dispatch_g<bf16_t, SWA>(a, G, batch, max_q, s) : dispatch_g<f16_t, SWA>(a, G, batch, max_q, s);
+  a.fast_stage = (a.page_shift >= 4 && c.cache_token_stride * 16 * 2 + 256 < (int64_t{1} << 31) && !no_fs) ? 1 : 0;
+  // no workspace (or one too small, or misaligned): run unsplit
+  const bool split = p.ksplit > 1 && c.workspace && c.workspace_bytes >= p.bytes && aligned_to(c.workspace, 16);
+  a.ksplit = split ? p.ksplit : 1;
+  a.ws_o = split ? static_cast<float*>(c.workspace) : nullptr;
+  a.ws_ml = split ? a.ws_o + p.rows * g.head_dim : nullptr;
+  const int G = static_cast<int>(g.q_heads / g.kv_heads);
+  return c.dtype == MOJO_BF16 ? dispatch_g<bf16_t, SWA>(a, G, g.batch, p.max_q, s) : dispatch_g<f16_t, SWA>(a, G, g.batch, p.max_q, s);
+}
+
+static int paged_prefill(const PrefillCall& c) {
+  if (c.g.total_tokens == 0) return MOJO_OK;
+  const PrefillPlan p = prefill_plan(c.g);               // (p.swa: a call without a window is the GQA op itself)
+  return !p.swa ? paged_prefill_planned<false>(c, p) : paged_prefill_planned<true>(c, p);
 }
 
 extern "C" int64_t mojo_hip_paged_prefill_gqa_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
                                                               int64_t kv_heads, int64_t head_dim, int64_t block_size,
                                                               int64_t max_blocks_per_seq, int64_t max_q_len_hint,
                                                               int64_t max_kv_len_hint) {
-  return prefill_workspace_bytes(total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
-                                 max_kv_len_hint, -1, 0);
+  return prefill_plan({total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
+                       max_kv_len_hint}).query_bytes;
+}
+
+extern "C" int64_t mojo_hip_paged_prefill_swa_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
+                                                              int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                                              int64_t max_blocks_per_seq, int64_t max_q_len_hint,
+                                                              int64_t max_kv_len_hint, int64_t local_window,
+                                                              int64_t global_window) {
+  return prefill_plan({total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
+                       max_kv_len_hint, local_window, global_window}).query_bytes;
 }
 
 extern "C" int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cache, const void* value_cache,
@@ -1174,19 +1193,13 @@ extern "C" int mojo_hip_paged_prefill_gqa(const void* query, const void* key_cac
                                           int64_t cache_token_stride, int64_t max_q_len_hint, int64_t max_kv_len_hint,
                                           float softmax_scale, int layout_abab, int dtype, void* workspace,
                                           int64_t workspace_bytes, mojo_stream_t stream) {
-  return paged_prefill<false>(query, key_cache, value_cache, cu_q_lens, cu_total_seq_lens, block_tables, out, total_tokens, batch,
-                              q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride, cache_block_stride,
-                              cache_head_stride, cache_token_stride, max_q_len_hint, max_kv_len_hint, softmax_scale, layout_abab,
-                              dtype, workspace, workspace_bytes, -1, 0, stream);
-}
-
-extern "C" int64_t mojo_hip_paged_prefill_swa_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
-                                                              int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                                                              int64_t max_blocks_per_seq, int64_t max_q_len_hint,
-                                                              int64_t max_kv_len_hint, int64_t local_window,
-                                                              int64_t global_window) {
-  return prefill_workspace_bytes(total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
-                                 max_kv_len_hint, local_window, global_window);
+  PrefillCall c;
+  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.cu_q_lens = cu_q_lens; c.cu_total_seq_lens = cu_total_seq_lens;
+  c.block_tables = block_tables; c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  c.g = {total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint};
+  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
+  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab; c.dtype = dtype;
+  return paged_prefill(c);
 }
 
 extern "C" int mojo_hip_paged_prefill_swa(const void* query, const void* key_cache, const void* value_cache,
@@ -1199,15 +1212,14 @@ extern "C" int mojo_hip_paged_prefill_swa(const void* query, const void* key_cac
                                           float softmax_scale, int layout_abab, int dtype, void* workspace,
                                           int64_t workspace_bytes, int64_t local_window, int64_t global_window,
                                           mojo_stream_t stream) {
-  if (local_window < 0 && global_window <= 0)            // no window: the GQA op itself
-    return paged_prefill<false>(query, key_cache, value_cache, cu_q_lens, cu_total_seq_lens, block_tables, out, total_tokens,
-                                batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
-                                cache_block_stride, cache_head_stride, cache_token_stride, max_q_len_hint, max_kv_len_hint,
-                                softmax_scale, layout_abab, dtype, workspace, workspace_bytes, -1, 0, stream);
-  return paged_prefill<true>(query, key_cache, value_cache, cu_q_lens, cu_total_seq_lens, block_tables, out, total_tokens, batch,
-                             q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride, cache_block_stride,
-                             cache_head_stride, cache_token_stride, max_q_len_hint, max_kv_len_hint, softmax_scale, layout_abab,
-                             dtype, workspace, workspace_bytes, local_window, global_window, stream);
+  PrefillCall c;
+  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.cu_q_lens = cu_q_lens; c.cu_total_seq_lens = cu_total_seq_lens;
+  c.block_tables = block_tables; c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  c.g = {total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint,
+         local_window, global_window};
+  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
+  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab; c.dtype = dtype;
+  return paged_prefill(c);
 }
 
 #if defined(PF_STAMPS) || defined(PF_WG_STAMPS)

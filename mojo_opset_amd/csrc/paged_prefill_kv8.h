@@ -1,5 +1,5 @@
 // MojoPagedPrefillGQAWithKVDequant — the simple route: a dequantising page gather, then the 16-bit prefill on its pages.
-// Included at the end of paged_prefill_gqa.hip (calls paged_prefill<false> of that file).
+// Included at the end of paged_prefill_gqa.hip (calls paged_prefill of that file).
 //
 // gather_kv8_kernel reads the int8 pages a sequence's block table names, multiplies by the per-channel scales
 // (K8 * key_scale, V8 * value_scale: fp32 products rounded to the query dtype) and writes compact 16-bit scratch pages:
@@ -74,22 +74,20 @@ __global__ __launch_bounds__(256) void gather_kv8_kernel(GatherKv8Args a) {
 
 struct PrefillKv8Plan { int64_t ppb, ws_inner, off_table, off_k, off_v, total; };
 
-static PrefillKv8Plan prefill_kv8_plan(int64_t total_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
-                                       int64_t block_size, int64_t max_blocks_per_seq, int64_t max_q_len_hint, int64_t max_kv_len_hint) {
+// `g`: the call's geometry over the int8 cache.  `inner`: the same over the scratch pages, what the 16-bit prefill is planned on.
+static PrefillKv8Plan prefill_kv8_plan(const PrefillGeom& g, PrefillGeom& inner) {
   PrefillKv8Plan p{};
-  int64_t cap = block_size * max_blocks_per_seq;
-  if (max_kv_len_hint > 0 && max_kv_len_hint < cap) cap = max_kv_len_hint;
-  p.ppb = block_size > 0 ? ceil_div(cap, block_size) : 0;
+  int64_t cap = g.page * g.max_pages;
+  if (g.max_kv_hint > 0 && g.max_kv_hint < cap) cap = g.max_kv_hint;
+  p.ppb = g.page > 0 ? ceil_div(cap, g.page) : 0;
   if (p.ppb < 1) p.ppb = 1;                              // (a table without columns: one scratch page per row, marked absent)
-  int64_t n_qb;
-  int ks = 1;
-  if (total_tokens > 0 && batch > 0 && q_heads > 0 && kv_heads > 0 && q_heads % kv_heads == 0)
-    prefill_plan(total_tokens, batch, q_heads, kv_heads, block_size, p.ppb, max_q_len_hint, max_kv_len_hint, n_qb, ks);
-  p.ws_inner = ks > 1 ? n_qb * kv_heads * batch * ks * 128 * (head_dim + 2) * static_cast<int64_t>(sizeof(float)) + 64 : 0;
+  inner = g;
+  inner.max_pages = p.ppb;
+  p.ws_inner = prefill_plan(inner).query_bytes;
   auto up = [](int64_t x) { return (x + 255) & ~int64_t{255}; };
   p.off_table = up(p.ws_inner);
-  p.off_k = p.off_table + up(batch * p.ppb * 4);
-  const int64_t pool = up(batch * p.ppb * kv_heads * block_size * head_dim * 2);
+  p.off_k = p.off_table + up(g.batch * p.ppb * 4);
+  const int64_t pool = up(g.batch * p.ppb * g.kv_heads * g.page * g.head_dim * 2);
   p.off_v = p.off_k + pool;
   p.total = p.off_v + pool;
   return p;
@@ -102,8 +100,9 @@ extern "C" int64_t mojo_hip_paged_prefill_gqa_kv8_workspace_bytes(int64_t total_
                                                                   int64_t max_blocks_per_seq, int64_t max_q_len_hint,
                                                                   int64_t max_kv_len_hint) {
   if (total_tokens <= 0 || batch <= 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return 0;
-  return mojo::prefill_kv8_plan(total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
-                                max_kv_len_hint).total;
+  mojo::PrefillGeom inner;
+  return mojo::prefill_kv8_plan({total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint,
+                                 max_kv_len_hint}, inner).total;
 }
 
 extern "C" int mojo_hip_paged_prefill_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
@@ -136,12 +135,18 @@ extern "C" int mojo_hip_paged_prefill_gqa_kv8(const void* query, const void* key
                    aligned_to(key_cache, 16) && aligned_to(value_cache, 16) && aligned_to(query, 16) && aligned_to(out, 16) &&
                    aligned_to(key_scale, 16) && aligned_to(value_scale, 16),
                MOJO_EUNSUPPORTED, "paged_prefill_gqa_kv8: tensors must be 16-byte aligned with 16-byte row strides");
-  if (batch == 0)                                        // no sequences: the 16-bit entry point's own treatment (zeros)
-    return paged_prefill<false>(query, key_cache, value_cache, cu_q_lens, cu_total_seq_lens, block_tables, out, total_tokens, batch,
-                                q_heads, kv_heads, head_dim, block_size, 0, block_table_stride, 16, 16, 16, max_q_len_hint,
-                                max_kv_len_hint, softmax_scale, layout_abab, dtype, nullptr, 0, -1, 0, stream);
-  const PrefillKv8Plan p = prefill_kv8_plan(total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq,
-                                            max_q_len_hint, max_kv_len_hint);
+  // the 16-bit prefill over the scratch pages: dense [page][Hkv][token][D] pools and the scratch table, one row of ppb ids each
+  PrefillCall c;
+  c.query = query; c.cu_q_lens = cu_q_lens; c.cu_total_seq_lens = cu_total_seq_lens; c.out = out;
+  c.softmax_scale = softmax_scale; c.layout_abab = layout_abab; c.dtype = dtype; c.stream = stream;
+  const PrefillGeom geom{total_tokens, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_q_len_hint, max_kv_len_hint};
+  if (batch == 0) {                                      // no sequences: the 16-bit entry point's own treatment (zeros)
+    c.g = geom; c.g.max_pages = 0;
+    c.key_cache = key_cache; c.value_cache = value_cache; c.block_tables = block_tables; c.block_table_stride = block_table_stride;
+    c.cache_block_stride = c.cache_head_stride = c.cache_token_stride = 16;
+    return paged_prefill(c);
+  }
+  const PrefillKv8Plan p = prefill_kv8_plan(geom, c.g);
   MOJO_REQUIRE(workspace && workspace_bytes >= p.total, MOJO_EWORKSPACE, "paged_prefill_gqa_kv8: workspace %lld B < required %lld B",
                (long long)workspace_bytes, (long long)p.total);
   MOJO_REQUIRE(aligned_to(workspace, 256), MOJO_EINVAL, "paged_prefill_gqa_kv8: workspace must be 256-byte aligned");
@@ -160,10 +165,10 @@ extern "C" int mojo_hip_paged_prefill_gqa_kv8(const void* query, const void* key
   g.scale_dtype = scale_dtype; g.out_bf16 = dtype == MOJO_BF16 ? 1 : 0;
   hipLaunchKernelGGL(gather_kv8_kernel, dim3(static_cast<unsigned>(batch * p.ppb), static_cast<unsigned>(kv_heads)), dim3(256), 0, s, g);
   MOJO_CHECK_LAUNCH("paged_prefill_gqa_kv8(gather)");
-  const int rc = paged_prefill<false>(query, ws + p.off_k, ws + p.off_v, cu_q_lens, cu_total_seq_lens, g.table_out, out, total_tokens,
-                                      batch, q_heads, kv_heads, head_dim, block_size, p.ppb, p.ppb, kv_heads * block_size * head_dim,
-                                      block_size * head_dim, head_dim, max_q_len_hint, max_kv_len_hint, softmax_scale, layout_abab,
-                                      dtype, p.ws_inner > 0 ? ws : nullptr, p.ws_inner, -1, 0, stream);
+  c.key_cache = ws + p.off_k; c.value_cache = ws + p.off_v; c.block_tables = g.table_out; c.block_table_stride = p.ppb;
+  c.cache_block_stride = kv_heads * block_size * head_dim; c.cache_head_stride = block_size * head_dim; c.cache_token_stride = head_dim;
+  c.workspace = p.ws_inner > 0 ? ws : nullptr; c.workspace_bytes = p.ws_inner;
+  const int rc = paged_prefill(c);
   if (rc != MOJO_OK) return rc;
   note_launch("gather:kv8+%s", "prefill");
   return MOJO_OK;
