@@ -25,6 +25,15 @@
 // The LDS image belongs to ONE wave (LDS operations of a wave execute in order): no barrier anywhere in the loop.  Pages must
 // hold a multiple of 16 tokens (a tile then lies in one page), head_dim 64 or 128, group size <= 16; everything else takes the
 // vector-unit kernel.  Same chunking, pairing, in-LDS merge, workspace layout and hole / empty-row semantics as that kernel.
+//
+// The K/V stream is a ring of three tiles (8 KiB each) in registers.  From five tiles on, a wave runs rounds of three tiles
+// in which every request is unconditional: the compiler then counts the loads, and processing tile t waits for t's own eight
+// loads, vmcnt(23) .. (16), with the loads of t + 1 and t + 2 still outstanding (at head_dim 128 the compiler also puts the
+// first selects of the hole zeroing, vmcnt(15) .. (12), in front of the request for t + 2: DESIGN 4.1); the last one to four
+// tiles go through a tail of conditional requests.  Page ids never cost a round trip inside the stream: they sit in registers, 60 sub-tiles per window, and are read
+// by lane (see `id_window`).  As first written — a loop of conditional requests, the id of every tile fetched by a load —
+// the compiled loop waited vmcnt(0) for each id and vmcnt(7) .. (0) right after each request: one tile in flight, none
+// while the id travelled.  scripts/check_decode_ring.py reads the waits of the compiled loop (tests/test_isa_decode_ring.py).
 #pragma once
 
 namespace mojo {
@@ -131,15 +140,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   const int hq_l = min(tl, G - 1);                      // lanes past the group repeat its last head (computed, never stored)
   // B operands: line L (128 bytes = 8 chunks) of the row, parity p: lane k-group g4 holds the dims of chunk 8 L + 2 g4 + p
   constexpr int NL = D / 64;                            // 128-byte lines per token row
-  typename MM::frag8 qf[NL][2];
-  {
-    const int h = decode_head(a, kvh, hq_l, G);
-    const T* qp = static_cast<const T*>(a.q) + (static_cast<int64_t>(b) * a.hq + h) * a.dim;
-#pragma unroll
-    for (int L = 0; L < NL; ++L)
-#pragma unroll
-      for (int p = 0; p < 2; ++p) qf[L][p] = *reinterpret_cast<const typename MM::frag8*>(qp + (8 * L + 2 * g4 + p) * 8);
-  }
+  typename MM::frag8 qf[NL][2];                         // (loaded below, with the page ids)
 
   f32x4 o[ND];
 #pragma unroll
@@ -155,18 +156,16 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   auto scan_issue = [&](int base) {
 #pragma unroll
     for (int u = 0; u < SCAN; ++u) {
-      const int idx = base + u * 64 + lane;
-      scan_v[u] = idx < p1 ? table[idx] : 0;
+      scan_v[u] = table[min(base + u * 64 + lane, p1 - 1)];           // (unconditional: a guarded load is waited for on the spot)
     }
   };
   auto scan_reduce = [&](int base) {
 #pragma unroll
     for (int u = 0; u < SCAN; ++u) {
-      const unsigned long long neg = __ballot(scan_v[u] < 0);
+      const unsigned long long neg = __ballot(scan_v[u] < 0 && base + u * 64 + lane < p1);
       if (neg && first_neg == 0x7fffffff) first_neg = base + u * 64 + __builtin_ctzll(neg);
     }
   };
-  if (!SWA && has_work) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
 
   // K: instruction (token group j, line L) = tokens 8 j + (l & 7), chunk 8 L + (l >> 3);  V: whole rows, RPI rows per instruction
   constexpr int CPR = D / 8;                            // 16-byte chunks per row
@@ -179,19 +178,51 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   const int last_tile = ((tok_end - 1) / DECM_TILE) * DECM_TILE;      // first token of the last non-empty tile
   const int last_page = a.max_pages - 1;
 
+  // Page ids: one register per window of the chunk.  Lane i of the window at sub-tile `base` holds the table entry of
+  // sub-tile base + i (with the clamps of the tile itself: last tile, window jump, last table column), so the id of a
+  // tile is a lane read at a wave-uniform index: no load sits between a tile landing and the next request.  A round of
+  // the steady loop (three tiles, 3 NS sub-tiles) requests up to 2 NS sub-tiles past its own, and windows change between
+  // rounds only, so consecutive windows start IDW = 60 sub-tiles apart (a whole number of rounds) and overlap in their
+  // last four lanes.  `idw` is the window in use, `idn` the next one: requested when the ring
+  // enters `idw`, at least one round (24 tile loads) before its first use.  Lanes past the chunk's last tile repeat
+  // that tile's entry: nothing past the chunk's pages is fetched, let alone used.
+  constexpr int IDW = 60;
+  static_assert(IDW % (3 * NS) == 0 && IDW + 2 * NS <= 64, "windows change between rounds; a round's requests stay inside one");
+  auto id_window = [&](int s_base) -> int {
+    int tu = min(tok_begin + DECM_TILE * (s_base + lane), last_tile);
+    if constexpr (SWA) tu = decode_swa_real(win, tu);
+    return table[min(tu >> a.page_shift, last_page)];
+  };
+  {                                                     // waited for in front of the first S^T product only
+    const int h = decode_head(a, kvh, hq_l, G);
+    const T* qp = static_cast<const T*>(a.q) + (static_cast<int64_t>(b) * a.hq + h) * a.dim;
+#pragma unroll
+    for (int L = 0; L < NL; ++L)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) qf[L][p] = *reinterpret_cast<const typename MM::frag8*>(qp + (8 * L + 2 * g4 + p) * 8);
+  }
+  int idw = 0, idn = 0, id_base = 0;                    // (id_base: first sub-tile of idw)
+  // Prologue: the query slices, the two id windows and the hole scan are requested together — the first two tiles go out
+  // back to back as soon as window 0 has landed, with window 1 and the scan still on their way.
+  if (has_work) {
+    idw = id_window(0);
+    idn = id_window(IDW);
+    if constexpr (!SWA) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
+  }
   struct Tile { V8 k[NS][2][NL]; V8 v[NS][NV]; int lp[NS]; };
   auto ld = [&](const T* p) -> V8 {
     if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const V8*>(p));
     else return *reinterpret_cast<const V8*>(p);
   };
   auto load_tile = [&](Tile& t, int t0) {
+    const int s0 = __builtin_amdgcn_readfirstlane((t0 - tok_begin) / DECM_TILE) - id_base;   // lane of the window in use
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss) {
       int tu = min(t0 + DECM_TILE * ss, last_tile);         // wave-uniform; 16 | page: the sub-tile lies in one page
       if constexpr (SWA) tu = decode_swa_real(win, tu);
       const int lp = tu >> a.page_shift;
       t.lp[ss] = lp;
-      const int phys = max(table[min(lp, last_page)], 0);
+      const int phys = max(__builtin_amdgcn_readlane(idw, s0 + ss), 0);
       const int64_t pg = static_cast<int64_t>(phys) * a.c_blk + static_cast<int64_t>(tu - (lp << a.page_shift)) * a.c_tok;
 #pragma unroll
       for (int j = 0; j < 2; ++j)
@@ -326,24 +357,57 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
 
   Tile ta, tb, tc;
   if (has_work) {
-    load_tile(ta, tok_begin);
-    if (tok_begin + STEP < tok_end) load_tile(tb, tok_begin + STEP);
-    if constexpr (!SWA) {
-      scan_reduce(0);
-      for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
-        scan_issue(base);
-        scan_reduce(base);
+    auto scan_rest = [&]() {                             // the hole scan: what the prologue requested, then the rest of a long row
+      if constexpr (!SWA) {
+        scan_reduce(0);
+        for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
+          scan_issue(base);
+          scan_reduce(base);
+        }
       }
+    };
+    int t0 = tok_begin;
+    load_tile(ta, tok_begin);
+    if (tok_begin + 4 * STEP < tok_end) {
+      load_tile(tb, tok_begin + STEP);                   // (unconditional on the way into the loop: its waits count on both tiles)
+      scan_rest();
+      // steady state: every request is unconditional, so the waits of process() are counted — tile t waits for its own
+      // eight loads and leaves those of tiles t + 1 and t + 2 outstanding (no wait of the loop goes below vmcnt(12)).  One round = three tiles; the id window
+      // changes between rounds, after at least one round in the window before it.
+      for (;;) {
+        const int t_win = tok_begin + DECM_TILE * (id_base + IDW);    // first round of the next window
+        do {
+          load_tile(tc, t0 + 2 * STEP);
+          process(ta, t0);
+          load_tile(ta, t0 + 3 * STEP);
+          process(tb, t0 + STEP);
+          load_tile(tb, t0 + 4 * STEP);
+          process(tc, t0 + 2 * STEP);
+          t0 += 3 * STEP;
+        } while (t0 + 4 * STEP < tok_end && t0 < t_win);
+        if (t0 < t_win) break;
+        // (also in front of the tail: its requests lie in the new window.  The copy is an instruction of its own so that it
+        // stands in FRONT of the request, which then lands in the register the copy freed: as a plain assignment it is
+        // placed behind the request, and the copy out of a third register waits for vmcnt(0) with two tiles in flight)
+        asm volatile("v_mov_b32 %0, %1" : "=v"(idw) : "v"(idn));
+        id_base += IDW;
+        idn = id_window(id_base + IDW);
+        if (t0 + 4 * STEP >= tok_end) break;
+      }
+    } else {
+      if (tok_begin + STEP < tok_end) load_tile(tb, tok_begin + STEP);
+      scan_rest();
     }
-    for (int t0 = tok_begin; t0 < tok_end; t0 += 3 * STEP) {
-      if (t0 + 2 * STEP < tok_end) load_tile(tc, t0 + 2 * STEP);
-      process(ta, t0);
-      if (t0 + STEP >= tok_end) break;
+    // the last one to four tiles (ta and tb, where they exist, are on their way)
+    if (t0 + 2 * STEP < tok_end) load_tile(tc, t0 + 2 * STEP);
+    process(ta, t0);
+    if (t0 + STEP < tok_end) {
       if (t0 + 3 * STEP < tok_end) load_tile(ta, t0 + 3 * STEP);
       process(tb, t0 + STEP);
-      if (t0 + 2 * STEP >= tok_end) break;
-      if (t0 + 4 * STEP < tok_end) load_tile(tb, t0 + 4 * STEP);
-      process(tc, t0 + 2 * STEP);
+      if (t0 + 2 * STEP < tok_end) {
+        process(tc, t0 + 2 * STEP);
+        if (t0 + 3 * STEP < tok_end) process(ta, t0 + 3 * STEP);
+      }
     }
   }
 
