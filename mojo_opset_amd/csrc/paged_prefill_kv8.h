@@ -5,7 +5,8 @@
 // (K8 * key_scale, V8 * value_scale: fp32 products rounded to the query dtype) and writes compact 16-bit scratch pages:
 // page lp of sequence b lands at scratch page b * ppb + lp, which is also what the scratch table the same kernel writes says
 // (-1 for an id outside the pool — the prefill kernel reads such a page as zeros — and for every page past the sequence's
-// length, which is not gathered).  ppb = ceil(min(max_total_seq_len hint, page * table width) / page), sized without a host sync: a caller who
+// length, which is not gathered; scratch page 0, which the prefill kernel loads for a negative id, is zero-filled when it is
+// not gathered).  ppb =ceil(min(max_total_seq_len hint, page * table width) / page), sized without a host sync: a caller who
 // omits the hint on a wide table pays for the table's capacity in workspace (not in bytes moved).
 // The gather moves three int8-cache-sizes of bytes (1 read + 2 written) per gathered element, once per call.
 #pragma once
@@ -38,11 +39,25 @@ __global__ __launch_bounds__(256) void gather_kv8_kernel(GatherKv8Args a) {
   const bool ok = phys >= 0 && phys < a.num_blocks;
   // a scratch page is present only where it is written: inside the row's length and named by an id of the pool
   if (h == 0 && threadIdx.x == 0) a.table_out[sp] = (ok && lp < needed) ? sp : -1;
-  if (!ok || lp >= needed) return;
   const int pieces = a.dim / 16;
   const int per_tensor = a.page * pieces;
-  const int64_t src_base = static_cast<int64_t>(phys) * a.c_blk + static_cast<int64_t>(h) * a.c_head;
   const int64_t dst_base = (static_cast<int64_t>(sp) * a.hkv + h) * a.page * a.dim;
+  if (!ok || lp >= needed) {
+    // Scratch page 0 is the page the prefill kernel loads for every absent id (it clamps the id to 0 and gives those keys a
+    // probability of zero): when it is not gathered itself it must still hold finite numbers — 0 * NaN of an unwritten
+    // workspace would reach the output.  No other absent page is ever addressed.
+    if (sp == 0) {
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      for (int w = threadIdx.x; w < 2 * per_tensor; w += blockDim.x) {
+        const int which = w >= per_tensor;
+        char* dst = static_cast<char*>(which ? a.vs_out : a.ks_out) + (dst_base + static_cast<int64_t>(which ? w - per_tensor : w) * 16) * 2;
+        *reinterpret_cast<u32x4*>(dst) = z;
+        *reinterpret_cast<u32x4*>(dst + 16) = z;
+      }
+    }
+    return;
+  }
+  const int64_t src_base = static_cast<int64_t>(phys) * a.c_blk + static_cast<int64_t>(h) * a.c_head;
   for (int w = threadIdx.x; w < 2 * per_tensor; w += blockDim.x) {
     const int which = w >= per_tensor;
     const int r = which ? w - per_tensor : w;

@@ -284,3 +284,110 @@ def test_fuzz_dynamic_quant_bit_exact(seed):
             op.inv_smooth_scale.copy_(w)
         op = op.to(DEV)
     assert bit_equal(to_cpu(op(x.to(DEV))), ref(x))
+
+
+def _drawn_layout(rnd, k, v, table):
+    """A cache layout and a table layout of tests/cache_layouts.py, drawn; the views live on the device.  One spare page of
+    the pool is poisoned (NaN / 127) and named by every hidden table column."""
+    import cache_layouts as CL
+    hidden = CL.poison_page([k, v], CL.spare_pages(k.shape[0], table)[0])
+    names = rnd.choice(CL.CACHE_LAYOUTS), rnd.choice(CL.TABLE_LAYOUTS)
+    kv = CL.lay_out_kv(k, v, names[0]).to(DEV)
+    return kv.views, CL.lay_out_table(table, names[1], hidden).to(DEV).views[0], names
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_fuzz_swa(seed):
+    """The sliding-window pair, decode and prefill, on a drawn cache and table layout."""
+    import swa_golden
+    from hip_utils import last_launch
+    rnd = random.Random(10000 + seed + OFFSET)
+    hkv = rnd.choice([1, 2, 4, 8])
+    g = rnd.choice([1, 2, 4, 8])
+    d = rnd.choice([64, 96, 128])
+    page = rnd.choice([16, 32, 64, 128])
+    dtype = rnd.choice([torch.bfloat16, torch.bfloat16, torch.float16])
+    kw = dict(gqa_layout=rnd.choice(["ABAB", "AABB"]), global_window_size=rnd.choice([None, 4, 40, 130]),
+              local_window_size=rnd.choice([1, 17, 64, 255, 1023]))
+    # decode
+    batch = rnd.choice([1, 2, 3, 5, 8, 17])
+    max_len = rnd.choice([40, 300, 1100, 2500])
+    lens = [rnd.choice([0, 1, rnd.randint(1, max_len), max_len]) for _ in range(batch)]
+    q, k, v, lens_t, table = make_decode_inputs(batch, hkv * g, hkv, d, max_len, page, dtype=dtype, seed=seed + OFFSET, lens=lens)
+    (kd, vd), td, names = _drawn_layout(rnd, k, v, table)
+    want = swa_golden.TorchPagedDecodeSWA(**kw).forward(q, k, v, lens_t, table)
+    op = hip_cls("MojoPagedDecodeSWA")(**kw)
+    got = to_cpu(op(q.to(DEV), kd, vd, lens_t.to(DEV), td))
+    assert last_launch().endswith(":swa"), (last_launch(), names)
+    assert bool(torch.isfinite(got.float()).all()), names
+    assert_close_tree(got, want, 2e-2, 2e-2)
+    hinted = to_cpu(op(q.to(DEV), kd, vd, lens_t.to(DEV), td, max_total_seq_len=max(max(lens), 1)))
+    assert_close_tree(hinted, want, 2e-2, 2e-2)
+    # prefill
+    batch = rnd.choice([1, 2, 3, 4])
+    q_lens = [rnd.choice([0, 1, rnd.randint(1, 300), rnd.randint(100, 700)]) for _ in range(batch)]
+    cached = [rnd.choice([0, 0, rnd.randint(1, 500)]) for _ in range(batch)]
+    q, k, v, cu_q, table, cu_kv, kv_lens = make_prefill_inputs(q_lens, cached, hkv * g, hkv, d, page, dtype=dtype, seed=seed + OFFSET)
+    (kd, vd), td, names = _drawn_layout(rnd, k, v, table)
+    cu_kv = cu(kv_lens)
+    want = swa_golden.TorchPagedPrefillSWA(**kw).forward(q, k, v, cu_q, table, cu_total_seq_lens=cu_kv)
+    got = to_cpu(hip_cls("MojoPagedPrefillSWA")(**kw)(q.to(DEV), kd, vd, cu_q.to(DEV), td, cu_total_seq_lens=cu_kv.to(DEV)))
+    assert bool(torch.isfinite(got.float()).all()), names
+    assert_close_tree(got, want, 2e-2, 2e-2)
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_fuzz_kv_int8(seed):
+    """The int8-KV pair, decode and prefill, on a drawn cache and table layout, with a drawn scale dtype; in the decode a hole
+    (-1) may sit in a table row: the pages at and behind it read as zero K/V, i.e. as the oracle's page of zeros."""
+    from hip_utils import last_launch
+    from test_hip_kv_int8 import make_inputs
+    rnd = random.Random(11000 + seed + OFFSET)
+    hkv = rnd.choice([1, 2, 4])
+    g = rnd.choice([1, 2, 4, 8, 16])
+    d = rnd.choice([64, 80, 96, 128])
+    page = rnd.choice([16, 32, 64, 128])
+    dtype = rnd.choice([torch.bfloat16, torch.bfloat16, torch.float16])
+    scale_dtype = rnd.choice([torch.bfloat16, torch.float16, torch.float32])
+    layout = rnd.choice(["ABAB", "AABB"])
+    # decode
+    batch = rnd.choice([1, 2, 3, 5, 8, 17])
+    max_len = rnd.choice([40, 300, 1100, 2500])
+    lens = [rnd.choice([0, 1, rnd.randint(1, max_len), max_len]) for _ in range(batch)]
+    q, k8, ks, v8, vs, table = make_inputs(hkv * g, hkv, d, page, lens, batch, seed=seed + OFFSET, dtype=dtype)
+    ks, vs = ks.to(scale_dtype), vs.to(scale_dtype)
+    lens_t = torch.tensor(lens, dtype=torch.int32)
+    filled = table
+    if rnd.random() < 0.4 and table.shape[1] > 2:
+        spare = [i for i in range(k8.shape[0]) if i not in set(table[table >= 0].tolist())]
+        k8[spare[-1]], v8[spare[-1]] = 0, 0
+        b, p = rnd.randrange(batch), rnd.randrange(1, table.shape[1])
+        table, filled = table.clone(), table.clone()
+        table[b, p] = -1
+        filled[b, p:] = spare[-1]
+    (kd, vd), td, names = _drawn_layout(rnd, k8, v8, table)
+    ref = torch_cls("MojoPagedDecodeGQAWithKVDequant")(gqa_layout=layout)
+    ref.query_dtype = dtype
+    want = ref(q, None, k8, ks, v8, vs, lens_t, filled)
+    op = hip_cls("MojoPagedDecodeGQAWithKVDequant")(gqa_layout=layout)
+    got = to_cpu(op(q.to(DEV), None, kd, ks.to(DEV), vd, vs.to(DEV), lens_t.to(DEV), td))
+    assert last_launch().endswith(":kv8"), (last_launch(), names)
+    assert_close_tree(got, want, 2e-2, 2e-2)
+    hinted = to_cpu(op(q.to(DEV), None, kd, ks.to(DEV), vd, vs.to(DEV), lens_t.to(DEV), td, max_total_seq_len=max(max(lens), 1)))
+    assert_close_tree(hinted, want, 2e-2, 2e-2)
+    if d == 80 or g == 16:                                                # outside the prefill's envelope
+        return
+    # prefill
+    batch = rnd.choice([1, 2, 3, 4])
+    q_lens = [rnd.choice([0, 1, rnd.randint(1, 300), rnd.randint(100, 700)]) for _ in range(batch)]
+    kv_lens = [n + rnd.choice([0, 0, rnd.randint(1, 500)]) for n in q_lens]
+    q, k8, ks, v8, vs, table = make_inputs(hkv * g, hkv, d, page, kv_lens, sum(q_lens), seed=seed + OFFSET + 1, dtype=dtype)
+    ks, vs = ks.to(scale_dtype), vs.to(scale_dtype)
+    (kd, vd), td, names = _drawn_layout(rnd, k8, v8, table)
+    ref = torch_cls("MojoPagedPrefillGQAWithKVDequant")(gqa_layout=layout)
+    ref.query_dtype = dtype
+    want = ref(q, None, k8, ks, v8, vs, cu(q_lens), table, cu_total_seq_lens=cu(kv_lens))
+    op = hip_cls("MojoPagedPrefillGQAWithKVDequant")(gqa_layout=layout)
+    got = to_cpu(op(q.to(DEV), None, kd, ks.to(DEV), vd, vs.to(DEV), cu(q_lens).to(DEV), td, cu_total_seq_lens=cu(kv_lens).to(DEV)))
+    assert "kv8" in last_launch(), (last_launch(), names)
+    assert_close_tree(got, want, 2e-2, 2e-2)

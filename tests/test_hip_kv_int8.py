@@ -411,3 +411,128 @@ def test_decode_query_operand_saturates_instead_of_overflowing():
     ks[0, 0] = 8.0
     out = to_cpu(run_decode("AABB", q, k8, ks, v8, vs, torch.tensor(lens, dtype=torch.int32), table))
     assert bool(torch.isfinite(out.float()).all())
+
+
+# ---- decode edges: holes, unused table entries, relabelled pages, the cached instance -------------------------------------
+HOLE_LENS = [700, 129, 40]                         # row 0: 44 pages of 16 tokens
+LONG_HOLE_LENS = [4200, 40]                        # row 0: 263 pages — the hole scan's second batch of 256 pages runs
+
+
+def chunk_first_pages(n, page=16):
+    """First page of the second chunk of an n-token row for every chunk count a fused launch may choose (2 .. 8 waves): equal
+    pieces of whole 16-token tiles, 128 tokens at least (the rule `test_decode_lengths_at_tile_chunk_and_page_boundaries` names)."""
+    return sorted({-(-max(-(-n // c), 128) // 16) * 16 // page for c in range(2, 9)})
+
+
+HOLES = {"first": (HOLE_LENS, [0]), "mid": (HOLE_LENS, [20]), "chunk_first": (HOLE_LENS, chunk_first_pages(HOLE_LENS[0])),
+         "row_last": (HOLE_LENS, [43]), "page_258": (LONG_HOLE_LENS, [258])}
+
+
+def hole_case(lens, seed=41):
+    hq, hkv = (4, 1) if lens is LONG_HOLE_LENS else (8, 2)
+    q, k8, ks, v8, vs, table = make_inputs(hq, hkv, 128, 16, lens, len(lens), seed=seed)
+    spare = [i for i in range(k8.shape[0]) if i not in set(table[table >= 0].tolist())]
+    k8[spare[0]], v8[spare[0]] = 0, 0              # the oracle's page of zero K and V
+    k8[spare[1]], v8[spare[1]] = 127, 127          # what an unused table entry may name
+    return q, k8, ks, v8, vs, table, spare[0], spare[1]
+
+
+def holed(table, page_idx, zero_page):
+    """(the table with -1 at row 0's page ``page_idx``, the oracle's copy: that entry and every later one of the row name the
+    page of zeros — pages at and behind the first negative id read as zero K/V, csrc/paged_decode_kv8.h)."""
+    hole, filled = table.clone(), table.clone()
+    hole[0, page_idx] = -1
+    filled[0, page_idx:] = zero_page
+    return hole, filled
+
+
+@pytest.mark.parametrize("where", list(HOLES))
+@pytest.mark.parametrize("form", ["fused", "split"])
+@pytest.mark.parametrize("layout", ["ABAB", "AABB"])
+def test_decode_holes_read_as_zero_keys_and_values(layout, form, where):
+    lens, pages = HOLES[where]
+    q, k8, ks, v8, vs, table, zero_page, _ = hole_case(lens)
+    lens_t = torch.tensor(lens, dtype=torch.int32)
+    assert (lens[0] + 15) // 16 > max(pages) and (where != "page_258" or pages[0] >= 256)
+    # (a few rows of 4 200 tokens are planned as 33 chunks of 128 tokens, the split form: chunks of 1 024 keep them in one
+    # workgroup of five waves, whose last wave scans 263 table entries)
+    chunk = "1024" if (form, where) == ("fused", "page_258") else None
+    with switch_env(MOJO_HIP_DECODE_FUSE="0" if form == "split" else None, MOJO_HIP_DECODE_CHUNK=chunk):
+        for p in pages:
+            hole, filled = holed(table, p, zero_page)
+            got = to_cpu(run_decode(layout, q, k8, ks, v8, vs, lens_t, hole))
+            assert ("split+merge" if form == "split" else ":fused:") in last_launch(), last_launch()
+            check(got, ref_decode(layout, q, k8, ks, v8, vs, lens_t, filled), f"hole {where} page {p} {form} {layout}")
+            # the same bits as the kernel's own result on the oracle's table: a hole is exactly a page of zeros
+            assert torch.equal(got, to_cpu(run_decode(layout, q, k8, ks, v8, vs, lens_t, filled)))
+
+
+@pytest.mark.parametrize("where", list(HOLES))
+@pytest.mark.parametrize("layout", ["ABAB", "AABB"])
+def test_prefill_holes_read_as_zero_keys_and_values(layout, where):
+    lens, pages = HOLES[where]
+    _, k8, ks, v8, vs, table, zero_page, _ = hole_case(lens)
+    q_lens = [min(n, 24) for n in lens]
+    hq = 4 if lens is LONG_HOLE_LENS else 8
+    q = torch.randn(sum(q_lens), hq, 128, generator=torch.Generator().manual_seed(43)).to(torch.bfloat16)
+    op, ref = hip_cls(PRE)(gqa_layout=layout), torch_cls(PRE)(gqa_layout=layout)
+    from mojo_opset_amd.backends.hip import lib as L
+    ws_bytes = max(L.load().mojo_hip_paged_prefill_gqa_kv8_workspace_bytes(q.shape[0], len(lens), hq, k8.shape[1], 128, 16, table.shape[1], 0, 0), 256)
+    for p in pages:
+        hole, filled = holed(table, p, zero_page)
+        # the op's workspace (scratch pages included) is uninitialised memory: hand the allocator a block of NaN patterns of
+        # its size to reuse, so that a scratch page that is addressed without having been gathered shows
+        junk = torch.full((ws_bytes,), 0xFF, dtype=torch.uint8, device=DEV)
+        del junk
+        got = op(*dev(q, None, k8, ks, v8, vs, cu(q_lens), hole), cu_total_seq_lens=cu(lens).to(DEV))
+        torch.cuda.synchronize()
+        assert "kv8" in last_launch()
+        check(to_cpu(got), ref(q, None, k8, ks, v8, vs, cu(q_lens), filled, cu_total_seq_lens=cu(lens)), f"prefill hole {where} page {p} {layout}")
+
+
+@pytest.mark.parametrize("form", ["fused", "split"])
+def test_decode_table_with_valid_ids_past_a_rows_length(form):
+    """Table columns past a row's pages name a real page of 127s (a pre-allocated cache): never read, not one bit changes."""
+    q, k8, ks, v8, vs, table, _, sevens = hole_case(HOLE_LENS)
+    lens_t = torch.tensor(HOLE_LENS, dtype=torch.int32)
+    wide = torch.full((table.shape[0], table.shape[1] + 5), -1, dtype=torch.int32)
+    wide[:, : table.shape[1]] = table
+    full = wide.clone()
+    full[full < 0] = sevens
+    with switch_env(MOJO_HIP_DECODE_FUSE="0" if form == "split" else None):
+        for hint in (None, 700, 704):
+            kw = {} if hint is None else {"max_total_seq_len": hint}
+            a = run_decode("AABB", q, k8, ks, v8, vs, lens_t, wide, **kw)
+            b = run_decode("AABB", q, k8, ks, v8, vs, lens_t, full, **kw)
+            assert torch.equal(a, b), hint
+        check(to_cpu(b), ref_decode("AABB", q, k8, ks, v8, vs, lens_t, table), f"full table {form}")
+
+
+@pytest.mark.parametrize("form", ["fused", "split"])
+def test_decode_relabelled_pages_and_a_second_launch_change_no_bit(form):
+    from test_hip_decode_ring import relabel
+    q, k8, ks, v8, vs, table, _, _ = hole_case(LONG_HOLE_LENS)
+    lens_t = torch.tensor(LONG_HOLE_LENS, dtype=torch.int32)
+    k2, v2, table2 = relabel(k8, v8, table)
+    with switch_env(MOJO_HIP_DECODE_FUSE="0" if form == "split" else None):
+        a = run_decode("AABB", q, k8, ks, v8, vs, lens_t, table)
+        assert torch.equal(run_decode("AABB", q, k8, ks, v8, vs, lens_t, table), a)
+        assert torch.equal(run_decode("AABB", q, k2, ks, v2, vs, lens_t, table2), a)
+    check(to_cpu(a), ref_decode("AABB", q, k8, ks, v8, vs, lens_t, table), f"relabel {form}")
+
+
+@pytest.mark.parametrize("form", ["fused", "split"])
+@pytest.mark.parametrize("scale_dtype", [torch.bfloat16, torch.float16, torch.float32], ids=["bf16", "fp16", "fp32"])
+def test_decode_cached_instance_gives_the_bits_of_the_streaming_one(scale_dtype, form):
+    """`MOJO_HIP_STREAM_NT=0` launches the instance with plain (cached) loads: `:cached:` in its name, the same bits."""
+    q, k8, ks, v8, vs, table = make_inputs(12, 3, 96, 32, SHORT_LENS, len(SHORT_LENS), seed=47)
+    ks, vs = ks.to(scale_dtype), vs.to(scale_dtype)
+    lens_t = torch.tensor(SHORT_LENS, dtype=torch.int32)
+    with switch_env(MOJO_HIP_DECODE_FUSE="0" if form == "split" else None):
+        a = run_decode("AABB", q, k8, ks, v8, vs, lens_t, table)
+        assert ":nt:" in last_launch(), last_launch()
+        with switch_env(MOJO_HIP_STREAM_NT="0"):
+            b = run_decode("AABB", q, k8, ks, v8, vs, lens_t, table)
+            assert ":cached:" in last_launch(), last_launch()
+    assert torch.equal(a, b)
+    check(to_cpu(a), ref_decode("AABB", q, k8, ks, v8, vs, lens_t, table), f"cached {form} {scale_dtype}")
