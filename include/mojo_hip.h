@@ -428,6 +428,42 @@ int mojo_hip_paged_prefill_gqa_kv8(const void* query, const void* key_cache, con
                                    int64_t cache_token_stride, int64_t max_q_len_hint, int64_t max_kv_len_hint,
                                    float softmax_scale, int layout_abab, int dtype, int scale_dtype,
                                    void* workspace, int64_t workspace_bytes, mojo_stream_t stream);
+/*      The same two ops with a sliding window (MojoPagedDecodeSWAWithKVDequant / MojoPagedPrefillSWAWithKVDequant): the
+ *      arguments of their _gqa_kv8 siblings plus local_window (< 0: none) and global_window (<= 0: none), with the
+ *      visibility rule of mojo_hip_paged_decode_swa / mojo_hip_paged_prefill_swa.  With neither window they run the
+ *      _gqa_kv8 op itself.  Decode walks (and sizes its launch on) the visible keys only; pages outside a row's visible
+ *      set are never read and may carry any VALID id or -1.  Prefill gathers only the pages that intersect a sequence's
+ *      visible union into a compact scratch (block_size a multiple of 16 with a window).                              */
+int64_t mojo_hip_paged_decode_swa_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                      int64_t head_dim, int64_t block_size,
+                                                      int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                      int64_t local_window, int64_t global_window);
+int mojo_hip_paged_decode_swa_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                  const void* value_cache, const void* value_scale,
+                                  const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                  void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                  int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                  int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                  int64_t cache_block_stride, int64_t cache_head_stride,
+                                  int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                  int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
+                                  int64_t local_window, int64_t global_window, mojo_stream_t stream);
+int64_t mojo_hip_paged_prefill_swa_kv8_workspace_bytes(int64_t total_tokens, int64_t batch, int64_t q_heads,
+                                                       int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                                       int64_t max_blocks_per_seq, int64_t max_q_len_hint,
+                                                       int64_t max_kv_len_hint, int64_t local_window,
+                                                       int64_t global_window);
+int mojo_hip_paged_prefill_swa_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                   const void* value_cache, const void* value_scale, const int32_t* cu_q_lens,
+                                   const int32_t* cu_total_seq_lens, const int32_t* block_tables, void* out,
+                                   int64_t total_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                   int64_t head_dim, int64_t num_blocks, int64_t block_size,
+                                   int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                   int64_t cache_block_stride, int64_t cache_head_stride,
+                                   int64_t cache_token_stride, int64_t max_q_len_hint, int64_t max_kv_len_hint,
+                                   float softmax_scale, int layout_abab, int dtype, int scale_dtype,
+                                   void* workspace, int64_t workspace_bytes, int64_t local_window,
+                                   int64_t global_window, mojo_stream_t stream);
 
 /* ---- MoE routing either side of the grouped GEMM (core/operators/moe.py).
  *      gating (:299-316): softmax(hidden.float() @ gate_weight [hidden, E] fp32) over all experts, top-k in descending

@@ -56,7 +56,7 @@ def _paged_decode(op, what, symbols, query, key_cache, value_cache, total_seq_le
         caches, extra = (L.ptr(key_cache), L.ptr(value_cache)), windows
     else:
         caches = (L.ptr(key_cache), L.ptr(scales[0]), L.ptr(value_cache), L.ptr(scales[1]))
-        extra = (L.dtype_code(scales[0].dtype),)
+        extra = (L.dtype_code(scales[0].dtype), *windows)
     L.check(getattr(lib, symbols[1])(
         L.ptr(q), *caches, L.ptr(lens), L.ptr(tables), L.ptr(out), L.ptr(ws),
         ws.numel(), batch, hq, hkv, dim, page, tables.shape[1], tables.stride(0), key_cache.stride(0),

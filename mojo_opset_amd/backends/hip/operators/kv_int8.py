@@ -1,17 +1,19 @@
-"""HIP<Op> classes of the int8 paged KV cache with per-channel scales: the quantising store and the decode / prefill
-GQA that read it.  Everything that is not built raises ``NotImplementedError`` on the host, before any
+"""HIP<Op> classes of the int8 paged KV cache with per-channel scales: the quantising store, the decode / prefill
+GQA that read it and their sliding-window forms.  Everything that is not built raises ``NotImplementedError`` on the host, before any
 device work."""
 from typing import Optional
 
 import torch
 
-from ....core.operators.attention import (MojoPagedDecodeGQAWithKVDequant, MojoPagedPrefillGQAWithKVDequant,
+from ....core.operators.attention import (MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeSWAWithKVDequant,
+                                          MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillSWAWithKVDequant,
                                           assert_paged_decode_contract, assert_paged_prefill_contract)
 from ....core.operators.kv_cache import MojoStorePagedKVCacheC8, assert_paged_kv_layout_contract
 from .. import lib as L
-from .attention import _paged_decode, _paged_prefill
+from .attention import _paged_decode, _paged_prefill, _swa_windows
 
-__all__ = ["HIPStorePagedKVCacheC8", "HIPPagedDecodeGQAWithKVDequant", "HIPPagedPrefillGQAWithKVDequant"]
+__all__ = ["HIPStorePagedKVCacheC8", "HIPPagedDecodeGQAWithKVDequant", "HIPPagedPrefillGQAWithKVDequant",
+           "HIPPagedDecodeSWAWithKVDequant", "HIPPagedPrefillSWAWithKVDequant"]
 
 _ROCM = ["rocm"]
 _SCALE_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
@@ -19,6 +21,8 @@ _DECODE_DIMS = (64, 80, 96, 128)
 _PREFILL_DIMS = (64, 96, 128)
 _DECODE_KV8 = ("mojo_hip_paged_decode_gqa_kv8_workspace_bytes", "mojo_hip_paged_decode_gqa_kv8")
 _PREFILL_KV8 = ("mojo_hip_paged_prefill_gqa_kv8_workspace_bytes", "mojo_hip_paged_prefill_gqa_kv8")
+_DECODE_SWA_KV8 = ("mojo_hip_paged_decode_swa_kv8_workspace_bytes", "mojo_hip_paged_decode_swa_kv8")
+_PREFILL_SWA_KV8 = ("mojo_hip_paged_prefill_swa_kv8_workspace_bytes", "mojo_hip_paged_prefill_swa_kv8")
 
 
 def _dense(t):
@@ -147,3 +151,64 @@ class HIPPagedPrefillGQAWithKVDequant(MojoPagedPrefillGQAWithKVDequant):
         L.require_cuda(query, key_cache, value_cache, key_scale, value_scale, cu_q_lens, block_tables, cu_total_seq_lens)
         return _paged_prefill(self, what, _PREFILL_KV8, query, key_cache, value_cache, cu_q_lens, block_tables, softmax_scale,
                               cu_total_seq_lens, max_q_len, max_total_seq_len, scales=(_dense(key_scale), _dense(value_scale)))
+
+
+class HIPPagedDecodeSWAWithKVDequant(MojoPagedDecodeSWAWithKVDequant):
+    """Sliding-window paged decode over the int8 cache: `HIPPagedDecodeGQAWithKVDequant`'s kernel walking only the
+    16-token tiles of the global and local ranges.  Pages outside a row's visible set are never read: their
+    table entries may be -1 or any valid id.  With no window its entry point runs the unwindowed op, bit for bit."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, query_scale, key_cache, key_scale, value_cache, value_scale, total_seq_lens, block_table,
+                softmax_scale: Optional[float] = None, *, max_total_seq_len: Optional[int] = None,
+                leave_empty_rows: Optional[bool] = None):
+        what = "HIPPagedDecodeSWAWithKVDequant"
+        assert_paged_decode_contract(block_table, total_seq_lens)
+        _refuse_unbuilt(self, what, query, query_scale, None)
+        windows = _swa_windows(self, what)
+        batch, hq, dim = query.shape
+        n_blocks, hkv, page, dim_c = key_cache.shape
+        assert dim_c == dim and hq % hkv == 0
+        _check_int8_caches(what, key_cache, value_cache, key_scale, value_scale, hkv, dim)
+        if dim not in _DECODE_DIMS or page % 16 != 0 or not 1 <= hq // hkv <= 16:
+            raise NotImplementedError(f"{what}: head_dim {dim} / page {page} / group {hq // hkv} outside the envelope "
+                                      f"(head_dim {_DECODE_DIMS}, pages of a multiple of 16 tokens, groups of 1..16)")
+        if any(s % 16 for s in key_cache.stride()[:3]):
+            raise NotImplementedError(f"{what}: cache strides must be multiples of 16 bytes")
+        L.require_cuda(query, key_cache, value_cache, key_scale, value_scale, total_seq_lens, block_table)
+        return _paged_decode(self, what, _DECODE_SWA_KV8, query, key_cache, value_cache, total_seq_lens, block_table,
+                             softmax_scale, max_total_seq_len, leave_empty_rows,
+                             scales=(_dense(key_scale), _dense(value_scale)), windows=windows)
+
+
+class HIPPagedPrefillSWAWithKVDequant(MojoPagedPrefillSWAWithKVDequant):
+    """Sliding-window paged prefill over the int8 cache: the dequantising gather of the pages that intersect a sequence's
+    visible union — ``[0, global)`` and ``[kv_len - q_len - local, kv_len)`` — into a compact 16-bit scratch, then
+    `HIPPagedPrefillSWA`'s kernels on it.  The scratch holds ``ceil(global / page) + ceil((max_q_len +
+    local + 1) / page) + 2`` pages per sequence whatever the context (``max_q_len`` omitted: the token count);
+    ``max_q_len`` and ``max_total_seq_len``, when given, MUST be upper bounds (`HIPPagedPrefillGQAWithKVDequant`).  With a
+    window the pages must be a multiple of 16 tokens.  With no window its entry point runs the unwindowed op."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, query_scale, key_cache, key_scale, value_cache, value_scale, cu_q_lens, block_table,
+                softmax_scale: Optional[float] = None, cu_total_seq_lens: Optional[torch.Tensor] = None,
+                max_q_len: Optional[int] = None, max_total_seq_len: Optional[int] = None):
+        what = "HIPPagedPrefillSWAWithKVDequant"
+        assert_paged_prefill_contract(cu_q_lens, block_table, cu_total_seq_lens)
+        _refuse_unbuilt(self, what, query, query_scale, None)
+        windows = _swa_windows(self, what)
+        tokens, hq, dim = query.shape
+        n_blocks, hkv, page, dim_c = key_cache.shape
+        assert dim_c == dim and hq % hkv == 0
+        _check_int8_caches(what, key_cache, value_cache, key_scale, value_scale, hkv, dim)
+        windowed = windows[0] >= 0 or windows[1] > 0
+        if dim not in _PREFILL_DIMS or page % (16 if windowed else 4) != 0 or hq // hkv not in (1, 2, 4, 8):
+            raise NotImplementedError(f"{what}: head_dim {dim} / page {page} / group {hq // hkv} outside the envelope "
+                                      f"(head_dim {_PREFILL_DIMS}, pages of a multiple of 16 tokens — 4 without a window —, "
+                                      f"groups of 1, 2, 4, 8)")
+        if any(s % 16 for s in key_cache.stride()[:3]):
+            raise NotImplementedError(f"{what}: cache strides must be multiples of 16 bytes")
+        L.require_cuda(query, key_cache, value_cache, key_scale, value_scale, cu_q_lens, block_table, cu_total_seq_lens)
+        return _paged_prefill(self, what, _PREFILL_SWA_KV8, query, key_cache, value_cache, cu_q_lens, block_table,
+                              softmax_scale, cu_total_seq_lens, max_q_len, max_total_seq_len,
+                              scales=(_dense(key_scale), _dense(value_scale)), windows=windows)

@@ -6,6 +6,7 @@ from .operators import __all__ as _ops_all
 from .operators import EXTENDED_OPS, MojoPagedDecodeSWA, MojoPagedPrefillSWA  # noqa: F401  (beyond §8: not in __all__)
 from .operators import (KV_INT8_OPS, MojoPagedDecodeGQAWithKVDequant, MojoPagedPrefillGQAWithKVDequant,  # noqa: F401
                         MojoStorePagedKVCacheC8)
+from .operators import KV_INT8_SWA_OPS, MojoPagedDecodeSWAWithKVDequant, MojoPagedPrefillSWAWithKVDequant  # noqa: F401
 from .operators import QUANT_MOE_OPS, MojoMoEDynamicQuant, MojoQuantExperts, MojoQuantMoE  # noqa: F401
 from .operators import (SAMPLING_OPS, MojoApplyPenaltiesTempurate, MojoJoinProbRejectSampling, MojoRejectSampling,  # noqa: F401
                         MojoTopKSampling, MojoTopPFilter, MojoTopPSampling)

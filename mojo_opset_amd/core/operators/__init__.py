@@ -1,6 +1,7 @@
 from .activation import MojoSwiGLU
-from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeSWA, MojoPagedPrefillGQA,
-                        MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillSWA)
+from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeSWA,
+                        MojoPagedDecodeSWAWithKVDequant, MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
+                        MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
 from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
@@ -28,6 +29,9 @@ __all__ = [
 EXTENDED_OPS = ("MojoPagedDecodeSWA", "MojoPagedPrefillSWA")
 # The int8 paged KV cache with per-channel scales (the reference's experimental "C8" path): same standing as EXTENDED_OPS.
 KV_INT8_OPS = ("MojoStorePagedKVCacheC8", "MojoPagedDecodeGQAWithKVDequant", "MojoPagedPrefillGQAWithKVDequant")
+# Sliding-window attention over that int8 cache (the product of the two sets above): same standing; goldens in
+# tests/kv_int8_swa_golden.py.
+KV_INT8_SWA_OPS = ("MojoPagedDecodeSWAWithKVDequant", "MojoPagedPrefillSWAWithKVDequant")
 # W8A8 MoE experts (the reference's quantised MoE: per-expert smooth quantiser, int8 experts, the layer): same standing again;
 # goldens in tests/quant_moe_golden.py.
 QUANT_MOE_OPS = ("MojoMoEDynamicQuant", "MojoQuantExperts", "MojoQuantMoE")

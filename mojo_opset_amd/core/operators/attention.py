@@ -181,3 +181,54 @@ class MojoPagedPrefillGQAWithKVDequant(_PagedGQAKVDequantBase, MojoOperator):
                  context_dtype: torch.dtype = torch.int8, compute_dtype: torch.dtype = torch.bfloat16):
         super().__init__()
         self._init_kv_dequant(is_causal, gqa_layout, query_dtype, context_dtype, compute_dtype)
+
+
+class _PagedSWAKVDequantBase:
+    """Constructor of the windowed int8-cache pair (`mojo_opset/experimental/operators/attention.py:806-848`, :988-1030):
+    the attributes of `_PagedSWABase` and of `_PagedGQAKVDequantBase` together — ``is_causal``, ``gqa_layout``,
+    ``gqa_interleave``, ``global_window_size``, ``local_window_size``, ``query_dtype``, ``context_dtype``,
+    ``compute_dtype`` (and ``qmax`` / ``qmin`` with ``compute_dtype=torch.int8``)."""
+
+    def _init_swa_kv_dequant(self, is_causal, gqa_layout, global_window_size, local_window_size, query_dtype,
+                             context_dtype, compute_dtype) -> None:
+        _PagedSWABase._init_swa(self, is_causal, gqa_layout, global_window_size, local_window_size)
+        _PagedGQAKVDequantBase._init_kv_dequant(self, is_causal, gqa_layout, query_dtype, context_dtype, compute_dtype)
+
+    def extra_repr(self) -> str:
+        return (f"is_causal={self.is_causal!r}, gqa_layout={self.gqa_layout!r}, "
+                f"global_window_size={self.global_window_size!r}, local_window_size={self.local_window_size!r}, "
+                f"query_dtype={self.query_dtype!r}, context_dtype={self.context_dtype!r}, "
+                f"compute_dtype={self.compute_dtype!r}")
+
+
+class MojoPagedDecodeSWAWithKVDequant(_PagedSWAKVDequantBase, MojoOperator):
+    """`MojoPagedDecodeSWA` over an int8 K/V cache with per-channel scales (the visibility rule of `MojoPagedDecodeSWA`,
+    the cache of `MojoPagedDecodeGQAWithKVDequant`).
+
+    forward(query [B,Hq,D], query_scale (None: the query is not quantised), key_cache [N,Hkv,page,D] int8,
+            key_scale [Hkv,D], value_cache int8, value_scale [Hkv,D], total_seq_lens [B] i32, block_table [B,nb] i32,
+            softmax_scale=None, *, max_total_seq_len=None) -> [B,Hq,D]; rows of length 0 are zeros.
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,
+                 local_window_size: Optional[int] = None, query_dtype: torch.dtype = torch.bfloat16,
+                 context_dtype: torch.dtype = torch.int8, compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        self._init_swa_kv_dequant(is_causal, gqa_layout, global_window_size, local_window_size, query_dtype,
+                                  context_dtype, compute_dtype)
+
+
+class MojoPagedPrefillSWAWithKVDequant(_PagedSWAKVDequantBase, MojoOperator):
+    """`MojoPagedPrefillSWA` over an int8 K/V cache with per-channel scales.
+
+    forward(query [T,Hq,D], query_scale (None), key_cache int8, key_scale [Hkv,D], value_cache int8, value_scale [Hkv,D],
+            cu_q_lens [B+1] i32, block_table [B,nb] i32, softmax_scale=None, cu_total_seq_lens=None, max_q_len=None,
+            max_total_seq_len=None) -> [T,Hq,D]
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,
+                 local_window_size: Optional[int] = None, query_dtype: torch.dtype = torch.bfloat16,
+                 context_dtype: torch.dtype = torch.int8, compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        self._init_swa_kv_dequant(is_causal, gqa_layout, global_window_size, local_window_size, query_dtype,
+                                  context_dtype, compute_dtype)

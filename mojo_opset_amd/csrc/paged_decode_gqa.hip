@@ -641,7 +641,7 @@ static bool decode_use_mfma(int64_t G, int64_t head_dim, int64_t page) {
 struct DecodeGeom {
   int64_t batch = 0, q_heads = 0, kv_heads = 0, head_dim = 0, page = 0, max_pages = 0, len_hint = 0;
   int64_t local_window = -1, global_window = 0;
-  bool kv8 = false;                 // the int8-cache op (paged_decode_kv8.h): its own kernel, never grouped, halved or windowed
+  bool kv8 = false;                 // the int8-cache op (paged_decode_kv8.h): its own kernel, never grouped, paired or halved
 };
 
 struct DecodePlan {
@@ -658,7 +658,7 @@ struct DecodePlan {
 
 static DecodePlan decode_plan(const DecodeGeom& g) {
   DecodePlan p;
-  p.swa = !g.kv8 && (g.local_window >= 0 || g.global_window > 0);
+  p.swa = g.local_window >= 0 || g.global_window > 0;
   if (g.batch <= 0 || g.kv_heads <= 0 || g.q_heads <= 0) return p;
   p.capacity = decode_max_len(g.page, g.max_pages, g.len_hint);
   p.max_len = p.swa ? decode_swa_cap(p.capacity, g.local_window, g.global_window) : p.capacity;

@@ -22,6 +22,14 @@
 // V is loaded in whole rows (at head_dim 128 a load instruction moves eight 128-byte lines).  A step is 32 tokens
 // (two sub-tiles), three steps in flight.  Launch forms: FUSED (<= 8 chunks per row: one workgroup, merged in LDS) and
 // split + decode_merge_kernel; no paired and no grouped form.
+//
+// SWA (MojoPagedDecodeSWAWithKVDequant): the windowed instance walks the VIRTUAL key range of DecodeWin — the row length, the
+// chunking, both launch forms and the tail mask all run on it.  Each 16-token sub-tile of a step maps virtual -> real on its
+// own (g_al is a multiple of 16, not of the 32-token step: one step can hold the last global sub-tile and the first local
+// one); the sub-tiles holding g1 or lo get the per-key visibility mask on their scores.  Every sub-tile walked holds a
+// visible key, so only pages of the visible set are addressed: there is no hole scan, pages outside the window may be -1 or
+// recycled, and a negative id inside the visible set reads page 0 (as the 16-bit SWA op).  Invisible V rows are not zeroed:
+// int8 -> fp16 is always finite and their probabilities are exact zeros.
 #pragma once
 
 namespace mojo {
@@ -65,7 +73,7 @@ constexpr int KV8_STEP = 16 * KV8_NS;
 // floats of the partial area in front of the V images (rounded so that the images stay 16-byte aligned)
 __host__ __device__ constexpr int kv8_part_floats(int waves, int G, int D) { return (waves * G * (D + 2) + 3) & ~3; }
 
-template <int CPR /* head_dim / 16 */, bool NT, bool FUSED>
+template <int CPR /* head_dim / 16 */, bool NT, bool FUSED, bool SWA = false>
 __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   // (512 for the one-wave form too: two waves per SIMD)
   const DecodeArgs& a = ka.a;
   constexpr int D = CPR * 16, ND = CPR;
@@ -82,7 +90,10 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
   const int b = blockIdx.y / a.hkv;
   const int kvh = blockIdx.y % a.hkv;
 
-  const int seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;
+  DecodeWin win;                                        // (SWA only)
+  int seq_len = 0;                                      // SWA: the row's virtual length
+  if constexpr (SWA) seq_len = a.max_pages > 0 ? decode_swa_row(a, b, win) : 0;
+  else seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;
   const int chunk_tokens = decode_seq_chunk(a, seq_len);
   const int tok_begin = chunk * chunk_tokens;
   const bool has_work = seq_len > 0 && tok_begin < seq_len;
@@ -142,7 +153,7 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
       if (neg && first_neg == 0x7fffffff) first_neg = base + u * 64 + __builtin_ctzll(neg);
     }
   };
-  if (has_work) scan_issue(0);
+  if (!SWA && has_work) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
 
   const int vr = lane / CPR, vc = lane % CPR;           // V: row vr of a load instruction, piece vc of the row
   const bool v_lane = vr < RPI;
@@ -159,7 +170,7 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
     v_ok[u] = v_lane && row < 16;
     voff[u] = static_cast<int64_t>(min(row, 15)) * a.c_tok;
   }
-  const int last_tile = ((tok_end - 1) / 16) * 16;      // first token of the last non-empty sub-tile
+  const int last_tile = ((tok_end - 1) / 16) * 16;      // first token of the last non-empty sub-tile (SWA: virtual)
   const int last_page = a.max_pages - 1;
 
   struct Tile { u32x4 k[NS][NI]; u32x4 v[NS][NV]; int lp[NS]; };
@@ -171,7 +182,8 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
   auto load_tile = [&](Tile& t, int t0) {
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss) {
-      const int tu = min(t0 + 16 * ss, last_tile);      // wave-uniform
+      int tu = min(t0 + 16 * ss, last_tile);            // wave-uniform
+      if constexpr (SWA) tu = decode_swa_real(win, tu); // (16-aligned cuts: the sub-tile stays whole, in one page)
       const int lp = a.page_shift >= 0 ? (tu >> a.page_shift) : tu / a.page;
       t.lp[ss] = lp;
       const int phys = max(table[min(lp, last_page)], 0);
@@ -192,6 +204,7 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
   const unsigned r_base = v_u32 + (4 * g4 + (tl >> 2)) * VSTRIDE + (tl & 3) * 8;
 
   auto process = [&](Tile& t, int t0) {
+    if constexpr (!SWA) {
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss)
       if (t.lp[ss] >= first_neg) {                      // rare: pages behind a hole read as zeros
@@ -201,6 +214,7 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
 #pragma unroll
         for (int u = 0; u < NV; ++u) t.v[ss][u] = z;
       }
+    }
     const bool full = t0 + STEP <= tok_end;             // wave-uniform
     float x[NS][4];
 #pragma unroll
@@ -231,6 +245,17 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           if (!(t0 + 16 * ss + 4 * g4 + i < tok_end)) x[ss][i] = -INFINITY;
+    }
+    if constexpr (SWA) {                                // the sub-tiles holding g1 or lo: per-key visibility (real positions)
+#pragma unroll
+      for (int ss = 0; ss < NS; ++ss) {
+        const int rt0 = decode_swa_real(win, t0 + 16 * ss);
+        if (decode_swa_edge(win, rt0)) {                // wave-uniform
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (!decode_swa_vis(win, rt0 + 4 * g4 + i)) x[ss][i] = -INFINITY;
+        }
+      }
     }
     float mx = fmaxf(fmaxf(x[0][0], x[0][1]), fmaxf(x[0][2], x[0][3]));
 #pragma unroll
@@ -270,10 +295,12 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
   if (has_work) {
     load_tile(ta, tok_begin);
     if (tok_begin + STEP < tok_end) load_tile(tb, tok_begin + STEP);
-    scan_reduce(0);
-    for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
-      scan_issue(base);
-      scan_reduce(base);
+    if constexpr (!SWA) {
+      scan_reduce(0);
+      for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
+        scan_issue(base);
+        scan_reduce(base);
+      }
     }
     for (int t0 = tok_begin; t0 < tok_end; t0 += 3 * STEP) {
       if (t0 + 2 * STEP < tok_end) load_tile(tc, t0 + 2 * STEP);
@@ -350,39 +377,40 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
   }
 }
 
-template <int CPR, bool NT>
+template <int CPR, bool NT, bool SWA>
 static int launch_decode_kv8_cpr(const Kv8Args& ka, int64_t batch, int G, hipStream_t s) {
   const DecodeArgs& a = ka.a;
   constexpr int D = CPR * 16;
   constexpr size_t IMG = static_cast<size_t>(KV8_NS) * 16 * (D * 2 + 32);
   const char* nt_tag = NT ? "nt" : "cached";
+  const char* swa_tag = SWA ? ":swa" : "";
   const unsigned rows = static_cast<unsigned>(batch * a.hkv);
   if (a.n_chunks <= 8 && MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) != 0) {
     const size_t lds = static_cast<size_t>(kv8_part_floats(a.n_chunks, G, D)) * sizeof(float) + a.n_chunks * IMG;
     static std::atomic<uint64_t> attr_set{0};           // (per instantiation: dynamic LDS beyond 64 KiB needs the attribute)
     if (first_call_on_device(attr_set))
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_kv8_kernel<CPR, NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((decode_kv8_kernel<CPR, NT, true>), dim3(1, rows), dim3(static_cast<unsigned>(64 * a.n_chunks)), lds, s, ka, G);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_kv8_kernel<CPR, NT, true, SWA>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL((decode_kv8_kernel<CPR, NT, true, SWA>), dim3(1, rows), dim3(static_cast<unsigned>(64 * a.n_chunks)), lds, s, ka, G);
     MOJO_CHECK_LAUNCH("paged_decode_gqa_kv8(fused)");
-    note_launch("decode_mfma:fused:%s:kv8", nt_tag);
+    note_launch("decode_mfma:fused:%s:kv8%s", nt_tag, swa_tag);
     return MOJO_OK;
   }
-  hipLaunchKernelGGL((decode_kv8_kernel<CPR, NT, false>), dim3(static_cast<unsigned>(a.n_chunks), rows), dim3(64), IMG, s, ka, G);
+  hipLaunchKernelGGL((decode_kv8_kernel<CPR, NT, false, SWA>), dim3(static_cast<unsigned>(a.n_chunks), rows), dim3(64), IMG, s, ka, G);
   MOJO_CHECK_LAUNCH("paged_decode_gqa_kv8(split)");
-  if (ka.q_bf16) hipLaunchKernelGGL((decode_merge_kernel<bf16_t, false>), dim3(rows, G), dim3(256), 0, s, a, G);
-  else hipLaunchKernelGGL((decode_merge_kernel<f16_t, false>), dim3(rows, G), dim3(256), 0, s, a, G);
+  if (ka.q_bf16) hipLaunchKernelGGL((decode_merge_kernel<bf16_t, SWA>), dim3(rows, G), dim3(256), 0, s, a, G);
+  else hipLaunchKernelGGL((decode_merge_kernel<f16_t, SWA>), dim3(rows, G), dim3(256), 0, s, a, G);
   MOJO_CHECK_LAUNCH("paged_decode_gqa_kv8(merge)");
-  note_launch("decode_mfma:split+merge:%s:kv8", nt_tag);
+  note_launch("decode_mfma:split+merge:%s:kv8%s", nt_tag, swa_tag);
   return MOJO_OK;
 }
 
-template <bool NT>
+template <bool NT, bool SWA>
 static int launch_decode_kv8(const Kv8Args& ka, int64_t batch, int G, hipStream_t s) {
   switch (ka.a.dim) {
-    case 64: return launch_decode_kv8_cpr<4, NT>(ka, batch, G, s);
-    case 80: return launch_decode_kv8_cpr<5, NT>(ka, batch, G, s);
-    case 96: return launch_decode_kv8_cpr<6, NT>(ka, batch, G, s);
-    case 128: return launch_decode_kv8_cpr<8, NT>(ka, batch, G, s);
+    case 64: return launch_decode_kv8_cpr<4, NT, SWA>(ka, batch, G, s);
+    case 80: return launch_decode_kv8_cpr<5, NT, SWA>(ka, batch, G, s);
+    case 96: return launch_decode_kv8_cpr<6, NT, SWA>(ka, batch, G, s);
+    case 128: return launch_decode_kv8_cpr<8, NT, SWA>(ka, batch, G, s);
     default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: head_dim %d (supported: 64, 80, 96, 128)", ka.a.dim);
   }
   return MOJO_OK;
@@ -390,22 +418,15 @@ static int launch_decode_kv8(const Kv8Args& ka, int64_t batch, int G, hipStream_
 
 }  // namespace mojo
 
-extern "C" int64_t mojo_hip_paged_decode_gqa_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
-                                                                 int64_t head_dim, int64_t block_size,
-                                                                 int64_t max_blocks_per_seq, int64_t max_seq_len_hint) {
-  return mojo::decode_plan({batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, -1, 0, /*kv8=*/true}).query_bytes;
-}
-
-extern "C" int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
-                                             const void* value_cache, const void* value_scale,
-                                             const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
-                                             void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
-                                             int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                                             int64_t max_blocks_per_seq, int64_t block_table_stride,
-                                             int64_t cache_block_stride, int64_t cache_head_stride,
-                                             int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
-                                             int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
-                                             mojo_stream_t stream) {
+// The int8-cache entry points share one body: a window (local >= 0 or global > 0) selects the windowed instances, planned on
+// the visible capacity (decode_swa_cap); none runs the unwindowed op, whichever entry point was called.
+static int paged_decode_kv8(const void* query, const void* key_cache, const void* key_scale, const void* value_cache,
+                            const void* value_scale, const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                            void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads, int64_t kv_heads,
+                            int64_t head_dim, int64_t block_size, int64_t max_blocks_per_seq, int64_t block_table_stride,
+                            int64_t cache_block_stride, int64_t cache_head_stride, int64_t cache_token_stride,
+                            int64_t max_seq_len_hint, float softmax_scale, int layout_abab, int leave_empty_rows, int dtype,
+                            int scale_dtype, int64_t local_window, int64_t global_window, mojo_stream_t stream) {
   using namespace mojo;
   if (batch == 0) return MOJO_OK;
   MOJO_REQUIRE(query && key_cache && value_cache && key_scale && value_scale && total_seq_lens && block_tables && out, MOJO_EINVAL,
@@ -430,14 +451,69 @@ extern "C" int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_
   DecodeCall c;
   c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
   c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
-  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, -1, 0, /*kv8=*/true};
+  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window, global_window, /*kv8=*/true};
   c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
   c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
   c.leave_empty_rows = leave_empty_rows;
   const DecodePlan p = decode_plan(c.g);
   Kv8Args ka{};
+  if (p.swa) {
+    MOJO_REQUIRE(p.capacity < (int64_t{1} << 30) && local_window < (int64_t{1} << 30) && global_window < (int64_t{1} << 30),
+                 MOJO_EUNSUPPORTED, "paged_decode_swa_kv8: lengths and windows must stay below 2^30");
+    ka.a.swa_cap = static_cast<int>(p.capacity);
+    ka.a.local_win = local_window >= 0 ? static_cast<int>(local_window) : -1;
+    ka.a.global_win = global_window > 0 ? static_cast<int>(global_window) : 0;
+  }
   if (const int rc = decode_fill_args(ka.a, c, p, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
   ka.kscale = key_scale; ka.vscale = value_scale; ka.scale_dtype = scale_dtype; ka.q_bf16 = dtype == MOJO_BF16 ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0 ? launch_decode_kv8<true>(ka, batch, p.G, s) : launch_decode_kv8<false>(ka, batch, p.G, s);
+  const bool nt = MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0;
+  if (p.swa) return nt ? launch_decode_kv8<true, true>(ka, batch, p.G, s) : launch_decode_kv8<false, true>(ka, batch, p.G, s);
+  return nt ? launch_decode_kv8<true, false>(ka, batch, p.G, s) : launch_decode_kv8<false, false>(ka, batch, p.G, s);
+}
+
+extern "C" int64_t mojo_hip_paged_decode_gqa_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                                 int64_t head_dim, int64_t block_size,
+                                                                 int64_t max_blocks_per_seq, int64_t max_seq_len_hint) {
+  return mojo::decode_plan({batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, -1, 0, /*kv8=*/true}).query_bytes;
+}
+
+extern "C" int64_t mojo_hip_paged_decode_swa_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                                 int64_t head_dim, int64_t block_size,
+                                                                 int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                                 int64_t local_window, int64_t global_window) {
+  return mojo::decode_plan({batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window,
+                            global_window, /*kv8=*/true}).query_bytes;
+}
+
+extern "C" int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                             const void* value_cache, const void* value_scale,
+                                             const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                             void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                             int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                             int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                             int64_t cache_block_stride, int64_t cache_head_stride,
+                                             int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                             int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
+                                             mojo_stream_t stream) {
+  return paged_decode_kv8(query, key_cache, key_scale, value_cache, value_scale, total_seq_lens, block_tables, out, workspace,
+                          workspace_bytes, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                          cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale, layout_abab,
+                          leave_empty_rows, dtype, scale_dtype, -1, 0, stream);
+}
+
+extern "C" int mojo_hip_paged_decode_swa_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                             const void* value_cache, const void* value_scale,
+                                             const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                             void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                             int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                             int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                             int64_t cache_block_stride, int64_t cache_head_stride,
+                                             int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                             int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
+                                             int64_t local_window, int64_t global_window, mojo_stream_t stream) {
+  return paged_decode_kv8(query, key_cache, key_scale, value_cache, value_scale, total_seq_lens, block_tables, out, workspace,
+                          workspace_bytes, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                          cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale, layout_abab,
+                          leave_empty_rows, dtype, scale_dtype, local_window, global_window, stream);
 }
