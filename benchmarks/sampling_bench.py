@@ -1,7 +1,7 @@
 """Sampling benchmark (standalone; not part of bench.py): python benchmarks/sampling_bench.py
 
 The hip operators next to the same composition of torch operators on the device — the golden module
-(tests/sampling_golden.py) on GPU tensors, which is what an accelerated backend without a selection kernel runs: a sort of the
+(oracle/sampling.py) on GPU tensors, which is what an accelerated backend without a selection kernel runs: a sort of the
 whole row, two softmaxes, a cumulative sum, a multinomial draw.  The two legs are alternated in one process, five medians per
 leg (their spread is reported):
 
@@ -23,8 +23,8 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import sampling_golden as G  # noqa: E402
+sys.path.insert(0, ROOT)
+import oracle.sampling as G  # noqa: E402
 from benchmarks.extras import HBM_PEAK_GBS, _time, _time_graph, _want, hip  # noqa: E402
 
 LEGS = 5

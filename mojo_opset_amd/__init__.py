@@ -5,29 +5,19 @@ registers the ``HIP<Op>`` backend classes.  Backend selection follows the refere
 ``MOJO_BACKEND`` is read at every construction; on a ROCm host the priority is
 ``["hip", "torch"]``.  The package contains no CPU compute path.
 
-``__all__`` is the SURVEY §8 set, whose torch goldens live in the repo-level ``oracle/`` package.  Ops beyond §8
-(``EXTENDED_OPS``: the sliding-window pair ``MojoPagedDecodeSWA`` / ``MojoPagedPrefillSWA``) are package attributes
-too, but not in ``__all__``; their goldens are test infrastructure under ``tests/`` (``tests/swa_golden.py``).
-So are the ops of the int8 paged KV cache (``KV_INT8_OPS``: ``MojoStorePagedKVCacheC8``,
-``MojoPagedDecodeGQAWithKVDequant``, ``MojoPagedPrefillGQAWithKVDequant``; goldens in ``tests/kv_int8_golden.py``).
-And sliding-window attention over that cache (``KV_INT8_SWA_OPS``: ``MojoPagedDecodeSWAWithKVDequant``,
-``MojoPagedPrefillSWAWithKVDequant``; goldens in ``tests/kv_int8_swa_golden.py``).
-And the W8A8 MoE experts (``QUANT_MOE_OPS``: ``MojoMoEDynamicQuant``, ``MojoQuantExperts``, ``MojoQuantMoE``; goldens in
-``tests/quant_moe_golden.py``).  And the sampling step (``SAMPLING_OPS``: ``MojoTopKSampling``, ``MojoTopPSampling``,
-``MojoTopPFilter``, ``MojoRejectSampling``, ``MojoJoinProbRejectSampling``, ``MojoApplyPenaltiesTempurate``; goldens in
-``tests/sampling_golden.py``).  ``plugin.rebase_hip_backend`` registers all six sets into the reference.
+``__all__`` is the SURVEY §8 set.  The ops beyond it (``BEYOND_SURVEY_OPS``, the concatenation of the named sets of
+``core/operators/__init__.py``) are package attributes too, but not in ``__all__``; ``plugin.rebase_hip_backend``
+registers both into the reference.  The torch golden of every op, in ``__all__`` or not, is in the repo-level ``oracle/``
+package.
 """
 from .core import *  # noqa: F401,F403
 from .core import __all__ as _core_all
-from .core import EXTENDED_OPS, MojoPagedDecodeSWA, MojoPagedPrefillSWA  # noqa: F401
-from .core import (KV_INT8_OPS, MojoPagedDecodeGQAWithKVDequant, MojoPagedPrefillGQAWithKVDequant,  # noqa: F401
-                   MojoStorePagedKVCacheC8)
-from .core import KV_INT8_SWA_OPS, MojoPagedDecodeSWAWithKVDequant, MojoPagedPrefillSWAWithKVDequant  # noqa: F401
-from .core import QUANT_MOE_OPS, MojoMoEDynamicQuant, MojoQuantExperts, MojoQuantMoE  # noqa: F401
-from .core import (SAMPLING_OPS, MojoApplyPenaltiesTempurate, MojoJoinProbRejectSampling, MojoRejectSampling,  # noqa: F401
-                   MojoTopKSampling, MojoTopPFilter, MojoTopPSampling)
+from .core import (BEYOND_SURVEY_OPS, EXTENDED_OPS, KV_INT8_OPS, KV_INT8_SWA_OPS, QUANT_MOE_OPS,  # noqa: F401
+                   SAMPLING_OPS)
+from . import core as _core
 from . import backends  # noqa: F401  (registers HIP<Op> classes)
 from .paged_cache import PagedDummyCache  # noqa: E402  device-side block allocator (SURVEY §8 f4)
 
 __all__ = list(_core_all) + ["PagedDummyCache"]
+globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS})   # beyond §8: not in __all__
 __version__ = "0.1.0"

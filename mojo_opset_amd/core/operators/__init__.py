@@ -24,18 +24,16 @@ __all__ = [
     "MojoGemm", "MojoSwiGLUMLP",
 ]
 
-# Ops beyond the SURVEY §8 set: importable, but not in `__all__` (whose goldens live in the repo-level `oracle/`); their
-# goldens are test infrastructure under `tests/`.
-EXTENDED_OPS = ("MojoPagedDecodeSWA", "MojoPagedPrefillSWA")
-# The int8 paged KV cache with per-channel scales (the reference's experimental "C8" path): same standing as EXTENDED_OPS.
+# Ops beyond the SURVEY §8 set: attributes of the package, but not in `__all__`.  Their torch goldens are in `oracle/`, like
+# those of `__all__`.  A new set gets a tuple of its own here and joins BEYOND_SURVEY_OPS, which is what the packages above
+# re-export and what the plugin registers.
+EXTENDED_OPS = ("MojoPagedDecodeSWA", "MojoPagedPrefillSWA")                        # sliding-window attention
+# the int8 paged KV cache with per-channel scales (the reference's experimental "C8" path)
 KV_INT8_OPS = ("MojoStorePagedKVCacheC8", "MojoPagedDecodeGQAWithKVDequant", "MojoPagedPrefillGQAWithKVDequant")
-# Sliding-window attention over that int8 cache (the product of the two sets above): same standing; goldens in
-# tests/kv_int8_swa_golden.py.
-KV_INT8_SWA_OPS = ("MojoPagedDecodeSWAWithKVDequant", "MojoPagedPrefillSWAWithKVDequant")
-# W8A8 MoE experts (the reference's quantised MoE: per-expert smooth quantiser, int8 experts, the layer): same standing again;
-# goldens in tests/quant_moe_golden.py.
+KV_INT8_SWA_OPS = ("MojoPagedDecodeSWAWithKVDequant", "MojoPagedPrefillSWAWithKVDequant")   # the product of the two above
+# W8A8 MoE experts: per-expert smooth quantiser, int8 experts, the layer
 QUANT_MOE_OPS = ("MojoMoEDynamicQuant", "MojoQuantExperts", "MojoQuantMoE")
-# The sampling step (top-k / top-p over the vocabulary, speculative acceptance, penalties): same standing once more; goldens
-# in tests/sampling_golden.py.
+# the sampling step: top-k / top-p over the vocabulary, speculative acceptance, penalties
 SAMPLING_OPS = ("MojoTopKSampling", "MojoTopPSampling", "MojoTopPFilter", "MojoRejectSampling", "MojoJoinProbRejectSampling",
                 "MojoApplyPenaltiesTempurate")
+BEYOND_SURVEY_OPS = EXTENDED_OPS + KV_INT8_OPS + KV_INT8_SWA_OPS + QUANT_MOE_OPS + SAMPLING_OPS

@@ -2,7 +2,7 @@
 
 Follows `mojo_opset/core/operators/sampling.py`: `MojoTopKSampling` (:12-71), `MojoTopPSampling` (:74-144), `MojoTopPFilter`
 (:147-206), `MojoRejectSampling` (:209-253), `MojoJoinProbRejectSampling` (:256-307), `MojoApplyPenaltiesTempurate`
-(:310-361).  Constructors, call contracts and ``extra_repr`` only; the torch goldens are `tests/sampling_golden.py`, the
+(:310-361).  Constructors, call contracts and ``extra_repr`` only; the torch goldens are `oracle/sampling.py`, the
 kernels `csrc/sampling.hip`.
 
 Shared semantics (all in fp32 on ``logits.float()``):

@@ -1,9 +1,8 @@
 """Torch goldens of the int8 paged KV cache ops (`MojoStorePagedKVCacheC8`, `MojoPagedDecodeGQAWithKVDequant`,
 `MojoPagedPrefillGQAWithKVDequant`).
 
-Ops beyond the SURVEY §8 set carry their goldens here, in the tests.  Importing this module registers
-``TorchStorePagedKVCacheC8`` / ``TorchPagedDecodeGQAWithKVDequant`` / ``TorchPagedPrefillGQAWithKVDequant`` as the
-``torch`` backends of the three API classes.
+Importing this module registers ``TorchStorePagedKVCacheC8`` / ``TorchPagedDecodeGQAWithKVDequant`` /
+``TorchPagedPrefillGQAWithKVDequant`` as the ``torch`` backends of the three API classes.
 
 Semantics and rounding points restate `mojo_opset/experimental/operators/kv_cache.py:109-184` (store: the quotient
 ``state / scale`` under torch's type promotion, ``round``, clamp to [-128, 127], int8; plan rows written page by page)
@@ -11,8 +10,8 @@ and `mojo_opset/experimental/operators/attention.py:461-632` (prefill), :635-800
 ``compute_dtype=bfloat16`` keys and values are dequantised in fp32 (``K8 * key_scale``), scores are an fp32 matmul times
 the softmax scale, the softmax runs in fp32 and its probabilities are rounded to the query dtype before the fp32 product
 with the values.  With ``compute_dtype=int8`` the scaled query and the probabilities are quantised per row (amax / 127,
-clamped to 1e-5) and both products are integer-valued fp32 matmuls.  Pages are gathered by plain indexing of the table.
-`tests/golden/paged_kv_int8_*.pt` pin these classes bit for bit.
+clamped to 1e-5) and both products are integer-valued fp32 matmuls.  Pages are gathered by plain indexing of the table
+(`paged.index_pages`).  `tests/golden/paged_kv_int8_*.pt` pin these classes bit for bit.
 """
 import math
 from typing import Optional
@@ -21,6 +20,8 @@ import torch
 
 from mojo_opset_amd.core.operators import attention as _attn
 from mojo_opset_amd.core.operators import kv_cache as _kv
+
+from .paged import expand_kv_heads, index_pages
 
 _CPU = ["rocm", "cpu"]
 
@@ -34,7 +35,7 @@ def quantize_kv_cache(cache: torch.Tensor):
     return quant, scale.to(torch.bfloat16)
 
 
-def _row_quantize(x: torch.Tensor, qmax: int, qmin: int):
+def row_quantize(x: torch.Tensor, qmax: int, qmin: int):
     """Dynamic per-row symmetric quantisation (reference :450-459), in the dtype of ``x`` (bf16 for a bf16 query times a
     bf16 scale and for the probabilities): scale = amax / qmax with amax clamped to 1e-12, a scale below 1e-6 becomes 1."""
     scale = x.abs().amax(dim=-1, keepdim=True).clamp(min=1e-12) / qmax
@@ -43,24 +44,10 @@ def _row_quantize(x: torch.Tensor, qmax: int, qmin: int):
     return q, scale.view(*x.shape[:-1], 1)
 
 
-def _pages(cache, table_row, kv_len):
-    n_kv, page, dim = cache.shape[1], cache.shape[2], cache.shape[3]
-    blocks = (kv_len + page - 1) // page
-    x = cache[table_row[:blocks]]
-    return x.permute(1, 0, 2, 3).reshape(n_kv, blocks * page, dim)[:, :kv_len]
-
-
-def _expand(x, group, interleave):
-    if group == 1:
-        return x
-    reps = (group,) + (1,) * (x.dim() - 1)
-    return x.repeat(reps) if interleave else x.repeat_interleave(group, dim=0)
-
-
 def _attend(op, q, k8, v8, key_scale, value_scale, softmax_scale, mask_rows):
     """q [Hq, Lq, D], k8 / v8 [Hq, Lk, D] int8 (already expanded), scales [Hq, D] -> [Hq, Lq, D] fp32."""
     if op.compute_dtype == torch.int8:
-        q_quant, q_scale = _row_quantize(q * key_scale.unsqueeze(1), op.qmax, op.qmin)
+        q_quant, q_scale = row_quantize(q * key_scale.unsqueeze(1), op.qmax, op.qmin)
         scores = torch.matmul(q_quant.float(), k8.mT.float()) * q_scale * softmax_scale
     else:
         scores = torch.matmul(q.float(), (k8.float() * key_scale.unsqueeze(1).float()).mT) * softmax_scale
@@ -68,12 +55,12 @@ def _attend(op, q, k8, v8, key_scale, value_scale, softmax_scale, mask_rows):
         scores = torch.where(mask_rows, scores, float("-inf"))
     probs = torch.softmax(scores, dim=-1, dtype=torch.float32).to(q.dtype)
     if op.compute_dtype == torch.int8:
-        p_quant, p_scale = _row_quantize(probs, op.qmax, op.qmin)
+        p_quant, p_scale = row_quantize(probs, op.qmax, op.qmin)
         return torch.matmul(p_quant.float(), v8.float()) * p_scale * value_scale.unsqueeze(1)
     return torch.matmul(probs.float(), v8.float() * value_scale.unsqueeze(1).float())
 
 
-def _check_query(op, query, query_scale):
+def check_query(op, query, query_scale):
     if op.query_dtype == torch.int8:
         assert query_scale is not None and query.dtype == op.query_dtype, "query_scale must be provided for quantized query"
     else:
@@ -108,18 +95,18 @@ class TorchPagedDecodeGQAWithKVDequant(_attn.MojoPagedDecodeGQAWithKVDequant):
                 softmax_scale: Optional[float] = None, mask: Optional[torch.Tensor] = None, *,
                 max_total_seq_len: Optional[int] = None):
         _attn.assert_paged_decode_contract(block_tables, total_seq_lens)
-        _check_query(self, query, query_scale)
+        check_query(self, query, query_scale)
         batch, hq, dim = query.shape
         hkv = key_cache.shape[1]
-        group, interleave = hq // hkv, self.gqa_layout == "ABAB"
+        group, layout = hq // hkv, self.gqa_layout
         scale = 1.0 / math.sqrt(dim) if softmax_scale is None else softmax_scale
-        ks, vs = _expand(key_scale, group, interleave), _expand(value_scale, group, interleave)
+        ks, vs = expand_kv_heads(key_scale, group, layout), expand_kv_heads(value_scale, group, layout)
         out = torch.zeros(batch, hq, dim, dtype=query.dtype, device=query.device)
         for b, kv_len in enumerate(total_seq_lens.tolist()):
             if kv_len == 0:
                 continue
-            k8 = _expand(_pages(key_cache, block_tables[b], kv_len), group, interleave)
-            v8 = _expand(_pages(value_cache, block_tables[b], kv_len), group, interleave)
+            k8 = expand_kv_heads(index_pages(key_cache, block_tables[b], kv_len), group, layout)
+            v8 = expand_kv_heads(index_pages(value_cache, block_tables[b], kv_len), group, layout)
             rows = None
             if not self.is_causal and mask is not None:
                 rows = (mask if mask.dim() == 2 else mask[b])[kv_len, :kv_len]
@@ -135,20 +122,20 @@ class TorchPagedPrefillGQAWithKVDequant(_attn.MojoPagedPrefillGQAWithKVDequant):
                 mask: Optional[torch.Tensor] = None, max_q_len: Optional[int] = None,
                 max_total_seq_len: Optional[int] = None):
         _attn.assert_paged_prefill_contract(cu_q_lens, block_tables, cu_total_seq_lens)
-        _check_query(self, query, query_scale)
+        check_query(self, query, query_scale)
         tokens, hq, dim = query.shape
         hkv = key_cache.shape[1]
-        group, interleave = hq // hkv, self.gqa_layout == "ABAB"
+        group, layout = hq // hkv, self.gqa_layout
         scale = 1.0 / math.sqrt(dim) if softmax_scale is None else softmax_scale
-        ks, vs = _expand(key_scale, group, interleave), _expand(value_scale, group, interleave)
+        ks, vs = expand_kv_heads(key_scale, group, layout), expand_kv_heads(value_scale, group, layout)
         cu_q = cu_q_lens.tolist()
         cu_kv = cu_q if cu_total_seq_lens is None else cu_total_seq_lens.tolist()
         out = torch.zeros(tokens, hq, dim, dtype=query.dtype, device=query.device)
         for b in range(len(cu_q) - 1):
             lo, hi = cu_q[b], cu_q[b + 1]
             q_len, kv_len = hi - lo, cu_kv[b + 1] - cu_kv[b]
-            k8 = _expand(_pages(key_cache, block_tables[b], kv_len), group, interleave)
-            v8 = _expand(_pages(value_cache, block_tables[b], kv_len), group, interleave)
+            k8 = expand_kv_heads(index_pages(key_cache, block_tables[b], kv_len), group, layout)
+            v8 = expand_kv_heads(index_pages(value_cache, block_tables[b], kv_len), group, layout)
             rows = None
             if self.is_causal:
                 rows = torch.ones(q_len, kv_len, dtype=torch.bool, device=query.device).tril(kv_len - q_len)

@@ -1,12 +1,12 @@
 """Write tests/golden/paged_kv_int8_store.pt, _decode.pt and _prefill.pt: reference outputs of the int8 paged KV cache
 ops (authoring machine only).
 
-Usage: python scripts/make_kv_int8_golden.py /path/to/mojo_opset   (a checkout of the reference; nothing else reads it)
+Usage: python oracle/make_kv_int8_golden.py [reference root]   (default: MOJO_REFERENCE_ROOT, else /root/reference; nothing else reads it)
 
 The outputs come from the reference's own `MojoStorePagedKVCacheC8.forward`
 (`mojo_opset/experimental/operators/kv_cache.py:109-184`), `MojoPagedDecodeGQAWithKVDequant.forward` and
 `MojoPagedPrefillGQAWithKVDequant.forward` (`experimental/operators/attention.py:461-800`), called on CPU.  Each case
-records the constructor keywords, the inputs and the output; tests/test_kv_int8_golden.py pins tests/kv_int8_golden.py
+records the constructor keywords, the inputs and the output; tests/test_kv_int8_golden.py pins oracle/kv_int8.py
 to them bit for bit and tests/test_hip_kv_int8.py runs the hip backend on them.
 """
 import os
@@ -16,18 +16,10 @@ import types
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
-
-def cu(lens):
-    return torch.tensor([0] + list(torch.tensor(lens).cumsum(0).tolist()), dtype=torch.int32)
-
-
-def quantize_kv_cache(cache):
-    """The reference tests' recipe (tests/accuracy/operators/test_attention_quant.py:46-67)."""
-    cache_f = cache.float()
-    scale = (cache_f.abs().amax(dim=(0, 2)) / 127).clamp(min=1e-5)
-    quant = torch.round(cache_f / scale.unsqueeze(0).unsqueeze(2)).clamp(-128, 127).to(torch.int8)
-    return quant, scale.to(torch.bfloat16)
+from oracle.kv_int8 import quantize_kv_cache  # noqa: E402  (the reference tests' recipe, test_attention_quant.py:46-67)
+from oracle.paged import cu  # noqa: E402
 
 
 def paged_inputs(g, batch, hq, hkv, d, kv_lens, page, q_rows):
@@ -135,4 +127,4 @@ def main(reference_root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_OPSET_REFERENCE", "."))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_REFERENCE_ROOT", "/root/reference"))

@@ -1,12 +1,12 @@
 """Write tests/golden/paged_kv_int8_swa_decode.pt and _prefill.pt: reference outputs of sliding-window attention over the
 int8 paged KV cache (authoring machine only).
 
-Usage: python scripts/make_kv_int8_swa_golden.py /path/to/mojo_opset   (a checkout of the reference; nothing else reads it)
+Usage: python oracle/make_kv_int8_swa_golden.py [reference root]   (default: MOJO_REFERENCE_ROOT, else /root/reference; nothing else reads it)
 
 The outputs come from the reference's own `MojoPagedDecodeSWAWithKVDequant.forward` and
 `MojoPagedPrefillSWAWithKVDequant.forward` (`experimental/operators/attention.py:803-1151`), called on CPU.  Each case
 records the constructor keywords, the inputs and the output; tests/test_kv_int8_swa_golden.py pins
-tests/kv_int8_swa_golden.py to them bit for bit and tests/test_hip_kv_int8_swa.py runs the hip backend on them.  Two files:
+oracle/kv_int8_swa.py to them bit for bit and tests/test_hip_kv_int8_swa.py runs the hip backend on them.  Two files:
 all twelve cases in one exceed the size bound of a committed file.
 """
 import os
@@ -15,7 +15,11 @@ import types
 
 import torch
 
-from make_kv_int8_golden import ROOT, cu, paged_inputs
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from oracle.make_kv_int8_golden import paged_inputs  # noqa: E402
+from oracle.paged import cu  # noqa: E402
 
 BF16, INT8 = torch.bfloat16, torch.int8
 
@@ -73,4 +77,4 @@ def main(reference_root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_OPSET_REFERENCE", "."))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_REFERENCE_ROOT", "/root/reference"))

@@ -1,11 +1,11 @@
 """Write tests/golden/quant_moe.pt: reference outputs of the W8A8 MoE ops (authoring machine only).
 
-Usage: python scripts/make_quant_moe_golden.py /path/to/mojo_opset   (a checkout of the reference; nothing else reads it)
+Usage: python oracle/make_quant_moe_golden.py [reference root]   (default: MOJO_REFERENCE_ROOT, else /root/reference; nothing else reads it)
 
 The outputs come from the reference's own ``torch`` backends of `MojoMoEDynamicQuant`
 (`mojo_opset/core/operators/quantize.py:178-247`), `MojoQuantExperts` (`core/operators/moe.py:452-667`) and `MojoQuantMoE`
 (`:132-274`), built on CPU and loaded with the recorded state.  Each case records the constructor keywords, the state, the
-inputs and the output; tests/test_quant_moe_golden.py pins tests/quant_moe_golden.py to them bit for bit (both forms of
+inputs and the output; tests/test_quant_moe_golden.py pins oracle/quant_moe.py to them bit for bit (both forms of
 the integer product) and tests/test_hip_quant_moe.py runs the hip backend on them.
 
 The int8 expert weights dominate the file, so every int8 case uses ONE weight set (E 4, H 128, I 192; torch.save stores a
@@ -17,7 +17,9 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+sys.path.insert(0, ROOT)
+
+from oracle.quant_moe import pack_int4  # noqa: E402
 
 E, H, I = 4, 128, 192
 
@@ -44,8 +46,6 @@ def ep_counts(g, experts, tokens, top_k, dtype):
 def main(reference_root):
     sys.path.insert(0, reference_root)
     import mojo_opset as ref
-
-    from quant_moe_golden import pack_int4
 
     g = torch.Generator().manual_seed(2031)
     up8, up_s = quantize_rows(torch.randn(E, 2 * I, H, generator=g) * 0.1, 127)
@@ -107,4 +107,4 @@ def main(reference_root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_OPSET_REFERENCE", "."))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_REFERENCE_ROOT", "/root/reference"))

@@ -1,10 +1,10 @@
 """Write tests/golden/sampling.pt: reference outputs of the sampling ops (authoring machine only).
 
-Usage: python scripts/make_sampling_golden.py /path/to/mojo_opset   (a checkout of the reference; nothing else reads it)
+Usage: python oracle/make_sampling_golden.py [reference root]   (default: MOJO_REFERENCE_ROOT, else /root/reference; nothing else reads it)
 
 The outputs come from the reference's own ``torch`` backends of the six classes of `mojo_opset/core/operators/sampling.py`,
 built on CPU.  Each case records the constructor keywords, the inputs and the output; tests/test_sampling_golden.py pins
-tests/sampling_golden.py to them bit for bit and tests/test_hip_sampling.py runs the hip backend on them.
+oracle/sampling.py to them bit for bit and tests/test_hip_sampling.py runs the hip backend on them.
 
 * The reference selects with ``torch.topk``, which leaves the order among equal values open, so every recorded top-k input is
   asserted tie-free in its top K + 1: the recorded indices are then unambiguous.  The 16-bit rows are permutations of distinct
@@ -19,7 +19,6 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 NEG_INF = -float("inf")
 
@@ -154,4 +153,4 @@ def main(reference_root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_OPSET_REFERENCE", "."))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_REFERENCE_ROOT", "/root/reference"))

@@ -1,10 +1,10 @@
 """Write tests/golden/paged_swa.pt (decode) and paged_swa_prefill.pt: reference outputs of the sliding-window pair (authoring machine only).
 
-Usage: python scripts/make_swa_golden.py /path/to/mojo_opset   (a checkout of the reference; nothing else reads it)
+Usage: python oracle/make_swa_golden.py [reference root]   (default: MOJO_REFERENCE_ROOT, else /root/reference; nothing else reads it)
 
 The outputs come from the reference's own `MojoPagedDecodeSWA.forward` / `MojoPagedPrefillSWA.forward`
 (`mojo_opset/core/operators/attention.py:561-741`), called on CPU.  Each case records the constructor keywords, the
-inputs and the output; tests/test_swa_golden.py pins tests/swa_golden.py to them bit for bit and tests/test_hip_swa.py
+inputs and the output; tests/test_swa_golden.py pins oracle/swa.py to them bit for bit and tests/test_hip_swa.py
 checks the hip backend against them at the reference's bound (2e-2).
 """
 import os
@@ -14,6 +14,9 @@ import types
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from oracle.paged import cu  # noqa: E402
 
 
 def paged_inputs(g, batch, hq, hkv, d, kv_lens, page, dtype, q_rows):
@@ -36,7 +39,7 @@ def paged_inputs(g, batch, hq, hkv, d, kv_lens, page, dtype, q_rows):
 CASES = [
     # (kind, layout, local, global, page, hq, hkv, d, dtype, kv_lens, q_lens).  Sized to keep the file under 1 MiB: one
     # Mistral-like (4, 1023) decode case, the rest short (prefill at (4, 1023): tests/test_hip_swa.py); pages of 1024 tokens (256 KiB of K/V per page at the smallest head)
-    # are exercised by tests/test_hip_swa.py against tests/swa_golden.py instead.
+    # are exercised by tests/test_hip_swa.py against oracle/swa.py instead.
     ("decode", "AABB", 1023, 4, 16, 4, 1, 64, torch.bfloat16, [1060, 0], None),
     ("decode", "ABAB", 255, 4, 32, 4, 2, 64, torch.bfloat16, [262, 1], None),
     ("decode", "AABB", 0, None, 16, 2, 1, 128, torch.float16, [40, 17], None),
@@ -71,8 +74,7 @@ def main(reference_root):
             out = ref.MojoPagedDecodeSWA.forward(me, *args)
             op = "MojoPagedDecodeSWA"
         else:
-            cu_q = torch.tensor([0] + list(torch.tensor(q_lens).cumsum(0).tolist()), dtype=torch.int32)
-            cu_kv = torch.tensor([0] + list(torch.tensor(kv_lens).cumsum(0).tolist()), dtype=torch.int32)
+            cu_q, cu_kv = cu(q_lens), cu(kv_lens)
             args, kwargs = (q, k, v, cu_q, table), {"cu_total_seq_lens": cu_kv}
             out = ref.MojoPagedPrefillSWA.forward(me, *args, **kwargs)
             # the reference leaves rows of sequences without keys uninitialised (torch.empty_like); both backends zero them
@@ -90,4 +92,4 @@ def main(reference_root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_OPSET_REFERENCE", "."))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOJO_REFERENCE_ROOT", "/root/reference"))

@@ -1,7 +1,7 @@
 """Torch goldens of the W8A8 MoE ops (`MojoMoEDynamicQuant`, `MojoQuantExperts`, `MojoQuantMoE`).
 
-Ops beyond the SURVEY §8 set carry their goldens here, in the tests.  Importing this module registers
-``TorchMoEDynamicQuant`` / ``TorchQuantExperts`` / ``TorchQuantMoE`` as the ``torch`` backends of the three API classes.
+Importing this module registers ``TorchMoEDynamicQuant`` / ``TorchQuantExperts`` / ``TorchQuantMoE`` as the ``torch``
+backends of the three API classes.
 
 Semantics and rounding points restate `mojo_opset/core/operators/quantize.py:208-244` (the quantiser) and
 `mojo_opset/core/operators/moe.py:566-664` (the experts):
@@ -21,13 +21,13 @@ integer matrix product instead (fp64 matmul of the int8 values): the same bits w
 every output — then every partial fp32 sum of the reference is an integer below 2**24, exact in any order.  The form asserts
 that bound on its inputs (``dot_bound``).  `tests/golden/quant_moe.pt` pins both forms bit for bit.
 
-``TorchQuantMoE`` chains the ``torch`` backends of gating, dispatch and combine (``import oracle``) around
+``TorchQuantMoE`` chains the ``torch`` backends of gating, dispatch and combine (`oracle/torch_golden.py`, which the package
+imports with this module) around
 ``TorchQuantExperts`` through `MojoMoE.compose_forward`.
 """
 import torch
 import torch.nn.functional as F
 
-import oracle  # noqa: F401  (the torch backends of gating / dispatch / combine)
 from mojo_opset_amd.core.operators import moe as _moe
 from mojo_opset_amd.core.operators import quantize as _quant
 

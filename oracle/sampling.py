@@ -1,8 +1,7 @@
 """Torch goldens of the sampling ops (`SAMPLING_OPS`): top-k / top-p samplers, the nucleus filter, the two speculative
 acceptance steps and the penalties.
 
-Ops beyond the SURVEY §8 set carry their goldens here, in the tests.  Importing this module registers ``Torch<Op>`` as the
-``torch`` backend of each of the six API classes.  Semantics restate `mojo_opset/core/operators/sampling.py`;
+Importing this module registers ``Torch<Op>`` as the ``torch`` backend of each of the six API classes.  Semantics restate `mojo_opset/core/operators/sampling.py`;
 `tests/golden/sampling.pt` pins them to the reference's recorded outputs bit for bit.
 
 * `topk_sorted`: the reference calls ``torch.topk``, which leaves the order among equal values open.  Here it is pinned: a

@@ -1,13 +1,13 @@
 """Torch goldens of the sliding-window pair (`MojoPagedDecodeSWA`, `MojoPagedPrefillSWA`).
 
-Ops beyond the SURVEY §8 set carry their goldens here, in the tests, not in the repo-level `oracle/` package.  Importing
-this module registers ``TorchPagedDecodeSWA`` / ``TorchPagedPrefillSWA`` as the ``torch`` backends of the two API classes.
+Importing this module registers ``TorchPagedDecodeSWA`` / ``TorchPagedPrefillSWA`` as the ``torch`` backends of the two
+API classes.
 
 Semantics and rounding points restate `mojo_opset/core/operators/attention.py:507-531` (the window mask), :561-650
 (prefill) and :683-741 (decode): scores are a 16-bit ``bmm`` upcast to fp32 and scaled, masked with -inf outside the
 visible set, softmax statistics in fp32, the unnormalised probabilities rounded to the storage type, a 16-bit ``bmm``
-against V, upcast and divided by the fp32 row sum.  Pages are gathered by plain indexing of the table (a negative id
-indexes from the end of the cache, as in the reference).  `tests/golden/paged_swa.pt` pins these classes bit for bit.
+against V, upcast and divided by the fp32 row sum.  Pages are gathered by plain indexing of the table
+(`paged.index_pages`).  `tests/golden/paged_swa.pt` pins these classes bit for bit.
 """
 import math
 from typing import Optional
@@ -16,45 +16,15 @@ import torch
 
 from mojo_opset_amd.core.operators import attention as _attn
 
+from .paged import expand_kv_heads, index_pages, window_mask
+
 _CPU = ["rocm", "cpu"]
-
-
-def window_mask(q_len: int, kv_len: int, local: Optional[int], glob: Optional[int]) -> torch.Tensor:
-    """``[q_len, kv_len]`` bool: row i (position ``p = kv_len - q_len + i``) sees key j iff ``j <= p`` and, when a window
-    is set, ``j >= p - local`` or ``j < glob`` (reference :507-531)."""
-    pos = torch.arange(q_len)[:, None] + (kv_len - q_len)
-    key = torch.arange(kv_len)[None, :]
-    mask = key <= pos
-    if local is not None or glob is not None:
-        win = torch.zeros(q_len, kv_len, dtype=torch.bool)
-        if local is not None:
-            win |= pos <= key + local
-        if glob is not None:
-            win |= key < glob
-        mask &= win
-    return mask
-
-
-def _pages(cache, table_row, kv_len):
-    """``[Hkv, kv_len, D]`` of one sequence: its first ceil(kv_len / page) pages, token-major."""
-    n_kv, page, dim = cache.shape[1], cache.shape[2], cache.shape[3]
-    blocks = (kv_len + page - 1) // page
-    x = cache[table_row[:blocks].long()]                             # [blocks, Hkv, page, D]
-    return x.permute(1, 0, 2, 3).reshape(n_kv, blocks * page, dim)[:, :kv_len]
-
-
-def _expand(x, group, interleave):
-    """``[Hkv, S, D] -> [Hq, S, D]``: ABAB tiles the kv heads, AABB repeats each one."""
-    if group == 1:
-        return x
-    return x.repeat((group, 1, 1)) if interleave else x.repeat_interleave(group, dim=0)
 
 
 def _attend(op, q_i, k_i, v_i, kv_len, scale):
     """q_i [Hq, q_len, D], k_i / v_i [Hkv, kv_len, D] -> [Hq, q_len, D] fp32 (before the final cast)."""
     group = q_i.shape[0] // k_i.shape[0]
-    interleave = op.gqa_layout == "ABAB"
-    k_t = _expand(k_i.permute(0, 2, 1), group, interleave)
+    k_t = expand_kv_heads(k_i.permute(0, 2, 1), group, op.gqa_layout)
     s = torch.bmm(q_i, k_t).float() * scale
     if op.is_causal:
         s = torch.where(window_mask(q_i.shape[1], kv_len, op.local_window_size, op.global_window_size).to(s.device),
@@ -62,7 +32,7 @@ def _attend(op, q_i, k_i, v_i, kv_len, scale):
     s = s - torch.max(s, dim=-1, keepdim=True).values
     p = torch.exp(s)
     denom = torch.sum(p, dim=-1, keepdim=True)
-    return torch.bmm(p.to(q_i.dtype), _expand(v_i, group, interleave)).float() / denom
+    return torch.bmm(p.to(q_i.dtype), expand_kv_heads(v_i, group, op.gqa_layout)).float() / denom
 
 
 class TorchPagedDecodeSWA(_attn.MojoPagedDecodeSWA):
@@ -81,8 +51,8 @@ class TorchPagedDecodeSWA(_attn.MojoPagedDecodeSWA):
                 continue
             if int(block_table[b, 0]) < 0:
                 raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
-            o = _attend(self, query[b].unsqueeze(1), _pages(key_cache, block_table[b], kv_len),
-                        _pages(value_cache, block_table[b], kv_len), kv_len, scale)
+            o = _attend(self, query[b].unsqueeze(1), index_pages(key_cache, block_table[b], kv_len),
+                        index_pages(value_cache, block_table[b], kv_len), kv_len, scale)
             out[b] = o.squeeze(1).to(out.dtype)
         return out
 
@@ -109,7 +79,7 @@ class TorchPagedPrefillSWA(_attn.MojoPagedPrefillSWA):
                 continue
             if int(block_table[b, 0]) < 0:
                 raise ValueError("Paged prefill requires a valid block table for rows with kv lens > 0.")
-            o = _attend(self, query[lo:hi].permute(1, 0, 2), _pages(key_cache, block_table[b], kv_len),
-                        _pages(value_cache, block_table[b], kv_len), kv_len, scale)
+            o = _attend(self, query[lo:hi].permute(1, 0, 2), index_pages(key_cache, block_table[b], kv_len),
+                        index_pages(value_cache, block_table[b], kv_len), kv_len, scale)
             out[lo:hi] = o.permute(1, 0, 2).to(out.dtype)
         return out

@@ -23,6 +23,8 @@ from mojo_opset_amd.core.operators import normalization as _norm
 from mojo_opset_amd.core.operators import position_embedding as _pe
 from mojo_opset_amd.core.operators import quantize as _quant
 
+from .paged import expand_kv_heads, gather_pages
+
 _CPU = ["rocm", "cpu"]
 
 __all__ = [
@@ -34,42 +36,6 @@ __all__ = [
     "TorchResidualAddRMSNormQuant", "TorchStorePagedMLAKVCache",
     "gather_pages", "quant_gemm_formula",
 ]
-
-
-# ----------------------------------------------------------------------------------------------
-# paged-cache helpers
-# ----------------------------------------------------------------------------------------------
-def gather_pages(cache: torch.Tensor, table_row: torch.Tensor, length: int) -> torch.Tensor:
-    """``[length, heads, D]`` rows of one sequence pulled out of ``cache [N, heads, page, D]``.
-
-    Pages are walked in logical order; the walk stops at the first negative id and the remaining
-    rows stay zero — the behaviour of the reference's ``break`` inside a zero-initialised buffer
-    (`core/operators/attention.py:190-207`, :405-419).
-    """
-    page = cache.shape[2]
-    heads, dim = cache.shape[1], cache.shape[3]
-    out = torch.zeros(length, heads, dim, dtype=cache.dtype, device=cache.device)
-    n_pages = (length + page - 1) // page
-    ids = table_row[:n_pages].to(torch.int64)
-    bad = (ids < 0).nonzero()
-    if bad.numel():
-        n_pages = int(bad[0])
-        ids = ids[:n_pages]
-    if n_pages == 0:
-        return out
-    rows = cache[ids].permute(0, 2, 1, 3).reshape(n_pages * page, heads, dim)   # token-major
-    take = min(length, n_pages * page)
-    out[:take] = rows[:take]
-    return out
-
-
-def _expand_kv_heads(x: torch.Tensor, group: int, layout: str) -> torch.Tensor:
-    """``[S, Hkv, D] -> [S, Hq, D]``: AABB = repeat_interleave, ABAB = tile (:209-214)."""
-    if group == 1:
-        return x
-    if layout == "AABB":
-        return x.repeat_interleave(group, dim=1)
-    return x.repeat((1, group, 1))
 
 
 def _first_page_must_exist(table_row: torch.Tensor, what: str) -> None:
@@ -100,8 +66,8 @@ class TorchPagedDecodeGQA(_attn.MojoPagedDecodeGQA):
             if n <= 0:
                 continue
             _first_page_must_exist(block_tables[b], "decode")
-            k = _expand_kv_heads(gather_pages(key_cache, block_tables[b], n), group, self.gqa_layout)
-            v = _expand_kv_heads(gather_pages(value_cache, block_tables[b], n), group, self.gqa_layout)
+            k = expand_kv_heads(gather_pages(key_cache, block_tables[b], n), group, self.gqa_layout, dim=1)
+            v = expand_kv_heads(gather_pages(value_cache, block_tables[b], n), group, self.gqa_layout, dim=1)
             scores = torch.einsum("hd,khd->hk", query[b], k) * scale
             if not self.is_causal and mask is not None:
                 m = mask if mask.dim() == 2 else mask[b]
@@ -135,8 +101,8 @@ class TorchPagedPrefillGQA(_attn.MojoPagedPrefillGQA):
             if q_len == 0 or kv_len <= 0:
                 continue
             _first_page_must_exist(block_tables[b], "prefill")
-            k = _expand_kv_heads(gather_pages(key_cache, block_tables[b], kv_len), group, self.gqa_layout)
-            v = _expand_kv_heads(gather_pages(value_cache, block_tables[b], kv_len), group, self.gqa_layout)
+            k = expand_kv_heads(gather_pages(key_cache, block_tables[b], kv_len), group, self.gqa_layout, dim=1)
+            v = expand_kv_heads(gather_pages(value_cache, block_tables[b], kv_len), group, self.gqa_layout, dim=1)
             scores = torch.einsum("thd,khd->thk", query[lo:hi], k).float() * scale
             if self.is_causal:
                 band = torch.ones(q_len, kv_len, dtype=torch.bool, device=query.device).tril(kv_len - q_len)

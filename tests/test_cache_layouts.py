@@ -5,8 +5,8 @@ import pytest
 import torch
 
 import cache_layouts as CL
-import kv_int8_golden as G8
-import swa_golden
+import oracle.kv_int8 as G8
+import oracle.swa
 from conftest import bit_equal
 from hip_utils import torch_cls
 
@@ -117,13 +117,13 @@ def test_attention_goldens_return_the_same_bits_on_views(layout, table_layout):
     (tv,) = CL.lay_out_table(table, table_layout, hidden).views
     dec = torch_cls("MojoPagedDecodeGQA")()
     assert bit_equal(dec(q, kv, vv, lens, tv), dec(q, k, v, lens, table))
-    swa = swa_golden.TorchPagedDecodeSWA(global_window_size=4, local_window_size=20)
+    swa = oracle.swa.TorchPagedDecodeSWA(global_window_size=4, local_window_size=20)
     assert bit_equal(swa.forward(q, kv, vv, lens, tv), swa.forward(q, k, v, lens, table))
     q_lens = [20, 1, 0, 30]
     qp = torch.randn(sum(q_lens), hq, D, generator=g).bfloat16()
     pre = torch_cls("MojoPagedPrefillGQA")()
     assert bit_equal(pre(qp, kv, vv, cu(q_lens), tv, cu_total_seq_lens=cu(LENS)), pre(qp, k, v, cu(q_lens), table, cu_total_seq_lens=cu(LENS)))
-    pswa = swa_golden.TorchPagedPrefillSWA(global_window_size=4, local_window_size=20)
+    pswa = oracle.swa.TorchPagedPrefillSWA(global_window_size=4, local_window_size=20)
     assert bit_equal(pswa.forward(qp, kv, vv, cu(q_lens), tv, cu_total_seq_lens=cu(LENS)),
                      pswa.forward(qp, k, v, cu(q_lens), table, cu_total_seq_lens=cu(LENS)))
     # int8 cache

@@ -21,7 +21,7 @@ import pytest
 import torch
 
 import cache_layouts as CL
-import swa_golden
+import oracle.swa
 from conftest import bit_equal
 from hip_utils import DEV, assert_close_tree, hip_cls, last_launch, launches_of, switch_env, to_cpu, torch_cls
 from mojo_opset_amd.core.operators.kv_cache import build_paged_kv_chunk_metadata
@@ -118,7 +118,7 @@ def swa_decode_case(lens, glob, local):
     q, k, v, lens_t, table = make_decode_inputs(len(lens), 8, 2, 128, 0, 16, lens=list(lens), seed=31)
     hidden = poisoned_spare([k, v], table)
     kw = dict(gqa_layout="AABB", global_window_size=glob, local_window_size=local)
-    return (q, k, v, lens_t, table, hidden), swa_golden.TorchPagedDecodeSWA(**kw).forward(q, k, v, lens_t, table), kw
+    return (q, k, v, lens_t, table, hidden), oracle.swa.TorchPagedDecodeSWA(**kw).forward(q, k, v, lens_t, table), kw
 
 
 @pytest.mark.parametrize("layout", LAYOUTS, ids=LAYOUT_IDS)
@@ -159,7 +159,7 @@ def prefill_case(group, d, page, q_lens=Q_LENS, cached=CACHED, swa=None):
     hkv = 2
     q, k, v, cu_q, table, cu_kv, _ = make_prefill_inputs(list(q_lens), list(cached), hkv * group, hkv, d, page, seed=group + d + page)
     hidden = poisoned_spare([k, v], table)
-    ref = swa_golden.TorchPagedPrefillSWA(**swa_kw(swa)).forward if swa else torch_cls("MojoPagedPrefillGQA")()
+    ref = oracle.swa.TorchPagedPrefillSWA(**swa_kw(swa)).forward if swa else torch_cls("MojoPagedPrefillGQA")()
     return (q, k, v, cu_q, table, cu_kv, hidden), ref(q, k, v, cu_q, table, cu_total_seq_lens=cu_kv)
 
 

@@ -15,7 +15,7 @@ import functools
 import pytest
 import torch
 
-import swa_golden
+import oracle.swa
 from hip_utils import DEV, assert_close_tree, hip_cls, last_launch, switch_env, to_cpu, torch_cls
 from test_hip_decode_gqa import make_decode_inputs
 
@@ -212,5 +212,5 @@ def test_sliding_window_jump_inside_an_id_window(lens, glob, local):
     len 520: the local range starts inside the global one and the two collapse into one walk without a jump."""
     kw = dict(gqa_layout="AABB", global_window_size=glob, local_window_size=local)
     inputs = make_decode_inputs(len(lens), 8, 2, 128, 0, 16, lens=lens, seed=31)
-    want = swa_golden.TorchPagedDecodeSWA(**kw).forward(*inputs)
+    want = oracle.swa.TorchPagedDecodeSWA(**kw).forward(*inputs)
     run_checked(hip_cls("MojoPagedDecodeSWA")(**kw), inputs, want, ("decode_mfma:", ":swa"))

@@ -299,7 +299,7 @@ def _drawn_layout(rnd, k, v, table):
 @pytest.mark.parametrize("seed", range(16))
 def test_fuzz_swa(seed):
     """The sliding-window pair, decode and prefill, on a drawn cache and table layout."""
-    import swa_golden
+    import oracle.swa
     from hip_utils import last_launch
     rnd = random.Random(10000 + seed + OFFSET)
     hkv = rnd.choice([1, 2, 4, 8])
@@ -315,7 +315,7 @@ def test_fuzz_swa(seed):
     lens = [rnd.choice([0, 1, rnd.randint(1, max_len), max_len]) for _ in range(batch)]
     q, k, v, lens_t, table = make_decode_inputs(batch, hkv * g, hkv, d, max_len, page, dtype=dtype, seed=seed + OFFSET, lens=lens)
     (kd, vd), td, names = _drawn_layout(rnd, k, v, table)
-    want = swa_golden.TorchPagedDecodeSWA(**kw).forward(q, k, v, lens_t, table)
+    want = oracle.swa.TorchPagedDecodeSWA(**kw).forward(q, k, v, lens_t, table)
     op = hip_cls("MojoPagedDecodeSWA")(**kw)
     got = to_cpu(op(q.to(DEV), kd, vd, lens_t.to(DEV), td))
     assert last_launch().endswith(":swa"), (last_launch(), names)
@@ -330,7 +330,7 @@ def test_fuzz_swa(seed):
     q, k, v, cu_q, table, cu_kv, kv_lens = make_prefill_inputs(q_lens, cached, hkv * g, hkv, d, page, dtype=dtype, seed=seed + OFFSET)
     (kd, vd), td, names = _drawn_layout(rnd, k, v, table)
     cu_kv = cu(kv_lens)
-    want = swa_golden.TorchPagedPrefillSWA(**kw).forward(q, k, v, cu_q, table, cu_total_seq_lens=cu_kv)
+    want = oracle.swa.TorchPagedPrefillSWA(**kw).forward(q, k, v, cu_q, table, cu_total_seq_lens=cu_kv)
     got = to_cpu(hip_cls("MojoPagedPrefillSWA")(**kw)(q.to(DEV), kd, vd, cu_q.to(DEV), td, cu_total_seq_lens=cu_kv.to(DEV)))
     assert bool(torch.isfinite(got.float()).all()), names
     assert_close_tree(got, want, 2e-2, 2e-2)

@@ -1,4 +1,4 @@
-"""GPU parity of the int8 paged KV cache ops through the C ABI; oracle = tests/kv_int8_golden.py on CPU.
+"""GPU parity of the int8 paged KV cache ops through the C ABI; oracle = oracle/kv_int8.py on CPU.
 
 Store: bit-exact.  Decode and prefill: atol = rtol = 2e-2 on every element (decode: the reference's own bound,
 tests/accuracy/operators/test_attention_quant.py:460-461; prefill: the project's rule for GQA prefill, stricter than the
@@ -8,7 +8,7 @@ import math
 import pytest
 import torch
 
-import kv_int8_golden as G
+import oracle.kv_int8 as G
 from conftest import load_golden
 from hip_utils import DEV, assert_close_tree, hip_cls, last_launch, run_hip_case, switch_env, to_cpu, torch_cls
 from mojo_opset_amd.core.operators.kv_cache import build_paged_kv_chunk_metadata

@@ -1,5 +1,5 @@
 """GPU parity of sliding-window attention over the int8 paged KV cache (`MojoPagedDecodeSWAWithKVDequant`,
-`MojoPagedPrefillSWAWithKVDequant`) through the C ABI; oracle = tests/kv_int8_swa_golden.py on CPU.
+`MojoPagedPrefillSWAWithKVDequant`) through the C ABI; oracle = oracle/kv_int8_swa.py on CPU.
 
 atol = rtol = 2e-2 on every element: the project's bound for the same kernel arithmetic in tests/test_hip_kv_int8.py
 (tighter than the reference's 5e-2 on 90 % of the elements for this decode op).
@@ -11,7 +11,7 @@ import math
 import pytest
 import torch
 
-import kv_int8_swa_golden  # noqa: F401  (registers the torch backends)
+import oracle  # noqa: F401  (registers the torch backends)
 from conftest import load_golden
 from hip_utils import DEV, assert_close_tree, hip_cls, last_launch, run_hip_case, switch_env, to_cpu, torch_cls
 from test_hip_kv_int8 import cu, dev, make_inputs

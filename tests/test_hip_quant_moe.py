@@ -1,4 +1,4 @@
-"""GPU parity of the W8A8 MoE ops (`MojoMoEDynamicQuant`, `MojoQuantExperts`, `MojoQuantMoE`) against tests/quant_moe_golden.py.
+"""GPU parity of the W8A8 MoE ops (`MojoMoEDynamicQuant`, `MojoQuantExperts`, `MojoQuantMoE`) against oracle/quant_moe.py.
 
 * the quantiser and the grouped int8 product are BIT-EXACT (atol = rtol = 0): products and divisions are the IEEE single
   operations, int32 accumulation is exact and associative, so every kernel form, tile shape and K split gives the golden's bits
@@ -12,7 +12,7 @@
 import pytest
 import torch
 
-import quant_moe_golden as G
+import oracle.quant_moe as G
 from conftest import bit_equal, build_op, clone_tree, load_golden
 from hip_utils import DEV, hip_cls, last_launch, launches_of, run_hip_case, switch_env, to_cpu
 from mojo_opset_amd.backends.hip.operators.moe import HIPQuantExperts

@@ -1,4 +1,4 @@
-"""The hip backend of the sampling ops on the MI355X against the CPU goldens (tests/sampling_golden.py).
+"""The hip backend of the sampling ops on the MI355X against the CPU goldens (oracle/sampling.py).
 
 Tolerances (none comes from the code under test):
 
@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import mojo_opset_amd as mo
-import sampling_golden as G
+import oracle.sampling as G
 from conftest import bit_equal, clone_tree, load_golden, to_device
 
 pytestmark = pytest.mark.gpu

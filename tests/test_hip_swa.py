@@ -1,11 +1,11 @@
 """GPU parity of the sliding-window pair (`MojoPagedDecodeSWA`, `MojoPagedPrefillSWA`) through the C ABI.
 
 Tolerance: atol = rtol = 2e-2, the reference's own bound for these ops (test_attention.py:1434-1435, :1695-1696).
-The oracle is tests/swa_golden.py on CPU (pinned to the reference by tests/test_swa_golden.py)."""
+The oracle is oracle/swa.py on CPU (pinned to the reference by tests/test_swa_golden.py)."""
 import pytest
 import torch
 
-import swa_golden
+import oracle.swa
 from conftest import build_op, load_golden
 from hip_utils import DEV, assert_close_tree, hip_cls, last_launch, run_hip_case, switch_env, to_cpu
 
@@ -46,7 +46,7 @@ def prefill_inputs(kv_lens, q_lens, hq=8, hkv=2, d=128, page=16, dtype=torch.bfl
 def ops(kind, layout, glob, local):
     name = "MojoPagedDecodeSWA" if kind == "decode" else "MojoPagedPrefillSWA"
     kw = dict(gqa_layout=layout, global_window_size=glob, local_window_size=local)
-    return hip_cls(name)(**kw), getattr(swa_golden, "Torch" + name[4:])(**kw)
+    return hip_cls(name)(**kw), getattr(oracle.swa, "Torch" + name[4:])(**kw)
 
 
 def on_gpu(op, args, **kw):

@@ -2,17 +2,15 @@
 errors and `extra_repr`, `KV_INT8_OPS`, the plugin's registration, the host-side refusals of the hip classes and the
 workspace entry points.
 
-The recorded outputs (scripts/make_kv_int8_golden.py) are three files — store, decode, prefill — each under the 1 MiB
+The recorded outputs (oracle/make_kv_int8_golden.py) are three files — store, decode, prefill — each under the 1 MiB
 bound of a committed file."""
 import types
 
 import pytest
 import torch
 
-import kv_int8_golden
 import mojo_opset_amd as mo
-import oracle  # noqa: F401
-import swa_golden  # noqa: F401  (EXTENDED_OPS keep their torch backends whatever the collection order)
+import oracle.kv_int8
 from conftest import bit_equal, build_op, clone_tree, load_golden
 from mojo_opset_amd.core import MojoOperator
 from mojo_opset_amd.core.platform import get_platform
@@ -25,7 +23,7 @@ CASES = STORE + DECODE + PREFILL
 
 @pytest.mark.parametrize("case", [pytest.param(c, id=f"{c['op'][4:]}-{i}") for i, c in enumerate(CASES)])
 def test_golden_reproduces_the_reference_bit_for_bit(case):
-    op = build_op(getattr(kv_int8_golden, "Torch" + case["op"][4:]), case)
+    op = build_op(getattr(oracle.kv_int8, "Torch" + case["op"][4:]), case)
     out = op.forward(*clone_tree(case["args"]), **clone_tree(case["kwargs"]))
     assert bit_equal(out, case["out"])
 
@@ -74,7 +72,7 @@ def test_kv_int8_ops_are_attributes_but_not_in_all_or_extended_ops():
 
 @pytest.mark.parametrize("name", ATTN_OPS)
 def test_constructor_and_repr_follow_the_reference(name):
-    cls = getattr(kv_int8_golden, "Torch" + name[4:])
+    cls = getattr(oracle.kv_int8, "Torch" + name[4:])
     op = cls(gqa_layout="ABAB")
     assert (op.is_causal, op.gqa_layout, op.query_dtype, op.context_dtype, op.compute_dtype) == \
         (True, "ABAB", torch.bfloat16, torch.int8, torch.bfloat16)

@@ -2,18 +2,15 @@
 what the fixtures cover, dispatch, `KV_INT8_SWA_OPS`, the plugin's registration, constructor and `extra_repr`, the
 host-side refusals of the hip classes and the workspace entry points.
 
-The recorded outputs (scripts/make_kv_int8_swa_golden.py) are two files — decode, prefill — each under the 1 MiB bound of
+The recorded outputs (oracle/make_kv_int8_swa_golden.py) are two files — decode, prefill — each under the 1 MiB bound of
 a committed file."""
 import types
 
 import pytest
 import torch
 
-import kv_int8_golden  # noqa: F401  (the other sets keep their torch backends whatever the collection order)
-import kv_int8_swa_golden
 import mojo_opset_amd as mo
-import oracle  # noqa: F401
-import swa_golden  # noqa: F401
+import oracle.kv_int8_swa
 from conftest import bit_equal, build_op, clone_tree, load_golden
 from mojo_opset_amd.core import MojoOperator
 from mojo_opset_amd.core.platform import get_platform
@@ -25,7 +22,7 @@ CASES = DECODE + PREFILL
 
 @pytest.mark.parametrize("case", [pytest.param(c, id=f"{c['op'][4:]}-{i}") for i, c in enumerate(CASES)])
 def test_golden_reproduces_the_reference_bit_for_bit(case):
-    op = build_op(getattr(kv_int8_swa_golden, "Torch" + case["op"][4:]), case)
+    op = build_op(getattr(oracle.kv_int8_swa, "Torch" + case["op"][4:]), case)
     out = op.forward(*clone_tree(case["args"]), **clone_tree(case["kwargs"]))
     assert not torch.isnan(case["out"].float()).any()
     assert bit_equal(out, case["out"])
@@ -106,7 +103,7 @@ def test_rebase_registers_both_classes_into_a_stand_in_reference():
 
 @pytest.mark.parametrize("name", OPS)
 def test_constructor_and_repr_follow_the_reference(name):
-    cls = getattr(kv_int8_swa_golden, "Torch" + name[4:])
+    cls = getattr(oracle.kv_int8_swa, "Torch" + name[4:])
     op = cls(gqa_layout="ABAB", global_window_size=4, local_window_size=255)
     assert (op.is_causal, op.gqa_layout, op.gqa_interleave, op.global_window_size, op.local_window_size, op.query_dtype,
             op.context_dtype, op.compute_dtype) == (True, "ABAB", True, 4, 255, torch.bfloat16, torch.int8, torch.bfloat16)

@@ -2,7 +2,7 @@
 what the fixture must contain, dispatch and registration, `QUANT_MOE_OPS`, the plugin's registration, the constructor
 contract, the host-side refusals of the hip classes and the workspace query.
 
-The recorded outputs (scripts/make_quant_moe_golden.py) are one file under the 1 MiB bound of a committed file."""
+The recorded outputs (oracle/make_quant_moe_golden.py) are one file under the 1 MiB bound of a committed file."""
 import os
 import sys
 import types
@@ -11,8 +11,7 @@ import pytest
 import torch
 
 import mojo_opset_amd as mo
-import oracle  # noqa: F401
-import quant_moe_golden as G
+import oracle.quant_moe as G
 from conftest import GOLDEN, bit_equal, build_op, clone_tree, load_golden
 from mojo_opset_amd.core import MojoOperator
 from mojo_opset_amd.core.platform import get_platform

@@ -2,7 +2,7 @@
 contain, dispatch and registration, `SAMPLING_OPS`, the plugin's registration, the host-side refusals of the hip classes and
 the workspace query.
 
-The recorded outputs (scripts/make_sampling_golden.py) are one file under the 1 MiB bound of a committed file."""
+The recorded outputs (oracle/make_sampling_golden.py) are one file under the 1 MiB bound of a committed file."""
 import os
 import sys
 import types
@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import mojo_opset_amd as mo
-import sampling_golden as G
+import oracle.sampling as G
 from conftest import GOLDEN, bit_equal, clone_tree, load_golden
 from mojo_opset_amd.core import MojoOperator
 from mojo_opset_amd.core.platform import get_platform

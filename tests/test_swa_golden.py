@@ -1,17 +1,16 @@
 """The sliding-window pair without a GPU: the golden against the recorded reference outputs, dispatch, constructor and
 forward errors, `EXTENDED_OPS`, and the plugin's registration of both classes.
 
-The recorded outputs (scripts/make_swa_golden.py) are two files, decode and prefill, each under the 1 MiB bound of a
+The recorded outputs (oracle/make_swa_golden.py) are two files, decode and prefill, each under the 1 MiB bound of a
 committed file.  They hold no pages of 1024 tokens (one such page of K/V is 256 KiB at the smallest head) and no prefill
-at (4, 1023); tests/test_hip_swa.py runs both against tests/swa_golden.py instead."""
+at (4, 1023); tests/test_hip_swa.py runs both against oracle/swa.py instead."""
 import types
 
 import pytest
 import torch
 
 import mojo_opset_amd as mo
-import oracle  # noqa: F401
-import swa_golden
+import oracle.swa
 from conftest import build_op, clone_tree, load_golden
 from mojo_opset_amd.core import MojoOperator
 from mojo_opset_amd.core.platform import get_platform
@@ -22,7 +21,7 @@ CASES = load_golden("paged_swa") + load_golden("paged_swa_prefill")
 
 @pytest.mark.parametrize("case", [pytest.param(c, id=f"{c['op'][4:]}-{i}") for i, c in enumerate(CASES)])
 def test_golden_reproduces_the_reference_bit_for_bit(case):
-    op = build_op(getattr(swa_golden, "Torch" + case["op"][4:]), case)
+    op = build_op(getattr(oracle.swa, "Torch" + case["op"][4:]), case)
     out = op.forward(*clone_tree(case["args"]), **clone_tree(case["kwargs"]))
     assert torch.equal(out, case["out"])
 
@@ -53,7 +52,7 @@ def test_extended_ops_are_attributes_but_not_in_all():
 
 @pytest.mark.parametrize("name", SWA_OPS)
 def test_constructor_and_repr_follow_the_reference(name):
-    cls = getattr(swa_golden, "Torch" + name[4:])
+    cls = getattr(oracle.swa, "Torch" + name[4:])
     op = cls(gqa_layout="ABAB", global_window_size=4, local_window_size=255)
     assert (op.is_causal, op.gqa_layout, op.gqa_interleave, op.global_window_size, op.local_window_size) == \
         (True, "ABAB", True, 4, 255)
@@ -97,7 +96,7 @@ def test_non_causal_prefill_is_not_implemented():
 
 def test_golden_raises_on_a_missing_first_page():
     q, k, v, lens, _ = _decode_inputs()
-    op = swa_golden.TorchPagedDecodeSWA(local_window_size=3)
+    op = oracle.swa.TorchPagedDecodeSWA(local_window_size=3)
     with pytest.raises(ValueError):
         op.forward(q, k, v, lens, torch.tensor([[-1, -1]], dtype=torch.int32))
 
