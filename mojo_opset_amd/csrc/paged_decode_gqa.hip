@@ -21,6 +21,12 @@
 //
 // Algorithmic bytes per launch: sum_b len_b * Hkv * D * 2(K,V) * elt  +  2 * B * Hq * D * elt
 //                               + 4 * B * (max_blocks + 1).
+//
+// This file: DecodeArgs, the window (DecodeWin), the chunking rules and decode_head; paged_decode_common.h — what the three
+// decode kernels share on the device (paired prologue, row and chunk of a wave, hole scan, in-LDS merge, split epilogue, softmax
+// step of the matrix-core kernels); decode_split_kernel (vector units); paged_decode_mfma.h (16-bit matrix-core kernel); the
+// merge kernel; the planner; one launch selection for both 16-bit routes (launch_decode_nt); the entry points, which fill a
+// DecodeCall; paged_decode_kv8.h (int8-cache kernel and its entry points).
 #include <math.h>
 #include <stdlib.h>
 
@@ -136,6 +142,10 @@ __device__ __forceinline__ int decode_head(const DecodeArgs& a, int kvh, int g, 
   return (half * G + g) * (a.hkv >> a.hshift) + real;
 }
 
+}  // namespace mojo
+#include "paged_decode_common.h"
+namespace mojo {
+
 template <typename T, int G, bool NT, int MODE, bool SWA = false>
 __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_kernel(DecodeArgs a) {
   constexpr bool FUSED = MODE != DEC_SPLIT;
@@ -148,59 +158,18 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   const int j = lane % DEC_LPT;
   // (readfirstlane: the wave index must be a scalar, or every page-table lookup below turns into a vector load)
   const int wave_id = FUSED ? __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)) : 0;
-  int chunk = FUSED ? wave_id : static_cast<int>(blockIdx.x);
-  int b = blockIdx.y / a.hkv;
+  const int chunk0 = FUSED ? wave_id : static_cast<int>(blockIdx.x);
+  const int b0 = blockIdx.y / a.hkv;                     // (paired form: the pair index)
   const int kvh = blockIdx.y % a.hkv;
 
-  int seq_len, chunk_tokens;
   DecodeWin win;                                         // (SWA only)
-  // paired mode: the two sequences of this workgroup, their (clamped) lengths and the waves dealt to the first
-  int pb[2] = {0, -1}, plen[2] = {0, 0}, pchunk[2] = {DEC_TILE, DEC_TILE}, n_first = 8;
-  if constexpr (PAIRED) {
-    const int cap = a.n_chunks * a.chunk_tokens;
-    int len = -1;                                      // lanes past the batch rank behind every sequence
-    if (lane < a.batch) len = a.max_pages > 0 ? max(min(a.seq_lens[lane], cap), 0) : 0;
-    int rank = lane;                                   // position of sequence `lane` when ordered by length, longest first
-    if (__ballot(lane < a.batch && len != __builtin_amdgcn_readfirstlane(len)) != 0) {   // (a uniform batch keeps its order)
-      rank = 0;
-      for (int o = 0; o < a.batch; ++o) {
-        const int lo = __builtin_amdgcn_readlane(len, o);
-        rank += (lo > len || (lo == len && o < lane)) ? 1 : 0;
-      }
-    }
-    const int p = b;                                   // blockIdx.y / hkv is the pair index here
-    const unsigned long long first = __ballot(lane < a.batch && rank == p);
-    const unsigned long long second = __ballot(lane < a.batch && rank == a.batch - 1 - p && a.batch - 1 - p > p);
-    pb[0] = __builtin_ctzll(first);
-    plen[0] = __builtin_amdgcn_readlane(len, pb[0]);
-    if (second) {
-      pb[1] = __builtin_ctzll(second);
-      plen[1] = __builtin_amdgcn_readlane(len, pb[1]);
-    }
-    const int sum = plen[0] + plen[1];
-    n_first = plen[1] <= 0 ? 8 : min(max((8 * plen[0] + sum / 2) / sum, 1), 7);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int n_u = u ? 8 - n_first : n_first;
-      int c = n_u > 0 ? (plen[u] + n_u - 1) / n_u : DEC_TILE;
-      c = max(c, 128);
-      pchunk[u] = ((c + DEC_TILE - 1) / DEC_TILE) * DEC_TILE;
-    }
-    const int u = wave_id < n_first ? 0 : 1;
-    b = pb[u];
-    chunk = u ? wave_id - n_first : wave_id;
-    seq_len = b >= 0 ? plen[u] : 0;
-    chunk_tokens = pchunk[u];
-    if (b < 0) b = pb[0];                              // a wave without a sequence: valid addresses, no work
-  } else {
-    if constexpr (SWA) seq_len = a.max_pages > 0 ? decode_swa_row(a, b, win) : 0;
-    else seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;      // (no table columns: nothing to attend over)
-    chunk_tokens = decode_seq_chunk(a, seq_len);
-  }
-  const int tok_begin = chunk * chunk_tokens;
-  const bool has_work = seq_len > 0 && tok_begin < seq_len;
+  DecodePair pr;                                         // (PAIRED only)
+  DecodeRow row;
+  if constexpr (PAIRED) { pr = decode_pair(a, lane, b0); row = decode_row(pr, wave_id); }
+  else row = decode_row(a, b0, chunk0, decode_row_len<SWA>(a, b0, win));
+  const int b = row.b, chunk = row.chunk, tok_begin = row.tok_begin, tok_end = row.tok_end;
+  const bool has_work = row.has_work;
   if (!FUSED && !has_work) return;
-  const int tok_end = has_work ? min(seq_len, tok_begin + chunk_tokens) : tok_begin + 1;
   const bool dim_ok = j * 8 < a.dim;
   const int jd = dim_ok ? j * 8 : a.dim - 8;          // lanes past a short head re-read its last slice
 
@@ -230,33 +199,8 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   }
 
   const int32_t* table = a.tables + static_cast<int64_t>(b) * a.table_stride;
-  // The golden walks the pages in order and stops at the first negative id, leaving every later row zero
-  // (core/operators/attention.py:195-198).  `first_neg` = that page index among the pages up to the end of this chunk.
-  // The scan (64 table entries per load, one ballot each) does NOT gate the K/V loads: a load only needs its own table
-  // entry (a negative id is clamped to page 0, an address that certainly exists) and remembers its logical page; whether
-  // it must read as zero (logical page >= first_neg) is decided when the tile is consumed.  So the prologue is one
-  // round trip — scan batch, query and the first two tiles in flight together — instead of up to four dependent ones
-  // in front of the first K/V byte (measured fixed cost per call before: ~18 us).
-  int p1 = (tok_end + a.page - 1) / a.page;
-  int first_neg = 0x7fffffff;
-  if (p1 > a.max_pages) { first_neg = a.max_pages; p1 = a.max_pages; }
-  constexpr int SCAN = 4;                               // table loads in flight per scan step (256 pages)
-  int scan_v[SCAN];
-  auto scan_issue = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < SCAN; ++u) {
-      const int idx = base + u * 64 + lane;
-      scan_v[u] = idx < p1 ? table[idx] : 0;
-    }
-  };
-  auto scan_reduce = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < SCAN; ++u) {
-      const unsigned long long neg = __ballot(scan_v[u] < 0);
-      if (neg && first_neg == 0x7fffffff) first_neg = base + u * 64 + __builtin_ctzll(neg);
-    }
-  };
-  if (!SWA && has_work) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
+  DecodeHoles holes(a, tok_end);
+  if (!SWA && has_work) holes.issue(table, lane, 0);    // (SWA: no hole scan — pages outside the window may hold anything)
 
   const T* kbase = static_cast<const T*>(a.kc) + (kvh >> a.hshift) * a.c_head + jd;
   const T* vbase = static_cast<const T*>(a.vc) + (kvh >> a.hshift) * a.c_head + jd;
@@ -290,10 +234,10 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   };
 
   auto process = [&](Tile& t, int t0) {
-    if (t.lp[DEC_LOADS - 1] >= first_neg) {              // rare: pages behind a hole read as zeros (lp grows with u)
+    if (t.lp[DEC_LOADS - 1] >= holes.first_neg) {              // rare: pages behind a hole read as zeros (lp grows with u)
 #pragma unroll
       for (int u = 0; u < DEC_LOADS; ++u)
-        if (t.lp[u] >= first_neg) { V8 z = {}; t.k[u] = z; t.v[u] = z; }
+        if (t.lp[u] >= holes.first_neg) { V8 z = {}; t.k[u] = z; t.v[u] = z; }
     }
     const bool full = t0 + DEC_TILE <= tok_end;          // wave-uniform
     bool edge = false;                                   // SWA: the tile holds a window edge (wave-uniform)
@@ -380,13 +324,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   if (has_work) {
   load_tile(ta, tok_begin);
   if (tok_begin + DEC_TILE < tok_end) load_tile(tb, tok_begin + DEC_TILE);
-  if constexpr (!SWA) {
-  scan_reduce(0);
-  for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {   // contexts past 256 pages
-    scan_issue(base);
-    scan_reduce(base);
-  }
-  }
+  if constexpr (!SWA) holes.finish(table, lane);
   if constexpr (RING == 3) {
     for (int t0 = tok_begin; t0 < tok_end; t0 += 3 * DEC_TILE) {
       if (t0 + 2 * DEC_TILE < tok_end) load_tile(tc, t0 + 2 * DEC_TILE);
@@ -432,58 +370,20 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_split_ker
   }
 
   if constexpr (FUSED) {
-    const int stride = a.dim + 2;
     if (r == 0 && dim_ok) {
 #pragma unroll
       for (int g = 0; g < G; ++g) {
-        float* dst = s_part + (wave_id * G + g) * stride;     // (wave_id == chunk in the unpaired form)
+        float* dst = s_part + (wave_id * G + g) * (a.dim + 2);     // (wave_id == chunk in the unpaired form)
 #pragma unroll
         for (int e = 0; e < 8; ++e) dst[j * 8 + e] = acc[g][e];
         if (j == 0) { dst[a.dim] = m[g]; dst[a.dim + 1] = l[g]; }
       }
     }
-    __syncthreads();
-    // every thread of the workgroup takes (sequence of the pair, head g, 4 output elements) items
-    const int per_head = a.dim / 4;
-    typedef typename vec_of<T, 4>::type V4;
-    constexpr int UNITS = PAIRED ? 2 : 1;
-    for (int item = threadIdx.x; item < UNITS * G * per_head; item += blockDim.x) {
-      const int u = item / (G * per_head);
-      const int rest = item - u * (G * per_head);
-      const int g = rest / per_head, d0 = (rest - g * per_head) * 4;
-      int ub, ulen, uchunk, slot0, uwaves;
-      if constexpr (PAIRED) {
-        ub = pb[u]; ulen = plen[u]; uchunk = pchunk[u];
-        slot0 = u ? n_first : 0;
-        uwaves = u ? 8 - n_first : n_first;
-        if (ub < 0) continue;                            // odd batch: the middle sequence has no partner
-      } else {
-        ub = b; ulen = seq_len; uchunk = chunk_tokens; slot0 = 0; uwaves = static_cast<int>(blockDim.x >> 6);
-      }
-      const int n_chunks_seq = ulen <= 0 ? 0 : min((ulen + uchunk - 1) / uchunk, uwaves);
-      if (n_chunks_seq == 0 && a.leave_empty) continue;
-      const int h = decode_head(a, kvh, g, G);
-      float mx = -INFINITY;
-      for (int c = 0; c < n_chunks_seq; ++c) mx = fmaxf(mx, s_part[((slot0 + c) * G + g) * stride + a.dim]);
-      f32x4 num = {0.f, 0.f, 0.f, 0.f};
-      float den = 0.f;
-      for (int c = 0; c < n_chunks_seq; ++c) {
-        const float* src = s_part + ((slot0 + c) * G + g) * stride;
-        const float w = exp2f(src[a.dim] - mx);
-        den = fmaf(w, src[a.dim + 1], den);
-        num += f32x4{src[d0], src[d0 + 1], src[d0 + 2], src[d0 + 3]} * w;
-      }
-      const float inv = n_chunks_seq > 0 ? 1.0f / den : 0.f;      // empty sequence: zeros (golden semantics)
-      V4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = static_cast<T>(num[e] * inv);
-      *reinterpret_cast<V4*>(static_cast<T*>(a.out) + (static_cast<int64_t>(ub) * a.hq + h) * a.dim + d0) = o;
-    }
+    decode_lds_merge<PAIRED, false>(a, s_part, a.dim, G, kvh, row, pr, Store16<T>{a.out});
     return;
   }
   if (r != 0 || !dim_ok) return;
-  const int n_chunks_seq = (seq_len + chunk_tokens - 1) / chunk_tokens;
-  if (n_chunks_seq == 1) {
+  if (row.n_chunks_seq() == 1) {
     // single chunk: finish here, the merge kernel skips this row
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -716,88 +616,82 @@ static void launch_decode_mfma(const DecodeArgs& a, dim3 grid, dim3 block, int G
   else hipLaunchKernelGGL((decode_mfma_kernel<T, 2, NT, MODE, SWA>), grid, block, lds, s, a, G);
 }
 
+// The vector-unit kernel's instance for a run-time group size: f(std::integral_constant<int, G>) for G in 1, 2, 4, 8.
+template <typename F>
+static int dispatch_G(int G, F&& f) {
+  switch (G) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa: group size %d (supported: 1,2,4,8)", G);
+  }
+  return MOJO_OK;
+}
+
+// One launch of kernel mode MODE on either route (`what`: the launch's name in an error message).
+template <typename T, bool NT, int MODE, bool SWA>
+static int launch_decode_mode(const DecodeArgs& a, const DecodePlan& p, dim3 grid, dim3 block, const char* what, hipStream_t s) {
+  if (p.mfma) {
+    launch_decode_mfma<T, NT, MODE, SWA>(a, grid, block, p.G, s);
+  } else {
+    const size_t waves = block.x / 64;                  // [waves][G][dim + 2] partials, and the 8-head instance's query slices
+    const size_t lds = MODE == DEC_SPLIT ? 0 : waves * p.G * (a.dim + 2) * sizeof(float) + (p.G >= 8 ? waves * p.G * DEC_LPT * 16 : 0);
+    const int rc = dispatch_G(p.G, [&](auto g) {
+      hipLaunchKernelGGL((decode_split_kernel<T, decltype(g)::value, NT, MODE, SWA>), grid, block, lds, s, a);
+      return MOJO_OK;
+    });
+    if (rc != MOJO_OK) return rc;
+  }
+  MOJO_CHECK_LAUNCH(what);
+  return MOJO_OK;
+}
+
 template <typename T, bool NT, bool SWA>
 static int launch_decode_nt(const DecodeArgs& a, const DecodePlan& p, hipStream_t s) {
   const int64_t batch = a.batch;
-  const int G = p.G;
-  const bool no_fuse = MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) == 0;
-  const bool no_pair = MOJO_SWITCH("MOJO_HIP_DECODE_PAIR", 1) == 0;
-  const char* nt_tag = NT ? "nt" : "cached";
-  const char* swa_tag = SWA ? ":swa" : "";             // (the windowed instances: never the paired form)
-  if (p.mfma) {
-    if (!SWA && a.n_chunks == 4 && batch >= 2 && batch <= 64 && !no_fuse && !no_pair) {
-      launch_decode_mfma<T, NT, DEC_PAIRED, false>(a, dim3(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv)), dim3(512), G, s);
-      MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, paired)");
-      note_launch("decode_mfma:paired:%s%s", nt_tag, swa_tag);
-      return MOJO_OK;
-    }
-    if (a.n_chunks <= 8 && !no_fuse) {
-      launch_decode_mfma<T, NT, DEC_FUSED, SWA>(a, dim3(1, static_cast<unsigned>(batch * a.hkv)), dim3(static_cast<unsigned>(64 * a.n_chunks)), G, s);
-      MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, fused)");
-      note_launch("decode_mfma:fused:%s%s", nt_tag, swa_tag);
-      return MOJO_OK;
-    }
-    if (a.fuse_group > 0 && !no_fuse) {
-      // small grids (few (sequence, kv-head) rows, many chunks each): eight-wave workgroups merge their chunks in LDS and leave
-      // one partial each, so the launch keeps two waves per SIMD busy and the merge reads n_chunks / 8 partials per row
-      const unsigned n_sub = static_cast<unsigned>((a.n_chunks + a.fuse_group - 1) / a.fuse_group);
-      launch_decode_mfma<T, NT, DEC_FUSED, SWA>(a, dim3(n_sub, static_cast<unsigned>(batch * a.hkv)), dim3(static_cast<unsigned>(64 * a.fuse_group)), G, s);
-      MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, grouped)");
-      hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
-      MOJO_CHECK_LAUNCH("paged_decode_gqa(merge)");
-      note_launch("decode_mfma:grouped+merge:%s%s", nt_tag, swa_tag);
-      return MOJO_OK;
-    }
-    launch_decode_mfma<T, NT, DEC_SPLIT, SWA>(a, dim3(static_cast<unsigned>(a.n_chunks), static_cast<unsigned>(batch * a.hkv)), dim3(64), G, s);
-    MOJO_CHECK_LAUNCH("paged_decode_gqa(mfma, split)");
-    hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
+  const bool fuse = MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) != 0;
+  const bool pair = MOJO_SWITCH("MOJO_HIP_DECODE_PAIR", 1) != 0;
+  // The form of the launch, decided once for both routes.  The workgroup forms of the vector-unit kernel store four outputs
+  // per thread: head dims that are no multiple of 4 take its split form.
+  const bool wg_forms = fuse && (p.mfma || a.dim % 4 == 0);
+  enum { PAIRED, FUSED, GROUPED, SPLIT } form = SPLIT;
+  // paired: four waves per sequence fill the chip once — pair the sequences by length rank, deal each pair's 8 waves by length
+  if (!SWA && wg_forms && pair && a.n_chunks == 4 && batch >= 2 && batch <= 64) form = PAIRED;
+  // fused: all chunks of a (sequence, kv-head) in one workgroup, merged in LDS
+  else if (wg_forms && a.n_chunks <= 8) form = FUSED;
+  // grouped (matrix-core kernel): small grids (few (sequence, kv-head) rows, many chunks each) — eight-wave workgroups merge
+  // their chunks in LDS and leave one partial each, so the launch keeps two waves per SIMD busy and the merge reads
+  // n_chunks / 8 partials per row
+  else if (wg_forms && p.mfma && a.fuse_group > 0) form = GROUPED;
+  const unsigned rows = static_cast<unsigned>(batch * a.hkv);
+  static const char* const tags[] = {"paired", "fused", "grouped+merge", "split+merge"};
+  static const char* const whats[2][4] = {
+      {"paged_decode_gqa(paired)", "paged_decode_gqa(fused)", "paged_decode_gqa(grouped)", "paged_decode_gqa(split)"},
+      {"paged_decode_gqa(mfma, paired)", "paged_decode_gqa(mfma, fused)", "paged_decode_gqa(mfma, grouped)", "paged_decode_gqa(mfma, split)"}};
+  const char* const what = whats[p.mfma ? 1 : 0][form];
+  int rc = MOJO_OK;
+  switch (form) {
+    case PAIRED:                                       // (never with a window: the windowed instances have no paired form)
+      rc = launch_decode_mode<T, NT, DEC_PAIRED, false>(a, p, dim3(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv)), dim3(512), what, s);
+      break;
+    case FUSED:
+      rc = launch_decode_mode<T, NT, DEC_FUSED, SWA>(a, p, dim3(1, rows), dim3(static_cast<unsigned>(64 * a.n_chunks)), what, s);
+      break;
+    case GROUPED:
+      rc = launch_decode_mode<T, NT, DEC_FUSED, SWA>(a, p, dim3(static_cast<unsigned>((a.n_chunks + a.fuse_group - 1) / a.fuse_group), rows),
+                                                     dim3(static_cast<unsigned>(64 * a.fuse_group)), what, s);
+      break;
+    case SPLIT:
+      rc = launch_decode_mode<T, NT, DEC_SPLIT, SWA>(a, p, dim3(static_cast<unsigned>(a.n_chunks), rows), dim3(64), what, s);
+      break;
+  }
+  if (rc != MOJO_OK) return rc;
+  if (form == GROUPED || form == SPLIT) {
+    hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(rows, p.G), dim3(256), 0, s, a, p.G);
     MOJO_CHECK_LAUNCH("paged_decode_gqa(merge)");
-    note_launch("decode_mfma:split+merge:%s%s", nt_tag, swa_tag);
-    return MOJO_OK;
   }
-  if (!SWA && a.n_chunks == 4 && batch >= 2 && batch <= 64 && a.dim % 4 == 0 && !no_fuse && !no_pair) {
-    // four waves per sequence fill the chip once: pair the sequences by length rank and deal each pair's 8 waves by length
-    dim3 grid(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv));
-    const size_t lds = static_cast<size_t>(8) * G * (a.dim + 2) * sizeof(float) + (G >= 8 ? static_cast<size_t>(8) * G * DEC_LPT * 16 : 0);
-    switch (G) {
-      case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
-      case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
-      case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
-      case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_PAIRED, false>), grid, dim3(512), lds, s, a); break;
-      default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa: group size %d (supported: 1,2,4,8)", G);
-    }
-    MOJO_CHECK_LAUNCH("paged_decode_gqa(paired)");
-    note_launch("decode_valu:paired:%s%s", nt_tag, swa_tag);
-    return MOJO_OK;
-  }
-  if (a.n_chunks <= 8 && a.dim % 4 == 0 && !no_fuse) {   // all chunks of a (sequence, kv-head) in one workgroup: merged in LDS
-    dim3 grid(1, static_cast<unsigned>(batch * a.hkv));
-    const dim3 block(static_cast<unsigned>(64 * a.n_chunks));
-    const size_t lds = static_cast<size_t>(a.n_chunks) * G * (a.dim + 2) * sizeof(float) +
-                       (G >= 8 ? static_cast<size_t>(a.n_chunks) * G * DEC_LPT * 16 : 0);
-    switch (G) {
-      case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
-      case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
-      case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
-      case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_FUSED, SWA>), grid, block, lds, s, a); break;
-      default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa: group size %d (supported: 1,2,4,8)", G);
-    }
-    MOJO_CHECK_LAUNCH("paged_decode_gqa(fused)");
-    note_launch("decode_valu:fused:%s%s", nt_tag, swa_tag);
-    return MOJO_OK;
-  }
-  dim3 grid(static_cast<unsigned>(a.n_chunks), static_cast<unsigned>(batch * a.hkv));
-  switch (G) {
-    case 1: hipLaunchKernelGGL((decode_split_kernel<T, 1, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((decode_split_kernel<T, 2, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((decode_split_kernel<T, 4, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((decode_split_kernel<T, 8, NT, DEC_SPLIT, SWA>), grid, dim3(64), 0, s, a); break;
-    default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_decode_gqa: group size %d (supported: 1,2,4,8)", G);
-  }
-  MOJO_CHECK_LAUNCH("paged_decode_gqa(split)");
-  hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(static_cast<unsigned>(batch * a.hkv), G), dim3(256), 0, s, a, G);
-  MOJO_CHECK_LAUNCH("paged_decode_gqa(merge)");
-  note_launch("decode_valu:split+merge:%s%s", nt_tag, swa_tag);
+  note_launch("%s:%s:%s%s", p.mfma ? "decode_mfma" : "decode_valu", tags[form], NT ? "nt" : "cached", SWA ? ":swa" : "");
   return MOJO_OK;
 }
 
@@ -824,7 +718,35 @@ struct DecodeCall {
   float softmax_scale = 0.f;
   int layout_abab = 0, leave_empty_rows = 0, dtype = 0;
   mojo_stream_t stream = nullptr;
+  const void *key_scale = nullptr, *value_scale = nullptr;   // the int8-cache ops (g.kv8): per-channel scales [Hkv][D] and their dtype
+  int scale_dtype = 0;
 };
+
+// What every decode entry point checks first (`op`: the entry point's name in the messages).
+static int decode_check_call(const DecodeCall& c, const char* op) {
+  const DecodeGeom& g = c.g;
+  MOJO_REQUIRE(c.query && c.key_cache && c.value_cache && c.total_seq_lens && c.block_tables && c.out &&
+                   (!g.kv8 || (c.key_scale && c.value_scale)), MOJO_EINVAL, "%s: null pointer", op);
+  MOJO_REQUIRE(g.batch > 0 && g.q_heads > 0 && g.kv_heads > 0 && g.q_heads % g.kv_heads == 0, MOJO_EINVAL,
+               "%s: bad head counts Hq=%lld Hkv=%lld", op, (long long)g.q_heads, (long long)g.kv_heads);
+  MOJO_REQUIRE(c.dtype == MOJO_BF16 || c.dtype == MOJO_F16, MOJO_EUNSUPPORTED, "%s: %sdtype %d (bf16/fp16 only)", op,
+               g.kv8 ? "query " : "", c.dtype);
+  // (the 16-bit op may run a kv head as two halves on twice the grid heads)
+  MOJO_REQUIRE(g.max_pages >= 0 && g.batch * g.kv_heads * (g.kv8 ? 1 : 2) <= 65535, MOJO_EUNSUPPORTED,
+               "%s: batch*kv_heads %lld exceeds the grid limit", op, (long long)(g.batch * g.kv_heads));
+  return MOJO_OK;
+}
+
+// The window of a planned windowed call (p.swa), in the kernel's 32-bit terms.
+static int decode_set_window(DecodeArgs& a, const DecodeCall& c, const DecodePlan& p, const char* op) {
+  const DecodeGeom& g = c.g;
+  MOJO_REQUIRE(p.capacity < (int64_t{1} << 30) && g.local_window < (int64_t{1} << 30) && g.global_window < (int64_t{1} << 30),
+               MOJO_EUNSUPPORTED, "%s: lengths and windows must stay below 2^30", op);
+  a.swa_cap = static_cast<int>(p.capacity);
+  a.local_win = g.local_window >= 0 ? static_cast<int>(g.local_window) : -1;
+  a.global_win = g.global_window > 0 ? static_cast<int>(g.global_window) : 0;
+  return MOJO_OK;
+}
 
 // The kernel arguments of a planned call, its workspace bound (`op`: the entry point's name in the messages).
 static int decode_fill_args(DecodeArgs& a, const DecodeCall& c, const DecodePlan& p, const char* op) {
@@ -849,12 +771,7 @@ static int decode_fill_args(DecodeArgs& a, const DecodeCall& c, const DecodePlan
 template <bool SWA>
 static int paged_decode_planned(const DecodeCall& c, const DecodePlan& p) {
   const DecodeGeom& g = c.g;
-  MOJO_REQUIRE(c.query && c.key_cache && c.value_cache && c.total_seq_lens && c.block_tables && c.out, MOJO_EINVAL,
-               "paged_decode_gqa: null pointer");
-  MOJO_REQUIRE(g.batch > 0 && g.q_heads > 0 && g.kv_heads > 0 && g.q_heads % g.kv_heads == 0, MOJO_EINVAL,
-               "paged_decode_gqa: bad head counts Hq=%lld Hkv=%lld", (long long)g.q_heads, (long long)g.kv_heads);
-  MOJO_REQUIRE(c.dtype == MOJO_BF16 || c.dtype == MOJO_F16, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa: dtype %d (bf16/fp16 only)", c.dtype);
+  if (const int rc = decode_check_call(c, "paged_decode_gqa"); rc != MOJO_OK) return rc;
   MOJO_REQUIRE(g.head_dim % 8 == 0 && g.head_dim >= 8 && g.head_dim <= 8 * DEC_LPT, MOJO_EUNSUPPORTED,
                "paged_decode_gqa: head_dim %lld (multiple of 8, <= %d)", (long long)g.head_dim, 8 * DEC_LPT);
   MOJO_REQUIRE(g.page % DEC_TPL == 0, MOJO_EUNSUPPORTED, "paged_decode_gqa: block_size %lld must be a multiple of %d",
@@ -863,15 +780,9 @@ static int paged_decode_planned(const DecodeCall& c, const DecodePlan& p) {
                    aligned_to(c.key_cache, 16) && aligned_to(c.value_cache, 16) && aligned_to(c.query, 16) &&
                    aligned_to(c.out, 16),
                MOJO_EUNSUPPORTED, "paged_decode_gqa: tensors must be 16-byte aligned with 16-byte row strides");
-  MOJO_REQUIRE(g.max_pages >= 0 && g.batch * g.kv_heads * 2 <= 65535, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa: batch*kv_heads %lld exceeds the grid limit", (long long)(g.batch * g.kv_heads));
   DecodeArgs a;
   if constexpr (SWA) {
-    MOJO_REQUIRE(p.capacity < (int64_t{1} << 30) && g.local_window < (int64_t{1} << 30) && g.global_window < (int64_t{1} << 30),
-                 MOJO_EUNSUPPORTED, "paged_decode_swa: lengths and windows must stay below 2^30");
-    a.swa_cap = static_cast<int>(p.capacity);
-    a.local_win = g.local_window >= 0 ? static_cast<int>(g.local_window) : -1;
-    a.global_win = g.global_window > 0 ? static_cast<int>(g.global_window) : 0;
+    if (const int rc = decode_set_window(a, c, p, "paged_decode_swa"); rc != MOJO_OK) return rc;
   }
   if (const int rc = decode_fill_args(a, c, p, "paged_decode_gqa"); rc != MOJO_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(c.stream);
@@ -906,14 +817,11 @@ extern "C" int mojo_hip_paged_decode_gqa(const void* query, const void* key_cach
                                          int64_t cache_block_stride, int64_t cache_head_stride,
                                          int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
                                          int layout_abab, int leave_empty_rows, int dtype, mojo_stream_t stream) {
-  DecodeCall c;
-  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
-  c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint};
-  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
-  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
-  c.leave_empty_rows = leave_empty_rows; c.dtype = dtype;
-  return paged_decode(c);
+  // (no window: the windowed entry point runs the GQA op itself)
+  return mojo_hip_paged_decode_swa(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes, batch,
+                                   q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                                   cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
+                                   layout_abab, leave_empty_rows, dtype, /*local_window=*/-1, /*global_window=*/0, stream);
 }
 
 extern "C" int mojo_hip_paged_decode_swa(const void* query, const void* key_cache, const void* value_cache,

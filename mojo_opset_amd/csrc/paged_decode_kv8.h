@@ -1,6 +1,7 @@
 // decode_kv8_kernel: MojoPagedDecodeGQAWithKVDequant — paged decode over an int8 K/V cache with per-channel scales.
-// Included at the end of paged_decode_gqa.hip: shares DecodeArgs, the chunking rules, decode_head, the hole / empty-row /
-// capacity-clamp semantics and the merge kernel with the 16-bit op; the 16-bit kernels themselves are not touched.
+// Included at the end of paged_decode_gqa.hip: shares DecodeArgs, the chunking rules, decode_head and the merge kernel with the
+// 16-bit op, and through paged_decode_common.h the row prologue, the hole scan, the in-LDS merge, the split epilogue and the
+// softmax step (fp16 probabilities: dec_mma<f16_t>::pack); the entry points fill the 16-bit ops' DecodeCall.
 //
 // The scales never meet a K or V element:
 //   q'[h, d] = q[h, d] * key_scale[kvh, d]             once per wave, fp32 product rounded to fp16
@@ -42,15 +43,15 @@ struct Kv8Args {
   int q_bf16;                    // query / output dtype: 1 = bf16, 0 = fp16
 };
 
-__device__ __forceinline__ void kv8_store4(void* out, int bf16, int64_t i, float x0, float x1, float x2, float x3) {
-  if (bf16) {
-    const bf16x4 v = {static_cast<bf16_t>(x0), static_cast<bf16_t>(x1), static_cast<bf16_t>(x2), static_cast<bf16_t>(x3)};
-    *reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(out) + i) = v;
-  } else {
-    const f16x4 v = {static_cast<f16_t>(x0), static_cast<f16_t>(x1), static_cast<f16_t>(x2), static_cast<f16_t>(x3)};
-    *reinterpret_cast<f16x4*>(static_cast<f16_t*>(out) + i) = v;
+// the output store of the shared merge and split epilogue, in the query's run-time dtype
+struct Kv8Store {
+  void* out;
+  int bf16;
+  __device__ __forceinline__ void operator()(int64_t at, f32x4 x) const {
+    if (bf16) Store16<bf16_t>{out}(at, x);
+    else Store16<f16_t>{out}(at, x);
   }
-}
+};
 
 // four int8 of a dword -> four fp16 (exact): elements 0, 1 in `lo`, 2, 3 in `hi`
 __device__ __forceinline__ void kv8_unpack4(unsigned w, f16x2& lo, f16x2& hi) {
@@ -90,15 +91,11 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
   const int b = blockIdx.y / a.hkv;
   const int kvh = blockIdx.y % a.hkv;
 
-  DecodeWin win;                                        // (SWA only)
-  int seq_len = 0;                                      // SWA: the row's virtual length
-  if constexpr (SWA) seq_len = a.max_pages > 0 ? decode_swa_row(a, b, win) : 0;
-  else seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;
-  const int chunk_tokens = decode_seq_chunk(a, seq_len);
-  const int tok_begin = chunk * chunk_tokens;
-  const bool has_work = seq_len > 0 && tok_begin < seq_len;
+  DecodeWin win;                                        // (SWA only; the row's length is then the virtual one)
+  const DecodeRow row = decode_row(a, b, chunk, decode_row_len<SWA>(a, b, win));
+  const int tok_begin = row.tok_begin, tok_end = row.tok_end;
+  const bool has_work = row.has_work;
   if (!FUSED && !has_work) return;
-  const int tok_end = has_work ? min(seq_len, tok_begin + chunk_tokens) : tok_begin + 1;
 
   // query operand: lane (head tl, k-group g4), piece g4 + 4 i, half hh -> dims 16 (g4 + 4 i) + 8 hh .. + 7, scaled
   const int hq_l = min(tl, G - 1);                      // lanes past the group repeat its last head (computed, never stored)
@@ -134,26 +131,8 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
 
   const int32_t* table = a.tables + static_cast<int64_t>(b) * a.table_stride;
   // holes: as the 16-bit kernels — the pages at and behind the first negative id read as zeros; the scan does not gate the loads
-  int p1 = (tok_end + a.page - 1) / a.page;
-  int first_neg = 0x7fffffff;
-  if (p1 > a.max_pages) { first_neg = a.max_pages; p1 = a.max_pages; }
-  constexpr int SCAN = 4;
-  int scan_v[SCAN];
-  auto scan_issue = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < SCAN; ++u) {
-      const int idx = base + u * 64 + lane;
-      scan_v[u] = idx < p1 ? table[idx] : 0;
-    }
-  };
-  auto scan_reduce = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < SCAN; ++u) {
-      const unsigned long long neg = __ballot(scan_v[u] < 0);
-      if (neg && first_neg == 0x7fffffff) first_neg = base + u * 64 + __builtin_ctzll(neg);
-    }
-  };
-  if (!SWA && has_work) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
+  DecodeHoles holes(a, tok_end);
+  if (!SWA && has_work) holes.issue(table, lane, 0);    // (SWA: no hole scan — pages outside the window may hold anything)
 
   const int vr = lane / CPR, vc = lane % CPR;           // V: row vr of a load instruction, piece vc of the row
   const bool v_lane = vr < RPI;
@@ -207,7 +186,7 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
     if constexpr (!SWA) {
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss)
-      if (t.lp[ss] >= first_neg) {                      // rare: pages behind a hole read as zeros
+      if (t.lp[ss] >= holes.first_neg) {                     // rare: pages behind a hole read as zeros
         const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int i = 0; i < NI; ++i) t.k[ss][i] = z;
@@ -257,30 +236,8 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
         }
       }
     }
-    float mx = fmaxf(fmaxf(x[0][0], x[0][1]), fmaxf(x[0][2], x[0][3]));
-#pragma unroll
-    for (int ss = 1; ss < NS; ++ss) mx = fmaxf(mx, fmaxf(fmaxf(x[ss][0], x[ss][1]), fmaxf(x[ss][2], x[ss][3])));
-    mx = xor_max_16_32(mx);                             // the head's maximum over the step (all four token groups)
-    float ref = m;
-    if (mx - m > 8.0f) ref = mx;                        // lazy reference: probabilities stay below 2^8 (fp16 holds them)
-    if (!__all(ref == m)) {
-      const float alpha = m == ref ? 1.f : fast_exp2(m - ref);
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
-      m = ref;
-    }
-    const float ms = m == -INFINITY ? 0.f : m;
     f16x4 pf[NS];
-#pragma unroll
-    for (int ss = 0; ss < NS; ++ss) {
-      float p[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) p[i] = fast_exp2(x[ss][i] - ms);
-      l += (p[0] + p[1]) + (p[2] + p[3]);
-      const f16x4 v = {static_cast<f16_t>(p[0]), static_cast<f16_t>(p[1]), static_cast<f16_t>(p[2]), static_cast<f16_t>(p[3])};
-      pf[ss] = v;
-    }
+    decode_softmax_step<dec_mma<f16_t>>(x, m, l, o, pf);   // (fp16 probabilities whatever the query dtype; below 2^8)
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -295,13 +252,7 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
   if (has_work) {
     load_tile(ta, tok_begin);
     if (tok_begin + STEP < tok_end) load_tile(tb, tok_begin + STEP);
-    if constexpr (!SWA) {
-      scan_reduce(0);
-      for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
-        scan_issue(base);
-        scan_reduce(base);
-      }
-    }
+    if constexpr (!SWA) holes.finish(table, lane);
     for (int t0 = tok_begin; t0 < tok_end; t0 += 3 * STEP) {
       if (t0 + 2 * STEP < tok_end) load_tile(tc, t0 + 2 * STEP);
       process(ta, t0);
@@ -323,58 +274,20 @@ __global__ __launch_bounds__(512) void decode_kv8_kernel(Kv8Args ka, int G) {   
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[dt][i] *= sv[i];
   }
-  const bool head_ok = tl < G;
+  const Kv8Store store{a.out, ka.q_bf16};
   if constexpr (FUSED) {
-    const int stride = D + 2;
-    if (head_ok) {
-      float* dst = s_part + (wave_id * G + tl) * stride;
+    if (tl < G) {
+      float* dst = s_part + (wave_id * G + tl) * (D + 2);
 #pragma unroll
       for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
         for (int i = 0; i < 4; ++i) dst[dt * 16 + 4 * g4 + i] = o[dt][i];
       if (g4 == 0) { dst[D] = m; dst[D + 1] = l; }
     }
-    __syncthreads();
-    const int per_head = D / 4;
-    const int n_chunks_seq = seq_len <= 0 ? 0 : min((seq_len + chunk_tokens - 1) / chunk_tokens, n_waves);
-    if (n_chunks_seq == 0 && a.leave_empty) return;     // (workgroup-uniform, after the barrier)
-    for (int item = threadIdx.x; item < G * per_head; item += blockDim.x) {
-      const int g = item / per_head, d0 = (item - g * per_head) * 4;
-      const int h = decode_head(a, kvh, g, G);
-      float mx = -INFINITY;
-      for (int c = 0; c < n_chunks_seq; ++c) mx = fmaxf(mx, s_part[(c * G + g) * stride + D]);
-      f32x4 num = {0.f, 0.f, 0.f, 0.f};
-      float den = 0.f;
-      for (int c = 0; c < n_chunks_seq; ++c) {
-        const float* src = s_part + (c * G + g) * stride;
-        const float w = exp2f(src[D] - mx);
-        den = fmaf(w, src[D + 1], den);
-        num += f32x4{src[d0], src[d0 + 1], src[d0 + 2], src[d0 + 3]} * w;
-      }
-      const float inv = n_chunks_seq > 0 ? 1.0f / den : 0.f;        // empty sequence: zeros (golden semantics)
-      kv8_store4(a.out, ka.q_bf16, (static_cast<int64_t>(b) * a.hq + h) * D + d0, num[0] * inv, num[1] * inv, num[2] * inv, num[3] * inv);
-    }
+    decode_lds_merge<false, false>(a, s_part, D, G, kvh, row, DecodePair{}, store);
     return;
   }
-  if (!head_ok) return;
-  const int n_chunks_seq = (seq_len + chunk_tokens - 1) / chunk_tokens;
-  if (n_chunks_seq == 1) {                              // single chunk: finish here, the merge kernel skips this row
-    const int h = decode_head(a, kvh, tl, G);
-    const float inv = 1.0f / l;
-    const int64_t row = (static_cast<int64_t>(b) * a.hq + h) * D + 4 * g4;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-      kv8_store4(a.out, ka.q_bf16, row + dt * 16, o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
-    return;
-  }
-  const int64_t slot = (static_cast<int64_t>(blockIdx.y) * a.n_chunks + chunk) * G + tl;
-  float* dst = a.ws_acc + slot * D + 4 * g4;
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<f32x4*>(dst + dt * 16) = o[dt];
-  if (g4 == 0) {
-    a.ws_ml[slot * 2 + 0] = m;
-    a.ws_ml[slot * 2 + 1] = l;
-  }
+  decode_split_finish(a, G, kvh, row, tl, g4, o, m, l, store);
 }
 
 template <int CPR, bool NT, bool SWA>
@@ -420,56 +333,34 @@ static int launch_decode_kv8(const Kv8Args& ka, int64_t batch, int G, hipStream_
 
 // The int8-cache entry points share one body: a window (local >= 0 or global > 0) selects the windowed instances, planned on
 // the visible capacity (decode_swa_cap); none runs the unwindowed op, whichever entry point was called.
-static int paged_decode_kv8(const void* query, const void* key_cache, const void* key_scale, const void* value_cache,
-                            const void* value_scale, const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
-                            void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads, int64_t kv_heads,
-                            int64_t head_dim, int64_t block_size, int64_t max_blocks_per_seq, int64_t block_table_stride,
-                            int64_t cache_block_stride, int64_t cache_head_stride, int64_t cache_token_stride,
-                            int64_t max_seq_len_hint, float softmax_scale, int layout_abab, int leave_empty_rows, int dtype,
-                            int scale_dtype, int64_t local_window, int64_t global_window, mojo_stream_t stream) {
+static int paged_decode_kv8(const DecodeCall& c) {
   using namespace mojo;
-  if (batch == 0) return MOJO_OK;
-  MOJO_REQUIRE(query && key_cache && value_cache && key_scale && value_scale && total_seq_lens && block_tables && out, MOJO_EINVAL,
-               "paged_decode_gqa_kv8: null pointer");
-  MOJO_REQUIRE(batch > 0 && q_heads > 0 && kv_heads > 0 && q_heads % kv_heads == 0, MOJO_EINVAL,
-               "paged_decode_gqa_kv8: bad head counts Hq=%lld Hkv=%lld", (long long)q_heads, (long long)kv_heads);
-  MOJO_REQUIRE(dtype == MOJO_BF16 || dtype == MOJO_F16, MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: query dtype %d (bf16/fp16 only)", dtype);
-  MOJO_REQUIRE(scale_dtype == MOJO_BF16 || scale_dtype == MOJO_F16 || scale_dtype == MOJO_F32, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa_kv8: scale dtype %d (bf16/fp16/fp32 only)", scale_dtype);
-  MOJO_REQUIRE(head_dim == 64 || head_dim == 80 || head_dim == 96 || head_dim == 128, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa_kv8: head_dim %lld (supported: 64, 80, 96, 128)", (long long)head_dim);
-  MOJO_REQUIRE(block_size > 0 && block_size % 16 == 0, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa_kv8: block_size %lld must be a multiple of 16", (long long)block_size);
-  MOJO_REQUIRE(q_heads / kv_heads <= 16, MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: group size %lld (supported: 1..16)",
-               (long long)(q_heads / kv_heads));
-  MOJO_REQUIRE(cache_token_stride % 16 == 0 && cache_head_stride % 16 == 0 && cache_block_stride % 16 == 0 &&
-                   aligned_to(key_cache, 16) && aligned_to(value_cache, 16) && aligned_to(query, 16) && aligned_to(out, 16) &&
-                   aligned_to(key_scale, 16) && aligned_to(value_scale, 16),
+  const DecodeGeom& g = c.g;
+  if (g.batch == 0) return MOJO_OK;
+  if (const int rc = decode_check_call(c, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
+  MOJO_REQUIRE(c.scale_dtype == MOJO_BF16 || c.scale_dtype == MOJO_F16 || c.scale_dtype == MOJO_F32, MOJO_EUNSUPPORTED,
+               "paged_decode_gqa_kv8: scale dtype %d (bf16/fp16/fp32 only)", c.scale_dtype);
+  MOJO_REQUIRE(g.head_dim == 64 || g.head_dim == 80 || g.head_dim == 96 || g.head_dim == 128, MOJO_EUNSUPPORTED,
+               "paged_decode_gqa_kv8: head_dim %lld (supported: 64, 80, 96, 128)", (long long)g.head_dim);
+  MOJO_REQUIRE(g.page > 0 && g.page % 16 == 0, MOJO_EUNSUPPORTED,
+               "paged_decode_gqa_kv8: block_size %lld must be a multiple of 16", (long long)g.page);
+  MOJO_REQUIRE(g.q_heads / g.kv_heads <= 16, MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: group size %lld (supported: 1..16)",
+               (long long)(g.q_heads / g.kv_heads));
+  MOJO_REQUIRE(c.cache_token_stride % 16 == 0 && c.cache_head_stride % 16 == 0 && c.cache_block_stride % 16 == 0 &&
+                   aligned_to(c.key_cache, 16) && aligned_to(c.value_cache, 16) && aligned_to(c.query, 16) && aligned_to(c.out, 16) &&
+                   aligned_to(c.key_scale, 16) && aligned_to(c.value_scale, 16),
                MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: tensors must be 16-byte aligned with 16-byte row strides");
-  MOJO_REQUIRE(max_blocks_per_seq >= 0 && batch * kv_heads <= 65535, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa_kv8: batch*kv_heads %lld exceeds the grid limit", (long long)(batch * kv_heads));
-  DecodeCall c;
-  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
-  c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
-  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window, global_window, /*kv8=*/true};
-  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
-  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
-  c.leave_empty_rows = leave_empty_rows;
-  const DecodePlan p = decode_plan(c.g);
+  const DecodePlan p = decode_plan(g);
   Kv8Args ka{};
   if (p.swa) {
-    MOJO_REQUIRE(p.capacity < (int64_t{1} << 30) && local_window < (int64_t{1} << 30) && global_window < (int64_t{1} << 30),
-                 MOJO_EUNSUPPORTED, "paged_decode_swa_kv8: lengths and windows must stay below 2^30");
-    ka.a.swa_cap = static_cast<int>(p.capacity);
-    ka.a.local_win = local_window >= 0 ? static_cast<int>(local_window) : -1;
-    ka.a.global_win = global_window > 0 ? static_cast<int>(global_window) : 0;
+    if (const int rc = decode_set_window(ka.a, c, p, "paged_decode_swa_kv8"); rc != MOJO_OK) return rc;
   }
   if (const int rc = decode_fill_args(ka.a, c, p, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
-  ka.kscale = key_scale; ka.vscale = value_scale; ka.scale_dtype = scale_dtype; ka.q_bf16 = dtype == MOJO_BF16 ? 1 : 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  ka.kscale = c.key_scale; ka.vscale = c.value_scale; ka.scale_dtype = c.scale_dtype; ka.q_bf16 = c.dtype == MOJO_BF16 ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(c.stream);
   const bool nt = MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0;
-  if (p.swa) return nt ? launch_decode_kv8<true, true>(ka, batch, p.G, s) : launch_decode_kv8<false, true>(ka, batch, p.G, s);
-  return nt ? launch_decode_kv8<true, false>(ka, batch, p.G, s) : launch_decode_kv8<false, false>(ka, batch, p.G, s);
+  if (p.swa) return nt ? launch_decode_kv8<true, true>(ka, g.batch, p.G, s) : launch_decode_kv8<false, true>(ka, g.batch, p.G, s);
+  return nt ? launch_decode_kv8<true, false>(ka, g.batch, p.G, s) : launch_decode_kv8<false, false>(ka, g.batch, p.G, s);
 }
 
 extern "C" int64_t mojo_hip_paged_decode_gqa_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
@@ -486,22 +377,6 @@ extern "C" int64_t mojo_hip_paged_decode_swa_kv8_workspace_bytes(int64_t batch, 
                             global_window, /*kv8=*/true}).query_bytes;
 }
 
-extern "C" int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
-                                             const void* value_cache, const void* value_scale,
-                                             const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
-                                             void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
-                                             int64_t kv_heads, int64_t head_dim, int64_t block_size,
-                                             int64_t max_blocks_per_seq, int64_t block_table_stride,
-                                             int64_t cache_block_stride, int64_t cache_head_stride,
-                                             int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
-                                             int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
-                                             mojo_stream_t stream) {
-  return paged_decode_kv8(query, key_cache, key_scale, value_cache, value_scale, total_seq_lens, block_tables, out, workspace,
-                          workspace_bytes, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
-                          cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale, layout_abab,
-                          leave_empty_rows, dtype, scale_dtype, -1, 0, stream);
-}
-
 extern "C" int mojo_hip_paged_decode_swa_kv8(const void* query, const void* key_cache, const void* key_scale,
                                              const void* value_cache, const void* value_scale,
                                              const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
@@ -512,8 +387,31 @@ extern "C" int mojo_hip_paged_decode_swa_kv8(const void* query, const void* key_
                                              int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
                                              int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
                                              int64_t local_window, int64_t global_window, mojo_stream_t stream) {
-  return paged_decode_kv8(query, key_cache, key_scale, value_cache, value_scale, total_seq_lens, block_tables, out, workspace,
-                          workspace_bytes, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
-                          cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale, layout_abab,
-                          leave_empty_rows, dtype, scale_dtype, local_window, global_window, stream);
+  DecodeCall c;
+  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
+  c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window, global_window, /*kv8=*/true};
+  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
+  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
+  c.leave_empty_rows = leave_empty_rows; c.dtype = dtype;
+  c.key_scale = key_scale; c.value_scale = value_scale; c.scale_dtype = scale_dtype;
+  return paged_decode_kv8(c);
+}
+
+extern "C" int mojo_hip_paged_decode_gqa_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                             const void* value_cache, const void* value_scale,
+                                             const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                             void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                             int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                             int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                             int64_t cache_block_stride, int64_t cache_head_stride,
+                                             int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                             int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
+                                             mojo_stream_t stream) {
+  // (no window: the windowed entry point runs the unwindowed op itself)
+  return mojo_hip_paged_decode_swa_kv8(query, key_cache, key_scale, value_cache, value_scale, total_seq_lens, block_tables, out, workspace,
+                                       workspace_bytes, batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq,
+                                       block_table_stride, cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint,
+                                       softmax_scale, layout_abab, leave_empty_rows, dtype, scale_dtype, /*local_window=*/-1,
+                                       /*global_window=*/0, stream);
 }

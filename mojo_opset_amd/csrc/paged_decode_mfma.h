@@ -1,5 +1,7 @@
 // decode_mfma_kernel: MojoPagedDecodeGQA with the two contractions on the matrix cores (round 3).
-// Included by paged_decode_gqa.hip (shares DecodeArgs, the chunking rules, decode_head, the merge kernel and the launch forms).
+// Included by paged_decode_gqa.hip (shares DecodeArgs, the chunking rules, decode_head, the merge kernel and the launch forms;
+// the paired prologue, the row prologue, the hole scan, the in-LDS merge, the split epilogue and the softmax step are those of
+// paged_decode_common.h — this file holds the tile layouts, the ring and the id windows).
 //
 // The vector-unit kernel (decode_split_kernel) spends ~600 vector instructions per 16-token tile for four query heads and
 // ~1 070 for eight (dot products, DPP butterflies, exponentials and the P V sums, all of them per head): with two waves per
@@ -24,7 +26,7 @@
 //
 // The LDS image belongs to ONE wave (LDS operations of a wave execute in order): no barrier anywhere in the loop.  Pages must
 // hold a multiple of 16 tokens (a tile then lies in one page), head_dim 64 or 128, group size <= 16; everything else takes the
-// vector-unit kernel.  Same chunking, pairing, in-LDS merge, workspace layout and hole / empty-row semantics as that kernel.
+// vector-unit kernel.  Chunking, pairing, in-LDS merge, workspace layout and hole / empty-row semantics are that kernel's: one definition.
 //
 // The K/V stream is a ring of three tiles (8 KiB each) in registers.  From five tiles on, a wave runs rounds of three tiles
 // in which every request is unconditional: the compiler then counts the loads, and processing tile t waits for t's own eight
@@ -83,58 +85,18 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   const int tl = lane & 15, g4 = lane >> 4;             // K / V loads: token tl of the tile, dim chunk g4 of each k-step
   const int wave_id = FUSED ? __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)) : 0;
   // (grouped form, DecodeArgs::fuse_group: workgroup x of a row owns chunks [x * waves, (x + 1) * waves) of it)
-  int chunk = FUSED ? static_cast<int>(blockIdx.x) * static_cast<int>(blockDim.x >> 6) + wave_id : static_cast<int>(blockIdx.x);
-  int b = blockIdx.y / a.hkv;
+  const int chunk0 = FUSED ? static_cast<int>(blockIdx.x) * static_cast<int>(blockDim.x >> 6) + wave_id : static_cast<int>(blockIdx.x);
+  const int b0 = blockIdx.y / a.hkv;                    // (paired form: the pair index)
   const int kvh = blockIdx.y % a.hkv;
 
-  int seq_len, chunk_tokens;
   DecodeWin win;                                        // (SWA only)
-  int pb[2] = {0, -1}, plen[2] = {0, 0}, pchunk[2] = {DEC_TILE, DEC_TILE}, n_first = 8;
-  if constexpr (PAIRED) {                               // (identical to decode_split_kernel: the two launches must agree)
-    const int cap = a.n_chunks * a.chunk_tokens;
-    int len = -1;
-    if (lane < a.batch) len = a.max_pages > 0 ? max(min(a.seq_lens[lane], cap), 0) : 0;
-    int rank = lane;
-    if (__ballot(lane < a.batch && len != __builtin_amdgcn_readfirstlane(len)) != 0) {
-      rank = 0;
-      for (int o = 0; o < a.batch; ++o) {
-        const int lo = __builtin_amdgcn_readlane(len, o);
-        rank += (lo > len || (lo == len && o < lane)) ? 1 : 0;
-      }
-    }
-    const int p = b;
-    const unsigned long long first = __ballot(lane < a.batch && rank == p);
-    const unsigned long long second = __ballot(lane < a.batch && rank == a.batch - 1 - p && a.batch - 1 - p > p);
-    pb[0] = __builtin_ctzll(first);
-    plen[0] = __builtin_amdgcn_readlane(len, pb[0]);
-    if (second) {
-      pb[1] = __builtin_ctzll(second);
-      plen[1] = __builtin_amdgcn_readlane(len, pb[1]);
-    }
-    const int sum = plen[0] + plen[1];
-    n_first = plen[1] <= 0 ? 8 : min(max((8 * plen[0] + sum / 2) / sum, 1), 7);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int n_u = u ? 8 - n_first : n_first;
-      int c = n_u > 0 ? (plen[u] + n_u - 1) / n_u : DEC_TILE;
-      c = max(c, 128);
-      pchunk[u] = ((c + DEC_TILE - 1) / DEC_TILE) * DEC_TILE;
-    }
-    const int u = wave_id < n_first ? 0 : 1;
-    b = pb[u];
-    chunk = u ? wave_id - n_first : wave_id;
-    seq_len = b >= 0 ? plen[u] : 0;
-    chunk_tokens = pchunk[u];
-    if (b < 0) b = pb[0];
-  } else {
-    if constexpr (SWA) seq_len = a.max_pages > 0 ? decode_swa_row(a, b, win) : 0;
-    else seq_len = a.max_pages > 0 ? decode_seq_len(a, b) : 0;
-    chunk_tokens = decode_seq_chunk(a, seq_len);
-  }
-  const int tok_begin = chunk * chunk_tokens;
-  const bool has_work = seq_len > 0 && tok_begin < seq_len;
+  DecodePair pr;                                        // (PAIRED only)
+  DecodeRow row;
+  if constexpr (PAIRED) { pr = decode_pair(a, lane, b0); row = decode_row(pr, wave_id); }
+  else row = decode_row(a, b0, chunk0, decode_row_len<SWA>(a, b0, win));
+  const int b = row.b, tok_begin = row.tok_begin, tok_end = row.tok_end;
+  const bool has_work = row.has_work;
   if (!FUSED && !has_work) return;
-  const int tok_end = has_work ? min(seq_len, tok_begin + chunk_tokens) : tok_begin + 1;
 
   // query slices: B operand, lane = (head tl, dims 32 s + 8 g4 .. + 7)
   const int hq_l = min(tl, G - 1);                      // lanes past the group repeat its last head (computed, never stored)
@@ -148,24 +110,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   float m = -INFINITY, l = 0.f;
 
   const int32_t* table = a.tables + static_cast<int64_t>(b) * a.table_stride;
-  int p1 = (tok_end + a.page - 1) / a.page;
-  int first_neg = 0x7fffffff;
-  if (p1 > a.max_pages) { first_neg = a.max_pages; p1 = a.max_pages; }
-  constexpr int SCAN = 4;
-  int scan_v[SCAN];
-  auto scan_issue = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < SCAN; ++u) {
-      scan_v[u] = table[min(base + u * 64 + lane, p1 - 1)];           // (unconditional: a guarded load is waited for on the spot)
-    }
-  };
-  auto scan_reduce = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < SCAN; ++u) {
-      const unsigned long long neg = __ballot(scan_v[u] < 0 && base + u * 64 + lane < p1);
-      if (neg && first_neg == 0x7fffffff) first_neg = base + u * 64 + __builtin_ctzll(neg);
-    }
-  };
+  DecodeHoles holes(a, tok_end);
 
   // K: instruction (token group j, line L) = tokens 8 j + (l & 7), chunk 8 L + (l >> 3);  V: whole rows, RPI rows per instruction
   constexpr int CPR = D / 8;                            // 16-byte chunks per row
@@ -207,7 +152,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   if (has_work) {
     idw = id_window(0);
     idn = id_window(IDW);
-    if constexpr (!SWA) scan_issue(0);                  // (SWA: no hole scan — pages outside the window may hold anything)
+    if constexpr (!SWA) holes.issue(table, lane, 0);   // (SWA: no hole scan — pages outside the window may hold anything)
   }
   struct Tile { V8 k[NS][2][NL]; V8 v[NS][NV]; int lp[NS]; };
   auto ld = [&](const T* p) -> V8 {
@@ -253,7 +198,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   auto process = [&](Tile& t, int t0) {
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss)
-      if (t.lp[ss] >= first_neg) {                       // rare: pages behind a hole read as zeros
+      if (t.lp[ss] >= holes.first_neg) {                      // rare: pages behind a hole read as zeros
         V8 z = {};
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -322,29 +267,8 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
           if (!ok) x[ss][i] = -INFINITY;
         }
     }
-    float mx = fmaxf(fmaxf(x[0][0], x[0][1]), fmaxf(x[0][2], x[0][3]));
-#pragma unroll
-    for (int ss = 1; ss < NS; ++ss) mx = fmaxf(mx, fmaxf(fmaxf(x[ss][0], x[ss][1]), fmaxf(x[ss][2], x[ss][3])));
-    mx = xor_max_16_32(mx);                              // the head's maximum over the step (all four token groups)
-    float ref = m;
-    if (mx - m > 8.0f) ref = mx;                         // m = -inf: any finite score; NaN (-inf - -inf): keep
-    if (!__all(ref == m)) {
-      const float alpha = m == ref ? 1.f : fast_exp2(m - ref);        // m = -inf: 0 (O and the sum are 0)
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
-      m = ref;
-    }
-    const float ms = m == -INFINITY ? 0.f : m;
     typename MM::frag4 pf[NS];
-#pragma unroll
-    for (int ss = 0; ss < NS; ++ss) {
-      float p[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) p[i] = fast_exp2(x[ss][i] - ms);
-      l += (p[0] + p[1]) + (p[2] + p[3]);
-      pf[ss] = MM::pack(p[0], p[1], p[2], p[3]);
-    }
+    decode_softmax_step<MM>(x, m, l, o, pf);
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -357,15 +281,7 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
 
   Tile ta, tb, tc;
   if (has_work) {
-    auto scan_rest = [&]() {                             // the hole scan: what the prologue requested, then the rest of a long row
-      if constexpr (!SWA) {
-        scan_reduce(0);
-        for (int base = 64 * SCAN; base < p1 && first_neg == 0x7fffffff; base += 64 * SCAN) {
-          scan_issue(base);
-          scan_reduce(base);
-        }
-      }
-    };
+    auto scan_rest = [&]() { if constexpr (!SWA) holes.finish(table, lane); };
     int t0 = tok_begin;
     load_tile(ta, tok_begin);
     if (tok_begin + 4 * STEP < tok_end) {
@@ -414,92 +330,17 @@ __global__ __launch_bounds__(MODE != DEC_SPLIT ? 512 : 64) void decode_mfma_kern
   // the row sums of the four token groups of a head meet (the reference maximum is already common to them)
   l = xor_sum_16_32(l);
   // lane holds head tl, dims 16 dt + 4 g4 + i
-  const bool head_ok = tl < G;
   if constexpr (FUSED) {
-    const int stride = D + 2;
-    if (head_ok) {
-      float* dst = s_part + (wave_id * G + tl) * stride;
+    if (tl < G) {
+      float* dst = s_part + (wave_id * G + tl) * (D + 2);
 #pragma unroll
       for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<f32x4*>(dst + dt * 16 + 4 * g4) = o[dt];
       if (g4 == 0) { dst[D] = m; dst[D + 1] = l; }
     }
-    __syncthreads();
-    const int per_head = D / 4;
-    typedef typename vec_of<T, 4>::type V4;
-    constexpr int UNITS = PAIRED ? 2 : 1;
-    for (int item = threadIdx.x; item < UNITS * G * per_head; item += blockDim.x) {
-      const int u = item / (G * per_head);
-      const int rest = item - u * (G * per_head);
-      const int g = rest / per_head, d0 = (rest - g * per_head) * 4;
-      int ub, ulen, uchunk, slot0, uwaves;
-      if constexpr (PAIRED) {
-        ub = pb[u]; ulen = plen[u]; uchunk = pchunk[u];
-        slot0 = u ? n_first : 0;
-        uwaves = u ? 8 - n_first : n_first;
-        if (ub < 0) continue;
-      } else {
-        ub = b; ulen = seq_len; uchunk = chunk_tokens; slot0 = 0; uwaves = static_cast<int>(blockDim.x >> 6);
-      }
-      int n_chunks_seq = ulen <= 0 ? 0 : min((ulen + uchunk - 1) / uchunk, uwaves);
-      bool partial = false;                                // grouped form: this workgroup's chunks are not the whole row
-      if constexpr (!PAIRED) {
-        if (a.fuse_group > 0) {
-          const int total = ulen <= 0 ? 0 : (ulen + uchunk - 1) / uchunk;
-          partial = total > uwaves;
-          n_chunks_seq = min(max(total - static_cast<int>(blockIdx.x) * uwaves, 0), uwaves);
-          if (blockIdx.x > 0 && n_chunks_seq == 0) continue;   // a workgroup past the row's last chunk: nothing to leave
-        }
-      }
-      if (n_chunks_seq == 0 && a.leave_empty) continue;
-      const int h = decode_head(a, kvh, g, G);
-      float mx = -INFINITY;
-      for (int c = 0; c < n_chunks_seq; ++c) mx = fmaxf(mx, s_part[((slot0 + c) * G + g) * stride + D]);
-      f32x4 num = {0.f, 0.f, 0.f, 0.f};
-      float den = 0.f;
-      for (int c = 0; c < n_chunks_seq; ++c) {
-        const float* src = s_part + ((slot0 + c) * G + g) * stride;
-        const float w = exp2f(src[D] - mx);
-        den = fmaf(w, src[D + 1], den);
-        num += f32x4{src[d0], src[d0 + 1], src[d0 + 2], src[d0 + 3]} * w;
-      }
-      if (partial) {                                         // un-normalised sums against this workgroup's maximum, for the merge launch
-        const int64_t slot = (static_cast<int64_t>(blockIdx.y) * a.n_chunks + blockIdx.x) * G + g;
-        *reinterpret_cast<f32x4*>(a.ws_acc + slot * D + d0) = num;
-        if (d0 == 0) { a.ws_ml[slot * 2 + 0] = mx; a.ws_ml[slot * 2 + 1] = den; }
-        continue;
-      }
-      const float inv = n_chunks_seq > 0 ? 1.0f / den : 0.f;
-      V4 ov;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ov[e] = static_cast<T>(num[e] * inv);
-      *reinterpret_cast<V4*>(static_cast<T*>(a.out) + (static_cast<int64_t>(ub) * a.hq + h) * D + d0) = ov;
-    }
+    decode_lds_merge<PAIRED, !PAIRED>(a, s_part, D, G, kvh, row, pr, Store16<T>{a.out});
     return;
   }
-  if (!head_ok) return;
-  const int n_chunks_seq = (seq_len + chunk_tokens - 1) / chunk_tokens;
-  if (n_chunks_seq == 1) {                               // single chunk: finish here, the merge kernel skips this row
-    const int h = decode_head(a, kvh, tl, G);
-    const float inv = 1.0f / l;
-    typedef typename vec_of<T, 4>::type V4;
-    T* dst = static_cast<T*>(a.out) + (static_cast<int64_t>(b) * a.hq + h) * D + 4 * g4;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) {
-      V4 ov;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ov[e] = static_cast<T>(o[dt][e] * inv);
-      *reinterpret_cast<V4*>(dst + dt * 16) = ov;
-    }
-    return;
-  }
-  const int64_t slot = (static_cast<int64_t>(blockIdx.y) * a.n_chunks + chunk) * G + tl;
-  float* dst = a.ws_acc + slot * D + 4 * g4;
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<f32x4*>(dst + dt * 16) = o[dt];
-  if (g4 == 0) {
-    a.ws_ml[slot * 2 + 0] = m;
-    a.ws_ml[slot * 2 + 1] = l;
-  }
+  decode_split_finish(a, G, kvh, row, tl, g4, o, m, l, Store16<T>{a.out});
 }
 
 }  // namespace mojo
