@@ -362,6 +362,32 @@ int mojo_hip_paged_prefill_swa(const void* query, const void* key_cache, const v
                                int layout_abab, int dtype, void* workspace, int64_t workspace_bytes,
                                int64_t local_window, int64_t global_window, mojo_stream_t stream);
 
+/* ---- MojoPagedDecodeNstepSWA (experimental/operators/attention.py:1154-1262): `steps` query rows per sequence (draft
+ *      verification, multi-token prediction) in one pass over the paged cache.  The arguments of mojo_hip_paged_decode_swa
+ *      plus `steps`; query and out are [batch][steps][q_heads][head_dim] dense, total_seq_lens counts the `steps` new tokens.
+ *      Step j sits at position p = len - steps + j and sees key t iff t <= p and (no window, or t >= p - local_window, or
+ *      t < global_window).  Rows of length <= 0 are zeros (left untouched with leave_empty_rows); a step with p < 0
+ *      (0 < len < steps) sees no key and stores zeros.  With no window negative page ids are holes as in the GQA op (zero
+ *      K/V from the first one on); with a window there is no hole scan, as in the SWA op.
+ *      steps == 1 IS mojo_hip_paged_decode_swa (same plan, same workspace, bit for bit).  steps > 1 runs on the matrix-core
+ *      decode kernel alone: head_dim 64 / 128, power-of-two pages of >= 16 tokens, groups of <= 16 heads, and
+ *      MOJO_HIP_DECODE_MFMA != 0.  For every other geometry the workspace query answers -1 and the entry point returns
+ *      MOJO_EUNSUPPORTED: the caller composes `steps` single-step calls on lengths len - (steps - 1 - j).                  */
+int64_t mojo_hip_paged_decode_nstep_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                    int64_t head_dim, int64_t block_size,
+                                                    int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                    int64_t local_window, int64_t global_window, int64_t steps);
+int mojo_hip_paged_decode_nstep(const void* query, const void* key_cache, const void* value_cache,
+                                const int32_t* total_seq_lens, const int32_t* block_tables,
+                                void* out, void* workspace, int64_t workspace_bytes,
+                                int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                                int64_t block_size, int64_t max_blocks_per_seq,
+                                int64_t block_table_stride, int64_t cache_block_stride,
+                                int64_t cache_head_stride, int64_t cache_token_stride,
+                                int64_t max_seq_len_hint, float softmax_scale, int layout_abab,
+                                int leave_empty_rows, int dtype, int64_t local_window,
+                                int64_t global_window, int64_t steps, mojo_stream_t stream);
+
 /* ---- int8 paged KV cache with per-channel scales ("C8"; experimental/operators/kv_cache.py:109-184,
  *      experimental/operators/attention.py:461-800).  Caches are int8 [N, Hkv, page, D] (strides in elements = bytes, 16-byte
  *      rows), scales [Hkv, D] dense, scale_dtype one of MOJO_BF16 / MOJO_F16 / MOJO_F32, taken as given (no cast launch).

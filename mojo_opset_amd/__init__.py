@@ -8,16 +8,17 @@ registers the ``HIP<Op>`` backend classes.  Backend selection follows the refere
 ``__all__`` is the SURVEY §8 set.  The ops beyond it (``BEYOND_SURVEY_OPS``, the concatenation of the named sets of
 ``core/operators/__init__.py``) are package attributes too, but not in ``__all__``; ``plugin.rebase_hip_backend``
 registers both into the reference.  The torch golden of every op, in ``__all__`` or not, is in the repo-level ``oracle/``
-package.
+package.  ``NSTEP_OPS`` (n-step paged decode) is a further set of package attributes the plugin registers; its torch golden
+is ``tests/nstep_golden.py``.
 """
 from .core import *  # noqa: F401,F403
 from .core import __all__ as _core_all
-from .core import (BEYOND_SURVEY_OPS, EXTENDED_OPS, KV_INT8_OPS, KV_INT8_SWA_OPS, QUANT_MOE_OPS,  # noqa: F401
+from .core import (BEYOND_SURVEY_OPS, EXTENDED_OPS, KV_INT8_OPS, KV_INT8_SWA_OPS, NSTEP_OPS, QUANT_MOE_OPS,  # noqa: F401
                    SAMPLING_OPS)
 from . import core as _core
 from . import backends  # noqa: F401  (registers HIP<Op> classes)
 from .paged_cache import PagedDummyCache  # noqa: E402  device-side block allocator (SURVEY §8 f4)
 
 __all__ = list(_core_all) + ["PagedDummyCache"]
-globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS})   # beyond §8: not in __all__
+globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS + NSTEP_OPS})   # beyond §8: not in __all__
 __version__ = "0.1.0"

@@ -64,6 +64,8 @@ SIGNATURES = {
     "mojo_hip_paged_decode_swa_workspace_bytes": (c_int64, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "mojo_hip_paged_decode_swa": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                                           c_float, c_int, c_int, c_int, _I, _I, _P]),
+    "mojo_hip_paged_decode_nstep_workspace_bytes": (c_int64, [_I] * 10),
+    "mojo_hip_paged_decode_nstep": (c_int, [_P] * 7 + [_I] * 12 + [c_float, c_int, c_int, c_int, _I, _I, _I, _P]),
     "mojo_hip_paged_prefill_swa_workspace_bytes": (c_int64, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "mojo_hip_paged_prefill_swa": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                                            c_float, c_int, c_int, _P, _I, _I, _I, _P]),

@@ -4,8 +4,9 @@ from typing import Optional
 
 import torch
 
-from ....core.operators.attention import (MojoPagedDecodeGQA, MojoPagedDecodeSWA, MojoPagedPrefillGQA,
-                                          MojoPagedPrefillSWA, assert_paged_decode_contract, assert_paged_prefill_contract)
+from ....core.operators.attention import (MojoPagedDecodeGQA, MojoPagedDecodeNstepSWA, MojoPagedDecodeSWA,
+                                          MojoPagedPrefillGQA, MojoPagedPrefillSWA, assert_nstep_query,
+                                          assert_paged_decode_contract, assert_paged_prefill_contract)
 from .... import switches
 from .. import lib as L
 
@@ -35,8 +36,9 @@ def _paged_decode(op, what, symbols, query, key_cache, value_cache, total_seq_le
                  max_total_seq_len, leave_empty_rows, scales=None, windows=()):
     """The host path of every paged decode op, from the opt-in table check to the launch.  ``what``: the class name in
     messages; ``symbols``: the C workspace query and entry point; ``scales``: (key_scale, value_scale) of the int8 cache,
-    dense; ``windows``: (local, global) of the SWA ABI.  The caller has checked its own contract and envelope."""
-    batch, hq, dim = query.shape
+    dense; ``windows``: (local, global) of the SWA ABI, (local, global, steps) of the n-step one, whose query is
+    ``[B, S, Hq, D]``.  The caller has checked its own contract and envelope."""
+    batch, (hq, dim) = query.shape[0], query.shape[-2:]
     hkv, page = key_cache.shape[1], key_cache.shape[2]
     if _validate_tables() and batch > 0 and block_tables.shape[1] > 0:
         if bool(((total_seq_lens > 0) & (block_tables[:, 0] < 0)).any()):
@@ -110,7 +112,7 @@ def _paged_prefill(op, what, symbols, query, key_cache, value_cache, cu_q_lens, 
 
 
 def _check_16bit_caches(what, query, key_cache, value_cache):
-    hq, dim = query.shape[1:]
+    hq, dim = query.shape[-2:]
     n_blocks, hkv, page, dim_c = key_cache.shape
     assert dim_c == dim and value_cache.shape == key_cache.shape and hq % hkv == 0
     assert query.dtype == key_cache.dtype == value_cache.dtype
@@ -119,6 +121,7 @@ def _check_16bit_caches(what, query, key_cache, value_cache):
 
 _DECODE_GQA = ("mojo_hip_paged_decode_gqa_workspace_bytes", "mojo_hip_paged_decode_gqa")
 _DECODE_SWA = ("mojo_hip_paged_decode_swa_workspace_bytes", "mojo_hip_paged_decode_swa")
+_DECODE_NSTEP = ("mojo_hip_paged_decode_nstep_workspace_bytes", "mojo_hip_paged_decode_nstep")
 _PREFILL_GQA = ("mojo_hip_paged_prefill_gqa_workspace_bytes", "mojo_hip_paged_prefill_gqa")
 _PREFILL_SWA = ("mojo_hip_paged_prefill_swa_workspace_bytes", "mojo_hip_paged_prefill_swa")
 
@@ -181,6 +184,55 @@ class HIPPagedDecodeSWA(MojoPagedDecodeSWA):
         _check_16bit_caches("HIPPagedDecodeSWA", query, key_cache, value_cache)
         return _paged_decode(self, "HIPPagedDecodeSWA", _DECODE_SWA, query, key_cache, value_cache, total_seq_lens,
                              block_table, softmax_scale, max_total_seq_len, leave_empty_rows, windows=windows)
+
+
+class HIPPagedDecodeNstepSWA(MojoPagedDecodeNstepSWA):
+    """``S`` query tokens per sequence in one pass over the paged cache: the matrix-core decode kernel with
+    (step, head) pairs in the 16 columns of its score product, so the K/V bytes are read once per block of ``16 // G`` steps.
+    ``S = 1`` is `HIPPagedDecodeSWA`, bit for bit.
+
+    Geometries that kernel does not take — ``head_dim`` other than 64 / 128, pages that are no power of two >= 16, more than
+    16 query heads per kv head, ``MOJO_HIP_DECODE_MFMA=0`` — run the COMPOSED route: ``S`` single-step launches, step ``j``
+    on ``query[:, j]`` with the lengths ``len - (S - 1 - j)`` (computed on the device: no sync, capture-safe).  It is
+    correct and costs ``S`` times the bytes.
+
+    Beyond the golden: a row with ``0 < len < S`` (the golden returns NaN) stores zeros for the steps that see no key, and
+    raises ``ValueError`` under ``MOJO_HIP_VALIDATE=1``; negative page ids are holes as in the single-step ops."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key_cache, value_cache, total_seq_lens, block_table, softmax_scale: Optional[float] = None,
+                *, max_total_seq_len: Optional[int] = None, leave_empty_rows: Optional[bool] = None):
+        what = "HIPPagedDecodeNstepSWA"
+        assert_paged_decode_contract(block_table, total_seq_lens)
+        assert_nstep_query(query)
+        if not self.is_causal:
+            raise NotImplementedError(f"{what} supports causal attention only")
+        windows = _swa_windows(self, what)
+        L.require_cuda(query, key_cache, value_cache, total_seq_lens, block_table)
+        _check_16bit_caches(what, query, key_cache, value_cache)
+        batch, steps, hq, dim = query.shape
+        if steps == 0:
+            return torch.empty_like(query)
+        if _validate_tables() and batch > 0 and bool(((total_seq_lens > 0) & (total_seq_lens < steps)).any()):
+            raise ValueError(f"{what}: a row holds fewer keys than the {steps} query steps it counts")
+        hint = int(max_total_seq_len) if max_total_seq_len is not None else 0
+        fused = L.load().mojo_hip_paged_decode_nstep_workspace_bytes(
+            batch, hq, key_cache.shape[1], dim, key_cache.shape[2], block_table.shape[1], hint, *windows, steps) >= 0
+        if fused:
+            return _paged_decode(self, what, _DECODE_NSTEP, query, key_cache, value_cache, total_seq_lens, block_table,
+                                 softmax_scale, max_total_seq_len, leave_empty_rows, windows=(*windows, steps))
+        # composed route: the single-step kernels, one launch per step.  Each call zeroes its empty rows; rows of sequences
+        # without keys are then left out of the copy where the caller keeps them (graph replay contract).
+        leave = _capturing(query) if leave_empty_rows is None else leave_empty_rows
+        out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+        keep = (total_seq_lens > 0)[:, None, None] if leave else None
+        for j in range(steps):
+            back = steps - 1 - j
+            lens_j = total_seq_lens if back == 0 else torch.where(total_seq_lens > 0, total_seq_lens - back, total_seq_lens)
+            o_j = _paged_decode(self, what, _DECODE_SWA, query[:, j], key_cache, value_cache, lens_j, block_table,
+                                softmax_scale, max_total_seq_len, False, windows=windows)
+            out[:, j] = o_j if keep is None else torch.where(keep, o_j, out[:, j])
+        return out
 
 
 class HIPPagedPrefillSWA(MojoPagedPrefillSWA):

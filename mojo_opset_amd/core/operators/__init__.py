@@ -1,5 +1,5 @@
 from .activation import MojoSwiGLU
-from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeSWA,
+from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA, MojoPagedDecodeSWA,
                         MojoPagedDecodeSWAWithKVDequant, MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
                         MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
@@ -37,3 +37,7 @@ QUANT_MOE_OPS = ("MojoMoEDynamicQuant", "MojoQuantExperts", "MojoQuantMoE")
 SAMPLING_OPS = ("MojoTopKSampling", "MojoTopPSampling", "MojoTopPFilter", "MojoRejectSampling", "MojoJoinProbRejectSampling",
                 "MojoApplyPenaltiesTempurate")
 BEYOND_SURVEY_OPS = EXTENDED_OPS + KV_INT8_OPS + KV_INT8_SWA_OPS + QUANT_MOE_OPS + SAMPLING_OPS
+# multi-token (n-step) paged decode: scores the draft run the sampling ops accept or reject.  A package attribute and a
+# plugin-registered class like the sets above, but not part of BEYOND_SURVEY_OPS: its torch golden is tests/nstep_golden.py,
+# not yet a module of `oracle/`.
+NSTEP_OPS = ("MojoPagedDecodeNstepSWA",)

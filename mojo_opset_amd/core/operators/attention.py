@@ -3,8 +3,8 @@
 Constructor arguments, contracts and `forward` signatures follow
 `mojo_opset/core/operators/attention.py` (`MojoPagedDecodeGQA` :113-232,
 `MojoPagedPrefillGQA` :315-451, contracts :12-37, `MojoPagedPrefillSWA` :533-650,
-`MojoPagedDecodeSWA` :653-744).  The classes are API-only; see
-`core/operator.py` for why the golden `forward` is not here.
+`MojoPagedDecodeSWA` :653-744) and `mojo_opset/experimental/operators/attention.py` (`MojoPagedDecodeNstepSWA`
+:1154-1262).  The classes are API-only; see `core/operator.py` for why the golden `forward` is not here.
 """
 from typing import Optional
 
@@ -104,6 +104,31 @@ class MojoPagedDecodeSWA(_PagedSWABase, MojoOperator):
 
     forward(query [B,Hq,D], key_cache/value_cache [N_blocks,Hkv,page,D], total_seq_lens [B] i32,
             block_table [B,max_blocks] i32, softmax_scale=None, *, max_total_seq_len=None) -> [B,Hq,D];
+    rows with seq_len <= 0 are zeros.
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,
+                 local_window_size: Optional[int] = None):
+        super().__init__()
+        self._init_swa(is_causal, gqa_layout, global_window_size, local_window_size)
+
+
+def assert_nstep_query(query) -> None:
+    """The n-step op's query is 4-D (reference experimental :1199-1201)."""
+    assert query.ndim == 4, (
+        f"MojoPagedDecodeNstepSWA expects 4D query [bsz, seq_len, n_q_heads, head_dim], got ndim={query.ndim}")
+
+
+class MojoPagedDecodeNstepSWA(_PagedSWABase, MojoOperator):
+    """``S`` query tokens per sequence (draft verification, multi-token prediction) against a paged KV cache, causal,
+    with the optional windows of `MojoPagedDecodeSWA`; with no window it is the n-step form of `MojoPagedDecodeGQA`.
+
+    ``total_seq_lens`` counts the ``S`` new tokens: step ``j`` of a row of ``kv_len`` keys sits at position
+    ``p = kv_len - S + j`` and sees key ``t`` iff ``t <= p`` and, when a window is set, ``t >= p - local_window_size`` or
+    ``t < global_window_size``.
+
+    forward(query [B,S,Hq,D], key_cache/value_cache [N_blocks,Hkv,page,D], total_seq_lens [B] i32,
+            block_table [B,max_blocks] i32, softmax_scale=None, *, max_total_seq_len=None) -> [B,S,Hq,D];
     rows with seq_len <= 0 are zeros.
     """
 

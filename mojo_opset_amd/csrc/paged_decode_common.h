@@ -10,6 +10,9 @@
 //   decode_lds_merge              a workgroup's partials meet in LDS: merge, normalise, store (or one partial, grouped form)
 //   decode_split_finish           split form of the matrix-core kernels: finish a single-chunk row, else leave a partial
 //   decode_softmax_step           online softmax of a matrix-core step, scores -> packed probabilities
+//   decode_lds_merge_nstep / decode_split_finish_nstep   the two epilogues over the (step, head) columns of DecodeSteps
+//                                 (functions of their own: the single-step ones, and with them every existing instance, stay
+//                                 exactly as they compile today)
 //   Store16                       the 16-bit kernels' output store (the int8 kernel has Kv8Store)
 #pragma once
 
@@ -233,6 +236,73 @@ __device__ __forceinline__ void decode_split_finish(const DecodeArgs& a, int G, 
     return;
   }
   const int64_t slot = (static_cast<int64_t>(blockIdx.y) * a.n_chunks + row.chunk) * G + tl;
+  float* dst = a.ws_acc + slot * D + 4 * g4;
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<f32x4*>(dst + dt * 16) = o[dt];
+  if (g4 == 0) {
+    a.ws_ml[slot * 2 + 0] = m;
+    a.ws_ml[slot * 2 + 1] = l;
+  }
+}
+
+// ---- the n-step epilogues (DecodeSteps) -------------------------------------------------------------------------------------
+// As decode_lds_merge<false, true> and decode_split_finish, over the NC columns of the block `st`: slot
+// s_part[wave][column][D + 2], a column's output row from decode_col_at.  A column without a step (decode_col_ok) is
+// skipped; a step that saw no key in any chunk (0 < len < steps) has maximum -inf and sum 0 and stores zeros — no weight
+// exp2(-inf - -inf), no 1 / 0; only a sequence without keys (st.len <= 0) is an empty row that a.leave_empty leaves alone.
+template <typename Store>
+__device__ __forceinline__ void decode_lds_merge_nstep(const DecodeArgs& a, const float* s_part, int D, int NC, const DecodeRow& row,
+                                                       const DecodeSteps& st, Store store) {
+  const int stride = D + 2;
+  __syncthreads();
+  const int per_col = D / 4;
+  const int uwaves = static_cast<int>(blockDim.x >> 6);
+  const int total = row.seq_len <= 0 ? 0 : row.n_chunks_seq();
+  int n_chunks_seq = min(total, uwaves);
+  bool partial = false;                                  // grouped form: this workgroup's chunks are not the whole row
+  if (a.fuse_group > 0) {
+    partial = total > uwaves;
+    n_chunks_seq = min(max(total - static_cast<int>(blockIdx.x) * uwaves, 0), uwaves);
+    if (blockIdx.x > 0 && n_chunks_seq == 0) return;     // a workgroup past the row's last chunk: nothing to leave
+  }
+  if (n_chunks_seq == 0 && a.leave_empty && st.len <= 0) return;
+  for (int item = threadIdx.x; item < NC * per_col; item += blockDim.x) {
+    const int c = item / per_col, d0 = (item - c * per_col) * 4;
+    if (!decode_col_ok(st, c)) continue;
+    float mx = -INFINITY;
+    for (int w = 0; w < n_chunks_seq; ++w) mx = fmaxf(mx, s_part[(w * NC + c) * stride + D]);
+    if (mx == -INFINITY) mx = 0.f;
+    f32x4 num = {0.f, 0.f, 0.f, 0.f};
+    float den = 0.f;
+    for (int w = 0; w < n_chunks_seq; ++w) {
+      const float* src = s_part + (w * NC + c) * stride;
+      const float wt = exp2f(src[D] - mx);
+      den = fmaf(wt, src[D + 1], den);
+      num += f32x4{src[d0], src[d0 + 1], src[d0 + 2], src[d0 + 3]} * wt;
+    }
+    if (partial) {                                       // un-normalised sums against this workgroup's maximum, for the merge launch
+      const int64_t slot = (static_cast<int64_t>(blockIdx.y) * a.n_chunks + blockIdx.x) * NC + c;
+      *reinterpret_cast<f32x4*>(a.ws_acc + slot * D + d0) = num;
+      if (d0 == 0) { a.ws_ml[slot * 2 + 0] = mx; a.ws_ml[slot * 2 + 1] = den; }
+      continue;
+    }
+    store(decode_col_at(a, st, c) + d0, num * (den > 0.f ? 1.0f / den : 0.f));
+  }
+}
+
+template <int ND, typename Store>
+__device__ __forceinline__ void decode_split_finish_nstep(const DecodeArgs& a, int NC, const DecodeRow& row, const DecodeSteps& st,
+                                                          int tl, int g4, const f32x4 (&o)[ND], float m, float l, Store store) {
+  constexpr int D = ND * 16;
+  if (!decode_col_ok(st, tl)) return;
+  if (row.n_chunks_seq() == 1) {
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    const int64_t at = decode_col_at(a, st, tl) + 4 * g4;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) store(at + dt * 16, o[dt] * inv);
+    return;
+  }
+  const int64_t slot = (static_cast<int64_t>(blockIdx.y) * a.n_chunks + row.chunk) * NC + tl;
   float* dst = a.ws_acc + slot * D + 4 * g4;
 #pragma unroll
   for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<f32x4*>(dst + dt * 16) = o[dt];

@@ -133,6 +133,9 @@ __device__ __forceinline__ int decode_seq_chunk(const DecodeArgs& a, int seq_len
 // max_len / 4 tokens; a long row paired with a short one leaves every wave ~(len_long + len_short) / 8, the batch mean / 4.
 // A uniform batch gets 4 + 4 waves per pair, i.e. exactly the MODE 1 work per wave.
 constexpr int DEC_SPLIT = 0, DEC_FUSED = 1, DEC_PAIRED = 2;
+// The `int G` argument of decode_mfma_nstep_kernel: heads per kv head, query rows per sequence (< 2^16), and whether the hole scan
+// runs (no window set) — see DecodeSteps for why these are not fields of DecodeArgs.
+constexpr int decode_nstep_arg(int G, int steps, int scan_holes) { return G | (steps << 8) | (scan_holes << 24); }
 
 // query head of (grid kv head kvh, head g of the kernel's G).  With hshift = 1 the grid's kv heads are the halves of the real
 // ones: real kv head kvh >> 1, heads (kvh & 1) * G + g of its 2 G.
@@ -140,6 +143,73 @@ __device__ __forceinline__ int decode_head(const DecodeArgs& a, int kvh, int g, 
   if (!a.abab) return kvh * G + g;                        // AABB: (real kv head, half, g) is already kvh * G + g
   const int real = kvh >> a.hshift, half = kvh & ((1 << a.hshift) - 1);
   return (half * G + g) * (a.hkv >> a.hshift) + real;
+}
+
+// N-step decode (MojoPagedDecodeNstepSWA): S query rows per sequence, step j at position len - S + j; key t is
+// visible to it iff t <= len - S + j and (no window, or t < global, or t >= len - S + j - local).  The 16 columns of the
+// matrix-core kernel's score product hold (step, head) pairs: a grid row owns a BLOCK of SB = 16 / G consecutive steps of one
+// (sequence, kv head), column c = (step c / G of the block, head c % G), C = SB * G columns in all.  With S > SB the blocks of
+// a (sequence, kv head) are grid rows of their own — row y = ((b * hkv) + kvh) * blocks + block — and each streams K/V itself.
+// A block of `nst` steps whose last step sees `len_e` keys is an nst-step problem on len_e keys, so the window of a block is a
+// DecodeWin with `lo` the lower edge of its FIRST step and the local range running to len_e: both staircases (the last
+// nst - 1 keys, and the local window's lower edges lo_k = max(len_e - nst + k - local, 0)) lie inside the walked range and are
+// masked per lane, a lane owning one column.  No window runs as a local window of the launch capacity (lo = 0, no gap).
+// S is an argument of the n-step kernels, not a field of DecodeArgs: a longer DecodeArgs moves the kernel arguments of every
+// decode kernel, and the compiler then groups their loads differently — the single-step instances would not compile to what
+// they compile to today.
+struct DecodeSteps {
+  int S = 1;                        // query rows per sequence
+  int b = 0, kvh = 0;               // sequence and grid kv head of the row
+  int j0 = 0, nst = 1;              // first step of the block, steps in it
+  int len = 0;                      // the sequence's length (len <= 0: an empty row, left or zeroed as a whole)
+  int lo_last = 0, gl = 0;          // lower edge of the block's last step; the global window as given (>= 0)
+  int G = 1;                        // query heads per kv head
+};
+__device__ __forceinline__ int decode_nstep_blocks(int steps, int G) { const int sb = 16 / G; return (steps + sb - 1) / sb; }
+__device__ __forceinline__ int decode_nstep_row(const DecodeArgs& a, int y, int G, int steps, DecodeWin& w, DecodeSteps& st) {
+  st.G = G;
+  st.S = steps;
+  const int sb = 16 / G, nb = decode_nstep_blocks(steps, G);
+  const int bh = y / nb, blk = y - bh * nb;
+  st.b = bh / a.hkv;
+  st.kvh = bh - st.b * a.hkv;
+  st.j0 = blk * sb;
+  st.nst = min(sb, steps - st.j0);
+  st.len = __builtin_amdgcn_readfirstlane(max(min(a.seq_lens[st.b], a.swa_cap), 0));
+  const int len_e = max(st.len - (steps - st.j0 - st.nst), 0);     // keys the block's last step sees
+  w.lo = a.local_win >= 0 ? max(len_e - st.nst - a.local_win, 0) : len_e;
+  st.lo_last = __builtin_amdgcn_readfirstlane(a.local_win >= 0 ? max(len_e - 1 - a.local_win, 0) : len_e);
+  st.gl = max(a.global_win, 0);
+  // the virtual range: as decode_swa_row, on len_e keys from the first step's lower edge
+  w.len = len_e;
+  w.g1 = min(st.gl, w.lo);
+  w.g_al = (w.g1 + DEC_TILE - 1) & ~(DEC_TILE - 1);
+  w.gap = 0;
+  int vlen = len_e;
+  if (w.lo >= len_e) {
+    vlen = w.g1;                                         // no local range: the global range alone
+  } else {
+    const int lo_al = w.lo & ~(DEC_TILE - 1);
+    if (lo_al > w.g_al) { w.gap = lo_al - w.g_al; vlen = len_e - w.gap; }
+  }
+  w.len = __builtin_amdgcn_readfirstlane(w.len);
+  w.g1 = __builtin_amdgcn_readfirstlane(w.g1);
+  w.lo = __builtin_amdgcn_readfirstlane(w.lo);
+  w.g_al = __builtin_amdgcn_readfirstlane(w.g_al);
+  w.gap = __builtin_amdgcn_readfirstlane(w.gap);
+  return __builtin_amdgcn_readfirstlane(min(vlen, a.n_chunks * a.chunk_tokens));
+}
+// column c of a block: valid (it holds a step of the block), its step within the block, its head
+__device__ __forceinline__ bool decode_col_ok(const DecodeSteps& st, int c) { return c < st.nst * st.G; }
+// element offset of column c's row in the [B][S][Hq][D] query / output (c valid)
+__device__ __forceinline__ int64_t decode_col_at(const DecodeArgs& a, const DecodeSteps& st, int c) {
+  const int k = c / st.G, g = c - k * st.G;
+  return ((static_cast<int64_t>(st.b) * st.S + st.j0 + k) * a.hq + decode_head(a, st.kvh, g, st.G)) * a.dim;
+}
+// a tile at real token rt0 every key of which every step of the block sees (else it is masked per lane)
+__device__ __forceinline__ bool decode_nstep_edge(const DecodeWin& w, const DecodeSteps& st, int rt0) {
+  const bool all_vis = rt0 + DEC_TILE <= w.len - st.nst + 1 && (rt0 + DEC_TILE <= st.gl || rt0 >= st.lo_last);
+  return !all_vis;
 }
 
 }  // namespace mojo
@@ -477,6 +547,66 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(DecodeArgs a, int G) 
   *reinterpret_cast<V4*>(dst) = o;
 }
 
+// The merge of the n-step launches: grid = (B*Hkv*blocks, C) — a row is a block of steps (DecodeSteps), blockIdx.y a column of
+// it, G the heads per kv head; otherwise decode_merge_kernel.  A step that saw no key (0 < len < steps) stores zeros.
+template <typename T>
+__global__ __launch_bounds__(256) void decode_merge_nstep_kernel(DecodeArgs a, int G, int steps) {
+  __shared__ float s_mx[8], s_den[8];
+  __shared__ f32x4 s_num[8][32];
+  const int c = blockIdx.y, cols = static_cast<int>(gridDim.y);
+  DecodeWin w;
+  DecodeSteps st;
+  const int seq_len = decode_nstep_row(a, blockIdx.x, G, steps, w, st);
+  if (!decode_col_ok(st, c)) return;                     // (workgroup-uniform, like every return in front of the barriers)
+  const int chunk_tokens = decode_seq_chunk(a, seq_len);
+  int n_chunks_seq = seq_len <= 0 ? 0 : (seq_len + chunk_tokens - 1) / chunk_tokens;
+  if (a.fuse_group > 0) n_chunks_seq = (n_chunks_seq + a.fuse_group - 1) / a.fuse_group;
+  if (n_chunks_seq == 1) return;
+  const int cl = threadIdx.x >> 5, dt = threadIdx.x & 31;
+  const int d0 = dt * 4;
+  const bool live = d0 < a.dim;
+  T* dst = static_cast<T*>(a.out) + decode_col_at(a, st, c) + d0;
+  typedef typename vec_of<T, 4>::type V4;
+  if (n_chunks_seq == 0) {
+    if ((a.leave_empty && st.len <= 0) || cl != 0 || !live) return;
+    V4 z = {};
+    *reinterpret_cast<V4*>(dst) = z;
+    return;
+  }
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * a.n_chunks * cols + c;
+  float mx = -INFINITY;
+  for (int k = cl; k < n_chunks_seq; k += 8) mx = fmaxf(mx, a.ws_ml[(base + static_cast<int64_t>(k) * cols) * 2]);
+  if (dt == 0) s_mx[cl] = mx;
+  __syncthreads();
+  mx = s_mx[0];
+#pragma unroll
+  for (int j = 1; j < 8; ++j) mx = fmaxf(mx, s_mx[j]);
+  if (mx == -INFINITY) mx = 0.f;                         // no key in any chunk: weights exp2(-inf) = 0, not NaN
+  f32x4 num = {0.f, 0.f, 0.f, 0.f};
+  float den = 0.f;
+#pragma unroll 4
+  for (int k = cl; k < n_chunks_seq; k += 8) {
+    const int64_t slot = base + static_cast<int64_t>(k) * cols;
+    const float wt = exp2f(a.ws_ml[slot * 2] - mx);
+    den = fmaf(wt, a.ws_ml[slot * 2 + 1], den);
+    if (live) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(a.ws_acc + slot * a.dim + d0);
+      num += x * wt;
+    }
+  }
+  s_num[cl][dt] = num;
+  if (dt == 0) s_den[cl] = den;
+  __syncthreads();
+  if (cl != 0 || !live) return;
+#pragma unroll
+  for (int j = 1; j < 8; ++j) { num += s_num[j][dt]; den += s_den[j]; }
+  const float inv = den > 0.f ? 1.0f / den : 0.f;
+  V4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = static_cast<T>(num[e] * inv);
+  *reinterpret_cast<V4*>(dst) = o;
+}
+
 static int decode_chunk_tokens(int64_t batch, int64_t kv_heads, int64_t max_len, bool grouped = false) {
   {                                                            // tuning override
     const int v = static_cast<int>(MOJO_SWITCH("MOJO_HIP_DECODE_CHUNK", 0));
@@ -514,10 +644,11 @@ static int64_t decode_max_len(int64_t page, int64_t max_pages, int64_t hint) {
 }
 
 // Sliding window: the most virtual tokens (DecodeWin) a row of a launch of real capacity `max_len` can walk — the global
-// range rounded up to a tile plus the local window's local + 1 keys and the tile they start in.
-static int64_t decode_swa_cap(int64_t max_len, int64_t local_window, int64_t global_window) {
+// range rounded up to a tile plus the local window's local + 1 keys and the tile they start in.  With `steps` query rows
+// (DecodeSteps) the local range of a block runs from its first step's lower edge to its last step's key: steps - 1 more.
+static int64_t decode_swa_cap(int64_t max_len, int64_t local_window, int64_t global_window, int64_t steps = 1) {
   int64_t span = global_window > 0 ? ceil_div(global_window, DEC_TILE) * DEC_TILE : 0;
-  if (local_window >= 0) span += local_window + DEC_TILE;
+  if (local_window >= 0) span += local_window + DEC_TILE + (steps - 1);
   return span < max_len ? span : max_len;
 }
 
@@ -542,6 +673,7 @@ struct DecodeGeom {
   int64_t batch = 0, q_heads = 0, kv_heads = 0, head_dim = 0, page = 0, max_pages = 0, len_hint = 0;
   int64_t local_window = -1, global_window = 0;
   bool kv8 = false;                 // the int8-cache op (paged_decode_kv8.h): its own kernel, never grouped, paired or halved
+  int64_t steps = 1;                // query rows per sequence (> 1: the n-step op, DecodeSteps; matrix-core kernel only)
 };
 
 struct DecodePlan {
@@ -553,22 +685,48 @@ struct DecodePlan {
   int hshift = 0, grid_kv_heads = 0, G = 0;             // kv heads the grid sees (= kv_heads << hshift) and query heads per grid kv head
   int64_t slots = 0;                // partials the launch may write: batch * grid_kv_heads * n_chunks * G
   int64_t bytes = 0;                // workspace the launch needs
-  int64_t query_bytes = 0;          // what the workspace query answers (0: degenerate geometry)
+  int64_t query_bytes = 0;          // what the workspace query answers (0: degenerate geometry; -1: no n-step kernel for it)
+  bool nstep = false;               // the n-step instances run (steps > 1): grid rows are blocks of steps, partials hold `cols` columns
+  int row_blocks = 1, cols = 0;     // blocks of steps per (sequence, kv head); columns of a partial (single step: G)
+  int steps = 1, scan_holes = 0;    // the n-step kernels' own arguments (decode_nstep_arg)
 };
+
+// The n-step op runs on the matrix-core kernel alone (its 16 columns are what holds the steps): the geometries that kernel
+// takes, and MOJO_HIP_DECODE_MFMA as for the single-step op — 0 = never (callers then compose single-step launches),
+// 1 = wherever it applies, unset = where it measured faster than `steps` single-step launches.
+static bool decode_nstep_fused(const DecodeGeom& g) {
+  if (g.kv8 || g.kv_heads <= 0 || g.q_heads % g.kv_heads != 0) return false;
+  const int64_t G = g.q_heads / g.kv_heads;
+  const bool pow2 = g.page > 0 && (g.page & (g.page - 1)) == 0;
+  if (!pow2 || g.page < 16 || (g.head_dim != 64 && g.head_dim != 128) || G > 16) return false;
+  return MOJO_SWITCH("MOJO_HIP_DECODE_MFMA", -1) != 0;
+}
+
 
 static DecodePlan decode_plan(const DecodeGeom& g) {
   DecodePlan p;
-  p.swa = g.local_window >= 0 || g.global_window > 0;
+  const bool window = g.local_window >= 0 || g.global_window > 0;
+  p.nstep = g.steps > 1;
+  p.swa = window || p.nstep;                              // (the n-step instances are windowed ones: no window = the capacity)
   if (g.batch <= 0 || g.kv_heads <= 0 || g.q_heads <= 0) return p;
+  if (p.nstep && !decode_nstep_fused(g)) { p.query_bytes = -1; return p; }   // not a geometry of the n-step kernel
   p.capacity = decode_max_len(g.page, g.max_pages, g.len_hint);
-  p.max_len = p.swa ? decode_swa_cap(p.capacity, g.local_window, g.global_window) : p.capacity;
+  p.max_len = !p.swa ? p.capacity : decode_swa_cap(p.capacity, window ? g.local_window : p.capacity, g.global_window, g.steps);
   const int64_t heads = g.q_heads / g.kv_heads;
+  p.cols = static_cast<int>(heads);
+  if (p.nstep) {
+    const int64_t sb = 16 / heads;                        // steps of a block (DecodeSteps)
+    p.row_blocks = static_cast<int>(ceil_div(g.steps, sb));
+    p.cols = static_cast<int>(sb * heads);
+    p.steps = static_cast<int>(g.steps);
+    p.scan_holes = window ? 0 : 1;                        // no window: negative page ids are holes, as in the GQA op
+  }
   // One form of the launch: the heads of a kv head together (hshift 0) or as two halves on twice the grid heads (hshift 1).
   auto form = [&](int hshift, DecodePlan& f) {
     f.hshift = hshift;
     f.grid_kv_heads = static_cast<int>(g.kv_heads << hshift);
     f.G = static_cast<int>(heads >> hshift);
-    f.mfma = !g.kv8 && decode_use_mfma(f.G, g.head_dim, g.page);
+    f.mfma = p.nstep || (!g.kv8 && decode_use_mfma(f.G, g.head_dim, g.page));
     // The grouped form (DecodeArgs::fuse_group; matrix-core kernel only) — MOJO_HIP_DECODE_GROUPED=0 restores the split + merge form.
     // Measured (scripts/probes/decode_grouped_ab.py, profiles/r4_decode_grouped_ab.txt; split + merge form -> grouped form, graph
     // replay): 8 q / 1 kv heads B 64 ctx 4096 (Llama-3-70B under TP 8) 33.6 -> 28.1 us, B 16 ctx 16384 38.2 -> 29.8 us; 32 / 8 heads
@@ -576,10 +734,10 @@ static DecodePlan decode_plan(const DecodeGeom& g) {
     // (the grouped launch exists in the fused form only: without MOJO_HIP_DECODE_FUSE the chunks are sized, written and merged
     // one by one — ADVICE r4: the merge kernel divided the chunk count by the group size although every chunk had its partial)
     const bool grouped = f.mfma && MOJO_SWITCH("MOJO_HIP_DECODE_GROUPED", 1) != 0 && MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) != 0;
-    f.chunk_tokens = decode_chunk_tokens(g.batch, f.grid_kv_heads, p.max_len, grouped);
+    f.chunk_tokens = decode_chunk_tokens(g.batch * p.row_blocks, f.grid_kv_heads, p.max_len, grouped);
     f.n_chunks = static_cast<int>(ceil_div(p.max_len > 0 ? p.max_len : 1, f.chunk_tokens));
     f.fuse_group = grouped && f.n_chunks > 8 ? 8 : 0;    // (the merge divides by it: set only where the grouped launch is taken)
-    f.slots = g.batch * g.kv_heads * f.n_chunks * heads;
+    f.slots = g.batch * g.kv_heads * p.row_blocks * f.n_chunks * p.cols;
   };
   // Groups of 8 query heads per kv head (Llama-3-70B: 64 / 8).  Round 2 ran them as two 4-head halves on twice as many grid
   // heads (twice the K/V bytes: 360 us at B 64, ctx 4096) because the 8-head instance spilled; the instance now walks its heads
@@ -603,11 +761,21 @@ static DecodePlan decode_plan(const DecodeGeom& g) {
   return p;
 }
 
-template <typename T, bool NT, int MODE, bool SWA>
-static void launch_decode_mfma(const DecodeArgs& a, dim3 grid, dim3 block, int G, hipStream_t s) {
+// (`cols`: columns of a partial — G, or the n-step block's 16 / G * G)
+template <typename T, bool NT, int MODE, bool SWA, bool NSTEP = false>
+static void launch_decode_mfma(const DecodeArgs& a, dim3 grid, dim3 block, int G, int cols, hipStream_t s) {
   const size_t waves = block.x / 64;
-  const size_t lds = (MODE != DEC_SPLIT ? waves * G * (a.dim + 2) * sizeof(float) : 0) + waves * 4096;   // + one 4 KiB V image (set) per wave
+  const size_t lds = (MODE != DEC_SPLIT ? waves * cols * (a.dim + 2) * sizeof(float) : 0) + waves * 4096;   // + one 4 KiB V image (set) per wave
   static std::atomic<uint64_t> attr_set{0};             // (per instantiation: dynamic LDS beyond 64 KiB needs the attribute)
+  if constexpr (NSTEP) {
+    if (first_call_on_device(attr_set)) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_nstep_kernel<T, 4, NT, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_nstep_kernel<T, 2, NT, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    }
+    if (a.dim == 128) hipLaunchKernelGGL((decode_mfma_nstep_kernel<T, 4, NT, MODE>), grid, block, lds, s, a, G);
+    else hipLaunchKernelGGL((decode_mfma_nstep_kernel<T, 2, NT, MODE>), grid, block, lds, s, a, G);
+    return;
+  }
   if (first_call_on_device(attr_set)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_kernel<T, 4, NT, MODE, SWA>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_mfma_kernel<T, 2, NT, MODE, SWA>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -630,10 +798,12 @@ static int dispatch_G(int G, F&& f) {
 }
 
 // One launch of kernel mode MODE on either route (`what`: the launch's name in an error message).
-template <typename T, bool NT, int MODE, bool SWA>
+template <typename T, bool NT, int MODE, bool SWA, bool NSTEP = false>
 static int launch_decode_mode(const DecodeArgs& a, const DecodePlan& p, dim3 grid, dim3 block, const char* what, hipStream_t s) {
-  if (p.mfma) {
-    launch_decode_mfma<T, NT, MODE, SWA>(a, grid, block, p.G, s);
+  if constexpr (NSTEP) {                                // (planned on the matrix-core kernel alone)
+    launch_decode_mfma<T, NT, MODE, SWA, true>(a, grid, block, decode_nstep_arg(p.G, p.steps, p.scan_holes), p.cols, s);
+  } else if (p.mfma) {
+    launch_decode_mfma<T, NT, MODE, SWA>(a, grid, block, p.G, p.cols, s);
   } else {
     const size_t waves = block.x / 64;                  // [waves][G][dim + 2] partials, and the 8-head instance's query slices
     const size_t lds = MODE == DEC_SPLIT ? 0 : waves * p.G * (a.dim + 2) * sizeof(float) + (p.G >= 8 ? waves * p.G * DEC_LPT * 16 : 0);
@@ -647,7 +817,7 @@ static int launch_decode_mode(const DecodeArgs& a, const DecodePlan& p, dim3 gri
   return MOJO_OK;
 }
 
-template <typename T, bool NT, bool SWA>
+template <typename T, bool NT, bool SWA, bool NSTEP>
 static int launch_decode_nt(const DecodeArgs& a, const DecodePlan& p, hipStream_t s) {
   const int64_t batch = a.batch;
   const bool fuse = MOJO_SWITCH("MOJO_HIP_DECODE_FUSE", 1) != 0;
@@ -664,7 +834,7 @@ static int launch_decode_nt(const DecodeArgs& a, const DecodePlan& p, hipStream_
   // their chunks in LDS and leave one partial each, so the launch keeps two waves per SIMD busy and the merge reads
   // n_chunks / 8 partials per row
   else if (wg_forms && p.mfma && a.fuse_group > 0) form = GROUPED;
-  const unsigned rows = static_cast<unsigned>(batch * a.hkv);
+  const unsigned rows = static_cast<unsigned>(batch * a.hkv * p.row_blocks);
   static const char* const tags[] = {"paired", "fused", "grouped+merge", "split+merge"};
   static const char* const whats[2][4] = {
       {"paged_decode_gqa(paired)", "paged_decode_gqa(fused)", "paged_decode_gqa(grouped)", "paged_decode_gqa(split)"},
@@ -676,32 +846,34 @@ static int launch_decode_nt(const DecodeArgs& a, const DecodePlan& p, hipStream_
       rc = launch_decode_mode<T, NT, DEC_PAIRED, false>(a, p, dim3(1, static_cast<unsigned>(((batch + 1) / 2) * a.hkv)), dim3(512), what, s);
       break;
     case FUSED:
-      rc = launch_decode_mode<T, NT, DEC_FUSED, SWA>(a, p, dim3(1, rows), dim3(static_cast<unsigned>(64 * a.n_chunks)), what, s);
+      rc = launch_decode_mode<T, NT, DEC_FUSED, SWA, NSTEP>(a, p, dim3(1, rows), dim3(static_cast<unsigned>(64 * a.n_chunks)), what, s);
       break;
     case GROUPED:
-      rc = launch_decode_mode<T, NT, DEC_FUSED, SWA>(a, p, dim3(static_cast<unsigned>((a.n_chunks + a.fuse_group - 1) / a.fuse_group), rows),
+      rc = launch_decode_mode<T, NT, DEC_FUSED, SWA, NSTEP>(a, p, dim3(static_cast<unsigned>((a.n_chunks + a.fuse_group - 1) / a.fuse_group), rows),
                                                      dim3(static_cast<unsigned>(64 * a.fuse_group)), what, s);
       break;
     case SPLIT:
-      rc = launch_decode_mode<T, NT, DEC_SPLIT, SWA>(a, p, dim3(static_cast<unsigned>(a.n_chunks), rows), dim3(64), what, s);
+      rc = launch_decode_mode<T, NT, DEC_SPLIT, SWA, NSTEP>(a, p, dim3(static_cast<unsigned>(a.n_chunks), rows), dim3(64), what, s);
       break;
   }
   if (rc != MOJO_OK) return rc;
   if (form == GROUPED || form == SPLIT) {
-    hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(rows, p.G), dim3(256), 0, s, a, p.G);
+    if constexpr (NSTEP) hipLaunchKernelGGL((decode_merge_nstep_kernel<T>), dim3(rows, p.cols), dim3(256), 0, s, a, p.G, p.steps);
+    else hipLaunchKernelGGL((decode_merge_kernel<T, SWA>), dim3(rows, p.G), dim3(256), 0, s, a, p.G);
     MOJO_CHECK_LAUNCH("paged_decode_gqa(merge)");
   }
-  note_launch("%s:%s:%s%s", p.mfma ? "decode_mfma" : "decode_valu", tags[form], NT ? "nt" : "cached", SWA ? ":swa" : "");
+  note_launch("%s:%s:%s%s", p.mfma ? "decode_mfma" : "decode_valu", tags[form], NT ? "nt" : "cached",
+              NSTEP ? ":nstep" : SWA ? ":swa" : "");
   return MOJO_OK;
 }
 
-template <typename T, bool SWA>
+template <typename T, bool SWA, bool NSTEP = false>
 static int launch_decode(const DecodeArgs& a, const DecodePlan& p, hipStream_t s) {
   // K/V are read exactly once: non-temporal loads keep them from displacing the block tables and
   // partials in L2/MALL (measured on MI355X, B=64 ctx=4096: 204 -> 190 us).  MOJO_HIP_STREAM_NT=0 disables (the switch of every
   // streaming kernel, common.h stream_nt()).
   const bool nt = MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0;
-  return nt ? launch_decode_nt<T, true, SWA>(a, p, s) : launch_decode_nt<T, false, SWA>(a, p, s);
+  return nt ? launch_decode_nt<T, true, SWA, NSTEP>(a, p, s) : launch_decode_nt<T, false, SWA, NSTEP>(a, p, s);
 }
 
 }  // namespace mojo
@@ -745,6 +917,7 @@ static int decode_set_window(DecodeArgs& a, const DecodeCall& c, const DecodePla
   a.swa_cap = static_cast<int>(p.capacity);
   a.local_win = g.local_window >= 0 ? static_cast<int>(g.local_window) : -1;
   a.global_win = g.global_window > 0 ? static_cast<int>(g.global_window) : 0;
+  if (p.nstep && p.scan_holes) a.local_win = static_cast<int>(p.capacity);   // no window: a local window of the capacity
   return MOJO_OK;
 }
 
@@ -768,7 +941,7 @@ static int decode_fill_args(DecodeArgs& a, const DecodeCall& c, const DecodePlan
 
 // The GQA and SWA entry points share one body: with SWA the launch is planned on the visible capacity (decode_swa_cap), the
 // windowed kernel instances run, and the paired and halved forms are not taken.
-template <bool SWA>
+template <bool SWA, bool NSTEP = false>
 static int paged_decode_planned(const DecodeCall& c, const DecodePlan& p) {
   const DecodeGeom& g = c.g;
   if (const int rc = decode_check_call(c, "paged_decode_gqa"); rc != MOJO_OK) return rc;
@@ -786,7 +959,7 @@ static int paged_decode_planned(const DecodeCall& c, const DecodePlan& p) {
   }
   if (const int rc = decode_fill_args(a, c, p, "paged_decode_gqa"); rc != MOJO_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(c.stream);
-  return c.dtype == MOJO_BF16 ? launch_decode<bf16_t, SWA>(a, p, s) : launch_decode<f16_t, SWA>(a, p, s);
+  return c.dtype == MOJO_BF16 ? launch_decode<bf16_t, SWA, NSTEP>(a, p, s) : launch_decode<f16_t, SWA, NSTEP>(a, p, s);
 }
 
 static int paged_decode(const DecodeCall& c) {
@@ -841,6 +1014,51 @@ extern "C" int mojo_hip_paged_decode_swa(const void* query, const void* key_cach
   c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
   c.leave_empty_rows = leave_empty_rows; c.dtype = dtype;
   return paged_decode(c);
+}
+
+// N-step decode: the SWA entry point's arguments plus `steps`; query and out are [batch][steps][q_heads][head_dim].
+extern "C" int64_t mojo_hip_paged_decode_nstep_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                               int64_t head_dim, int64_t block_size,
+                                                               int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                               int64_t local_window, int64_t global_window, int64_t steps) {
+  if (steps < 1) return -1;
+  DecodeGeom g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window, global_window};
+  g.steps = steps;
+  return decode_plan(g).query_bytes;
+}
+
+extern "C" int mojo_hip_paged_decode_nstep(const void* query, const void* key_cache, const void* value_cache,
+                                           const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                           void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                           int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                           int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                           int64_t cache_block_stride, int64_t cache_head_stride,
+                                           int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                           int layout_abab, int leave_empty_rows, int dtype, int64_t local_window,
+                                           int64_t global_window, int64_t steps, mojo_stream_t stream) {
+  MOJO_REQUIRE(steps >= 1 && steps < (int64_t{1} << 16), MOJO_EINVAL, "paged_decode_nstep: steps %lld", (long long)steps);
+  if (steps == 1)                                         // one step: the single-step op itself, same plan, bit for bit
+    return mojo_hip_paged_decode_swa(query, key_cache, value_cache, total_seq_lens, block_tables, out, workspace, workspace_bytes,
+                                     batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, block_table_stride,
+                                     cache_block_stride, cache_head_stride, cache_token_stride, max_seq_len_hint, softmax_scale,
+                                     layout_abab, leave_empty_rows, dtype, local_window, global_window, stream);
+  DecodeCall c;
+  c.query = query; c.key_cache = key_cache; c.value_cache = value_cache; c.total_seq_lens = total_seq_lens; c.block_tables = block_tables;
+  c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  c.g = {batch, q_heads, kv_heads, head_dim, block_size, max_blocks_per_seq, max_seq_len_hint, local_window, global_window};
+  c.g.steps = steps;
+  c.block_table_stride = block_table_stride; c.cache_block_stride = cache_block_stride; c.cache_head_stride = cache_head_stride;
+  c.cache_token_stride = cache_token_stride; c.softmax_scale = softmax_scale; c.layout_abab = layout_abab;
+  c.leave_empty_rows = leave_empty_rows; c.dtype = dtype;
+  if (batch == 0) return MOJO_OK;
+  if (const int rc = decode_check_call(c, "paged_decode_nstep"); rc != MOJO_OK) return rc;
+  const DecodePlan p = decode_plan(c.g);
+  MOJO_REQUIRE(p.query_bytes >= 0, MOJO_EUNSUPPORTED,
+               "paged_decode_nstep: not a geometry of the n-step kernel (head_dim 64 / 128, power-of-two pages >= 16, groups <= 16, "
+               "MOJO_HIP_DECODE_MFMA != 0): compose single-step calls");
+  MOJO_REQUIRE(batch * kv_heads * p.row_blocks <= 65535, MOJO_EUNSUPPORTED, "paged_decode_nstep: batch*kv_heads*step blocks %lld exceeds the grid limit",
+               (long long)(batch * kv_heads * p.row_blocks));
+  return paged_decode_planned<true, true>(c, p);
 }
 
 #include "paged_decode_kv8.h"
