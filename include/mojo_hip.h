@@ -491,6 +491,29 @@ int mojo_hip_paged_prefill_swa_kv8(const void* query, const void* key_cache, con
                                    void* workspace, int64_t workspace_bytes, int64_t local_window,
                                    int64_t global_window, mojo_stream_t stream);
 
+/* ---- MojoPagedDecodeNstepSWAWithKVDequant: `steps` query rows per sequence over the int8 cache.  The arguments of
+ *      mojo_hip_paged_decode_swa_kv8 plus `steps`; query and out are [batch][steps][q_heads][head_dim] dense; lengths, step
+ *      positions, visibility, empty rows, dead steps (0 < len < steps: zeros) and holes as mojo_hip_paged_decode_nstep; the
+ *      arithmetic is that of the single-step int8 kernel.  steps == 1 IS mojo_hip_paged_decode_swa_kv8 (same plan, same
+ *      workspace, bit for bit).  steps > 1 takes the geometries of the single-step int8 kernel (head_dim 64 / 80 / 96 / 128,
+ *      pages of a multiple of 16 tokens, groups of <= 16 heads) with MOJO_HIP_DECODE_MFMA != 0; for every other geometry the
+ *      workspace query answers -1 and the entry point returns MOJO_EUNSUPPORTED: the caller composes `steps` single-step
+ *      calls on lengths len - (steps - 1 - j).  batch * kv_heads * ceil(steps / (16 / group)) above 65535: MOJO_EUNSUPPORTED. */
+int64_t mojo_hip_paged_decode_nstep_kv8_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads,
+                                                        int64_t head_dim, int64_t block_size,
+                                                        int64_t max_blocks_per_seq, int64_t max_seq_len_hint,
+                                                        int64_t local_window, int64_t global_window, int64_t steps);
+int mojo_hip_paged_decode_nstep_kv8(const void* query, const void* key_cache, const void* key_scale,
+                                    const void* value_cache, const void* value_scale,
+                                    const int32_t* total_seq_lens, const int32_t* block_tables, void* out,
+                                    void* workspace, int64_t workspace_bytes, int64_t batch, int64_t q_heads,
+                                    int64_t kv_heads, int64_t head_dim, int64_t block_size,
+                                    int64_t max_blocks_per_seq, int64_t block_table_stride,
+                                    int64_t cache_block_stride, int64_t cache_head_stride,
+                                    int64_t cache_token_stride, int64_t max_seq_len_hint, float softmax_scale,
+                                    int layout_abab, int leave_empty_rows, int dtype, int scale_dtype,
+                                    int64_t local_window, int64_t global_window, int64_t steps, mojo_stream_t stream);
+
 /* ---- MoE routing either side of the grouped GEMM (core/operators/moe.py).
  *      gating (:299-316): softmax(hidden.float() @ gate_weight [hidden, E] fp32) over all experts, top-k in descending
  *      order (ties: lowest expert id), gates renormalised to sum 1.  top_k <= min(E, 64), E <= 1024.  With many

@@ -79,6 +79,8 @@ SIGNATURES = {
     "mojo_hip_paged_decode_swa_kv8": (c_int, [_P] * 9 + [_I] * 12 + [c_float, c_int, c_int, c_int, c_int, _I, _I, _P]),
     "mojo_hip_paged_prefill_swa_kv8_workspace_bytes": (c_int64, [_I] * 11),
     "mojo_hip_paged_prefill_swa_kv8": (c_int, [_P] * 9 + [_I] * 14 + [c_float, c_int, c_int, c_int, _P, _I, _I, _I, _P]),
+    "mojo_hip_paged_decode_nstep_kv8_workspace_bytes": (c_int64, [_I] * 10),
+    "mojo_hip_paged_decode_nstep_kv8": (c_int, [_P] * 9 + [_I] * 12 + [c_float, c_int, c_int, c_int, c_int, _I, _I, _I, _P]),
     "mojo_hip_group_gemm_workspace_bytes": (c_int64, [_I]),
     "mojo_hip_group_gemm": (c_int, [_P, _P, _P, _P, c_int, _I, _I, _I, _I, c_int, c_int, _P, _I, _P]),
     "mojo_hip_group_gemm_swiglu": (c_int, [_P, _P, _P, _P, c_int, _I, _I, _I, _I, c_int, c_int, _P, _I, _P]),

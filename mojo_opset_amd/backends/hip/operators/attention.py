@@ -186,6 +186,24 @@ class HIPPagedDecodeSWA(MojoPagedDecodeSWA):
                              block_table, softmax_scale, max_total_seq_len, leave_empty_rows, windows=windows)
 
 
+def _nstep_composed(op, what, symbols, query, key_cache, value_cache, total_seq_lens, block_table, softmax_scale,
+                    max_total_seq_len, leave_empty_rows, windows, scales=None):
+    """The composed route of the n-step ops: the single-step kernels (``symbols``), one launch per step, step ``j`` on
+    ``query[:, j]`` with the lengths ``len - (S - 1 - j)`` computed on the device.  Each call zeroes its empty rows; rows of
+    sequences without keys are then left out of the copy where the caller keeps them (graph replay contract)."""
+    steps = query.shape[1]
+    leave = _capturing(query) if leave_empty_rows is None else leave_empty_rows
+    out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    keep = (total_seq_lens > 0)[:, None, None] if leave else None
+    for j in range(steps):
+        back = steps - 1 - j
+        lens_j = total_seq_lens if back == 0 else torch.where(total_seq_lens > 0, total_seq_lens - back, total_seq_lens)
+        o_j = _paged_decode(op, what, symbols, query[:, j], key_cache, value_cache, lens_j, block_table,
+                            softmax_scale, max_total_seq_len, False, scales=scales, windows=windows)
+        out[:, j] = o_j if keep is None else torch.where(keep, o_j, out[:, j])
+    return out
+
+
 class HIPPagedDecodeNstepSWA(MojoPagedDecodeNstepSWA):
     """``S`` query tokens per sequence in one pass over the paged cache: the matrix-core decode kernel with
     (step, head) pairs in the 16 columns of its score product, so the K/V bytes are read once per block of ``16 // G`` steps.
@@ -221,18 +239,8 @@ class HIPPagedDecodeNstepSWA(MojoPagedDecodeNstepSWA):
         if fused:
             return _paged_decode(self, what, _DECODE_NSTEP, query, key_cache, value_cache, total_seq_lens, block_table,
                                  softmax_scale, max_total_seq_len, leave_empty_rows, windows=(*windows, steps))
-        # composed route: the single-step kernels, one launch per step.  Each call zeroes its empty rows; rows of sequences
-        # without keys are then left out of the copy where the caller keeps them (graph replay contract).
-        leave = _capturing(query) if leave_empty_rows is None else leave_empty_rows
-        out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
-        keep = (total_seq_lens > 0)[:, None, None] if leave else None
-        for j in range(steps):
-            back = steps - 1 - j
-            lens_j = total_seq_lens if back == 0 else torch.where(total_seq_lens > 0, total_seq_lens - back, total_seq_lens)
-            o_j = _paged_decode(self, what, _DECODE_SWA, query[:, j], key_cache, value_cache, lens_j, block_table,
-                                softmax_scale, max_total_seq_len, False, windows=windows)
-            out[:, j] = o_j if keep is None else torch.where(keep, o_j, out[:, j])
-        return out
+        return _nstep_composed(self, what, _DECODE_SWA, query, key_cache, value_cache, total_seq_lens, block_table,
+                               softmax_scale, max_total_seq_len, leave_empty_rows, windows)
 
 
 class HIPPagedPrefillSWA(MojoPagedPrefillSWA):

@@ -1,19 +1,20 @@
 """HIP<Op> classes of the int8 paged KV cache with per-channel scales: the quantising store, the decode / prefill
-GQA that read it and their sliding-window forms.  Everything that is not built raises ``NotImplementedError`` on the host, before any
+GQA that read it, their sliding-window forms and the n-step decode.  Everything that is not built raises ``NotImplementedError`` on the host, before any
 device work."""
 from typing import Optional
 
 import torch
 
-from ....core.operators.attention import (MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeSWAWithKVDequant,
-                                          MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillSWAWithKVDequant,
+from ....core.operators.attention import (MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWAWithKVDequant,
+                                          MojoPagedDecodeSWAWithKVDequant, MojoPagedPrefillGQAWithKVDequant,
+                                          MojoPagedPrefillSWAWithKVDequant, assert_nstep_query,
                                           assert_paged_decode_contract, assert_paged_prefill_contract)
 from ....core.operators.kv_cache import MojoStorePagedKVCacheC8, assert_paged_kv_layout_contract
 from .. import lib as L
-from .attention import _paged_decode, _paged_prefill, _swa_windows
+from .attention import _nstep_composed, _paged_decode, _paged_prefill, _swa_windows, _validate_tables
 
 __all__ = ["HIPStorePagedKVCacheC8", "HIPPagedDecodeGQAWithKVDequant", "HIPPagedPrefillGQAWithKVDequant",
-           "HIPPagedDecodeSWAWithKVDequant", "HIPPagedPrefillSWAWithKVDequant"]
+           "HIPPagedDecodeSWAWithKVDequant", "HIPPagedPrefillSWAWithKVDequant", "HIPPagedDecodeNstepSWAWithKVDequant"]
 
 _ROCM = ["rocm"]
 _SCALE_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
@@ -23,6 +24,7 @@ _DECODE_KV8 = ("mojo_hip_paged_decode_gqa_kv8_workspace_bytes", "mojo_hip_paged_
 _PREFILL_KV8 = ("mojo_hip_paged_prefill_gqa_kv8_workspace_bytes", "mojo_hip_paged_prefill_gqa_kv8")
 _DECODE_SWA_KV8 = ("mojo_hip_paged_decode_swa_kv8_workspace_bytes", "mojo_hip_paged_decode_swa_kv8")
 _PREFILL_SWA_KV8 = ("mojo_hip_paged_prefill_swa_kv8_workspace_bytes", "mojo_hip_paged_prefill_swa_kv8")
+_DECODE_NSTEP_KV8 = ("mojo_hip_paged_decode_nstep_kv8_workspace_bytes", "mojo_hip_paged_decode_nstep_kv8")
 
 
 def _dense(t):
@@ -179,6 +181,52 @@ class HIPPagedDecodeSWAWithKVDequant(MojoPagedDecodeSWAWithKVDequant):
         return _paged_decode(self, what, _DECODE_SWA_KV8, query, key_cache, value_cache, total_seq_lens, block_table,
                              softmax_scale, max_total_seq_len, leave_empty_rows,
                              scales=(_dense(key_scale), _dense(value_scale)), windows=windows)
+
+
+class HIPPagedDecodeNstepSWAWithKVDequant(MojoPagedDecodeNstepSWAWithKVDequant):
+    """``S`` query tokens per sequence in one pass over the int8 cache: `HIPPagedDecodeSWAWithKVDequant`'s
+    kernel with (step, head) pairs in the 16 columns of its score product, so the K/V bytes are read once per block of
+    ``16 // G`` steps.  ``S = 1`` is `HIPPagedDecodeSWAWithKVDequant`, bit for bit.
+
+    Where the workspace query answers -1 — ``MOJO_HIP_DECODE_MFMA=0`` — the COMPOSED route runs: ``S`` single-step
+    launches, step ``j`` on ``query[:, j]`` with the lengths ``len - (S - 1 - j)`` (computed on the device: no sync,
+    capture-safe).  It is correct and costs ``S`` times the bytes.
+
+    A row with ``0 < len < S`` stores zeros for the steps that see no key, and raises ``ValueError`` under
+    ``MOJO_HIP_VALIDATE=1``; with no window negative page ids are holes as in the single-step op."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, query_scale, key_cache, key_scale, value_cache, value_scale, total_seq_lens, block_table,
+                softmax_scale: Optional[float] = None, *, max_total_seq_len: Optional[int] = None,
+                leave_empty_rows: Optional[bool] = None):
+        what = "HIPPagedDecodeNstepSWAWithKVDequant"
+        assert_paged_decode_contract(block_table, total_seq_lens)
+        assert_nstep_query(query)
+        _refuse_unbuilt(self, what, query, query_scale, None)
+        windows = _swa_windows(self, what)
+        batch, steps, hq, dim = query.shape
+        n_blocks, hkv, page, dim_c = key_cache.shape
+        assert dim_c == dim and hq % hkv == 0
+        _check_int8_caches(what, key_cache, value_cache, key_scale, value_scale, hkv, dim)
+        if dim not in _DECODE_DIMS or page % 16 != 0 or not 1 <= hq // hkv <= 16:
+            raise NotImplementedError(f"{what}: head_dim {dim} / page {page} / group {hq // hkv} outside the envelope "
+                                      f"(head_dim {_DECODE_DIMS}, pages of a multiple of 16 tokens, groups of 1..16)")
+        if any(s % 16 for s in key_cache.stride()[:3]):
+            raise NotImplementedError(f"{what}: cache strides must be multiples of 16 bytes")
+        L.require_cuda(query, key_cache, value_cache, key_scale, value_scale, total_seq_lens, block_table)
+        if steps == 0:
+            return torch.empty_like(query)
+        if _validate_tables() and batch > 0 and bool(((total_seq_lens > 0) & (total_seq_lens < steps)).any()):
+            raise ValueError(f"{what}: a row holds fewer keys than the {steps} query steps it counts")
+        scales = (_dense(key_scale), _dense(value_scale))
+        hint = int(max_total_seq_len) if max_total_seq_len is not None else 0
+        fused = L.load().mojo_hip_paged_decode_nstep_kv8_workspace_bytes(
+            batch, hq, hkv, dim, page, block_table.shape[1], hint, *windows, steps) >= 0
+        if fused:
+            return _paged_decode(self, what, _DECODE_NSTEP_KV8, query, key_cache, value_cache, total_seq_lens, block_table,
+                                 softmax_scale, max_total_seq_len, leave_empty_rows, scales=scales, windows=(*windows, steps))
+        return _nstep_composed(self, what, _DECODE_SWA_KV8, query, key_cache, value_cache, total_seq_lens, block_table,
+                               softmax_scale, max_total_seq_len, leave_empty_rows, windows, scales=scales)
 
 
 class HIPPagedPrefillSWAWithKVDequant(MojoPagedPrefillSWAWithKVDequant):

@@ -1,6 +1,7 @@
 from .activation import MojoSwiGLU
-from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA, MojoPagedDecodeSWA,
-                        MojoPagedDecodeSWAWithKVDequant, MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
+from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
+                        MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
+                        MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
                         MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
@@ -41,3 +42,5 @@ BEYOND_SURVEY_OPS = EXTENDED_OPS + KV_INT8_OPS + KV_INT8_SWA_OPS + QUANT_MOE_OPS
 # plugin-registered class like the sets above, but not part of BEYOND_SURVEY_OPS: its torch golden is tests/nstep_golden.py,
 # not yet a module of `oracle/`.
 NSTEP_OPS = ("MojoPagedDecodeNstepSWA",)
+# the n-step decode over the int8 cache: a set of its own for the same reason (golden: tests/nstep_kv_int8_golden.py)
+NSTEP_KV_INT8_OPS = ("MojoPagedDecodeNstepSWAWithKVDequant",)

@@ -243,6 +243,27 @@ class MojoPagedDecodeSWAWithKVDequant(_PagedSWAKVDequantBase, MojoOperator):
                                   context_dtype, compute_dtype)
 
 
+class MojoPagedDecodeNstepSWAWithKVDequant(_PagedSWAKVDequantBase, MojoOperator):
+    """`MojoPagedDecodeNstepSWA` over an int8 K/V cache with per-channel scales: ``S`` query tokens per sequence, the
+    arithmetic of `MojoPagedPrefillSWAWithKVDequant` applied to the ``S`` rows of each sequence.
+
+    ``total_seq_lens`` counts the ``S`` new tokens: step ``j`` of a row of ``kv_len`` keys sits at position
+    ``p = kv_len - S + j`` and sees key ``t`` iff ``t <= p`` and, when a window is set, ``t >= p - local_window_size`` or
+    ``t < global_window_size``.
+
+    forward(query [B,S,Hq,D], query_scale (None: the query is not quantised), key_cache [N,Hkv,page,D] int8,
+            key_scale [Hkv,D], value_cache int8, value_scale [Hkv,D], total_seq_lens [B] i32, block_table [B,nb] i32,
+            softmax_scale=None, *, max_total_seq_len=None) -> [B,S,Hq,D]; rows with seq_len <= 0 are zeros.
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,
+                 local_window_size: Optional[int] = None, query_dtype: torch.dtype = torch.bfloat16,
+                 context_dtype: torch.dtype = torch.int8, compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        self._init_swa_kv_dequant(is_causal, gqa_layout, global_window_size, local_window_size, query_dtype,
+                                  context_dtype, compute_dtype)
+
+
 class MojoPagedPrefillSWAWithKVDequant(_PagedSWAKVDequantBase, MojoOperator):
     """`MojoPagedPrefillSWA` over an int8 K/V cache with per-channel scales.
 

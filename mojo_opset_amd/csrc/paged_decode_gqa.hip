@@ -26,7 +26,7 @@
 // decode kernels share on the device (paired prologue, row and chunk of a wave, hole scan, in-LDS merge, split epilogue, softmax
 // step of the matrix-core kernels); decode_split_kernel (vector units); paged_decode_mfma.h (16-bit matrix-core kernel); the
 // merge kernel; the planner; one launch selection for both 16-bit routes (launch_decode_nt); the entry points, which fill a
-// DecodeCall; paged_decode_kv8.h (int8-cache kernel and its entry points).
+// DecodeCall; paged_decode_kv8.h (int8-cache kernel and its entry points); paged_decode_kv8_nstep.h (its n-step form).
 #include <math.h>
 #include <stdlib.h>
 
@@ -673,7 +673,7 @@ struct DecodeGeom {
   int64_t batch = 0, q_heads = 0, kv_heads = 0, head_dim = 0, page = 0, max_pages = 0, len_hint = 0;
   int64_t local_window = -1, global_window = 0;
   bool kv8 = false;                 // the int8-cache op (paged_decode_kv8.h): its own kernel, never grouped, paired or halved
-  int64_t steps = 1;                // query rows per sequence (> 1: the n-step op, DecodeSteps; matrix-core kernel only)
+  int64_t steps = 1;                // query rows per sequence (> 1: the n-step op, DecodeSteps; matrix-core kernels only)
 };
 
 struct DecodePlan {
@@ -691,14 +691,20 @@ struct DecodePlan {
   int steps = 1, scan_holes = 0;    // the n-step kernels' own arguments (decode_nstep_arg)
 };
 
-// The n-step op runs on the matrix-core kernel alone (its 16 columns are what holds the steps): the geometries that kernel
-// takes, and MOJO_HIP_DECODE_MFMA as for the single-step op — 0 = never (callers then compose single-step launches),
-// 1 = wherever it applies, unset = where it measured faster than `steps` single-step launches.
+// The n-step op runs on the matrix-core kernels alone (their 16 columns are what holds the steps): the geometries the 16-bit
+// kernel takes, or with the int8 cache those of decode_kv8_kernel (paged_decode_kv8_nstep.h), and MOJO_HIP_DECODE_MFMA as for
+// the single-step op — 0 = never (callers then compose single-step launches), 1 = wherever it applies, unset = where it
+// measured faster than `steps` single-step launches.
 static bool decode_nstep_fused(const DecodeGeom& g) {
-  if (g.kv8 || g.kv_heads <= 0 || g.q_heads % g.kv_heads != 0) return false;
+  if (g.kv_heads <= 0 || g.q_heads % g.kv_heads != 0) return false;
   const int64_t G = g.q_heads / g.kv_heads;
-  const bool pow2 = g.page > 0 && (g.page & (g.page - 1)) == 0;
-  if (!pow2 || g.page < 16 || (g.head_dim != 64 && g.head_dim != 128) || G > 16) return false;
+  if (g.kv8) {
+    const bool dim_ok = g.head_dim == 64 || g.head_dim == 80 || g.head_dim == 96 || g.head_dim == 128;
+    if (!dim_ok || g.page <= 0 || g.page % 16 != 0 || G > 16) return false;
+  } else {
+    const bool pow2 = g.page > 0 && (g.page & (g.page - 1)) == 0;
+    if (!pow2 || g.page < 16 || (g.head_dim != 64 && g.head_dim != 128) || G > 16) return false;
+  }
   return MOJO_SWITCH("MOJO_HIP_DECODE_MFMA", -1) != 0;
 }
 
@@ -726,7 +732,7 @@ static DecodePlan decode_plan(const DecodeGeom& g) {
     f.hshift = hshift;
     f.grid_kv_heads = static_cast<int>(g.kv_heads << hshift);
     f.G = static_cast<int>(heads >> hshift);
-    f.mfma = p.nstep || (!g.kv8 && decode_use_mfma(f.G, g.head_dim, g.page));
+    f.mfma = !g.kv8 && (p.nstep || decode_use_mfma(f.G, g.head_dim, g.page));   // (int8 cache: its own kernel, never grouped)
     // The grouped form (DecodeArgs::fuse_group; matrix-core kernel only) — MOJO_HIP_DECODE_GROUPED=0 restores the split + merge form.
     // Measured (scripts/probes/decode_grouped_ab.py, profiles/r4_decode_grouped_ab.txt; split + merge form -> grouped form, graph
     // replay): 8 q / 1 kv heads B 64 ctx 4096 (Llama-3-70B under TP 8) 33.6 -> 28.1 us, B 16 ctx 16384 38.2 -> 29.8 us; 32 / 8 heads
@@ -1062,3 +1068,4 @@ extern "C" int mojo_hip_paged_decode_nstep(const void* query, const void* key_ca
 }
 
 #include "paged_decode_kv8.h"
+#include "paged_decode_kv8_nstep.h"

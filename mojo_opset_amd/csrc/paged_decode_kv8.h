@@ -331,32 +331,47 @@ static int launch_decode_kv8(const Kv8Args& ka, int64_t batch, int G, hipStream_
 
 }  // namespace mojo
 
+// What the int8-cache entry points check (`op`: the entry point's name in the messages).
+static int decode_kv8_check_call(const DecodeCall& c, const char* op) {
+  using namespace mojo;
+  const DecodeGeom& g = c.g;
+  if (const int rc = decode_check_call(c, op); rc != MOJO_OK) return rc;
+  MOJO_REQUIRE(c.scale_dtype == MOJO_BF16 || c.scale_dtype == MOJO_F16 || c.scale_dtype == MOJO_F32, MOJO_EUNSUPPORTED,
+               "%s: scale dtype %d (bf16/fp16/fp32 only)", op, c.scale_dtype);
+  MOJO_REQUIRE(g.head_dim == 64 || g.head_dim == 80 || g.head_dim == 96 || g.head_dim == 128, MOJO_EUNSUPPORTED,
+               "%s: head_dim %lld (supported: 64, 80, 96, 128)", op, (long long)g.head_dim);
+  MOJO_REQUIRE(g.page > 0 && g.page % 16 == 0, MOJO_EUNSUPPORTED,
+               "%s: block_size %lld must be a multiple of 16", op, (long long)g.page);
+  MOJO_REQUIRE(g.q_heads / g.kv_heads <= 16, MOJO_EUNSUPPORTED, "%s: group size %lld (supported: 1..16)", op,
+               (long long)(g.q_heads / g.kv_heads));
+  MOJO_REQUIRE(c.cache_token_stride % 16 == 0 && c.cache_head_stride % 16 == 0 && c.cache_block_stride % 16 == 0 &&
+                   aligned_to(c.key_cache, 16) && aligned_to(c.value_cache, 16) && aligned_to(c.query, 16) && aligned_to(c.out, 16) &&
+                   aligned_to(c.key_scale, 16) && aligned_to(c.value_scale, 16),
+               MOJO_EUNSUPPORTED, "%s: tensors must be 16-byte aligned with 16-byte row strides", op);
+  return MOJO_OK;
+}
+
+// The kernel arguments of a planned int8-cache call.
+static int decode_kv8_fill_args(mojo::Kv8Args& ka, const DecodeCall& c, const mojo::DecodePlan& p) {
+  using namespace mojo;
+  if (p.swa) {
+    if (const int rc = decode_set_window(ka.a, c, p, "paged_decode_swa_kv8"); rc != MOJO_OK) return rc;
+  }
+  if (const int rc = decode_fill_args(ka.a, c, p, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
+  ka.kscale = c.key_scale; ka.vscale = c.value_scale; ka.scale_dtype = c.scale_dtype; ka.q_bf16 = c.dtype == MOJO_BF16 ? 1 : 0;
+  return MOJO_OK;
+}
+
 // The int8-cache entry points share one body: a window (local >= 0 or global > 0) selects the windowed instances, planned on
 // the visible capacity (decode_swa_cap); none runs the unwindowed op, whichever entry point was called.
 static int paged_decode_kv8(const DecodeCall& c) {
   using namespace mojo;
   const DecodeGeom& g = c.g;
   if (g.batch == 0) return MOJO_OK;
-  if (const int rc = decode_check_call(c, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
-  MOJO_REQUIRE(c.scale_dtype == MOJO_BF16 || c.scale_dtype == MOJO_F16 || c.scale_dtype == MOJO_F32, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa_kv8: scale dtype %d (bf16/fp16/fp32 only)", c.scale_dtype);
-  MOJO_REQUIRE(g.head_dim == 64 || g.head_dim == 80 || g.head_dim == 96 || g.head_dim == 128, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa_kv8: head_dim %lld (supported: 64, 80, 96, 128)", (long long)g.head_dim);
-  MOJO_REQUIRE(g.page > 0 && g.page % 16 == 0, MOJO_EUNSUPPORTED,
-               "paged_decode_gqa_kv8: block_size %lld must be a multiple of 16", (long long)g.page);
-  MOJO_REQUIRE(g.q_heads / g.kv_heads <= 16, MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: group size %lld (supported: 1..16)",
-               (long long)(g.q_heads / g.kv_heads));
-  MOJO_REQUIRE(c.cache_token_stride % 16 == 0 && c.cache_head_stride % 16 == 0 && c.cache_block_stride % 16 == 0 &&
-                   aligned_to(c.key_cache, 16) && aligned_to(c.value_cache, 16) && aligned_to(c.query, 16) && aligned_to(c.out, 16) &&
-                   aligned_to(c.key_scale, 16) && aligned_to(c.value_scale, 16),
-               MOJO_EUNSUPPORTED, "paged_decode_gqa_kv8: tensors must be 16-byte aligned with 16-byte row strides");
+  if (const int rc = decode_kv8_check_call(c, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
   const DecodePlan p = decode_plan(g);
   Kv8Args ka{};
-  if (p.swa) {
-    if (const int rc = decode_set_window(ka.a, c, p, "paged_decode_swa_kv8"); rc != MOJO_OK) return rc;
-  }
-  if (const int rc = decode_fill_args(ka.a, c, p, "paged_decode_gqa_kv8"); rc != MOJO_OK) return rc;
-  ka.kscale = c.key_scale; ka.vscale = c.value_scale; ka.scale_dtype = c.scale_dtype; ka.q_bf16 = c.dtype == MOJO_BF16 ? 1 : 0;
+  if (const int rc = decode_kv8_fill_args(ka, c, p); rc != MOJO_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(c.stream);
   const bool nt = MOJO_SWITCH("MOJO_HIP_STREAM_NT", -1) != 0;
   if (p.swa) return nt ? launch_decode_kv8<true, true>(ka, g.batch, p.G, s) : launch_decode_kv8<false, true>(ka, g.batch, p.G, s);
