@@ -364,10 +364,14 @@ extern "C" int mojo_hip_gemm(const void* input, const void* weight, const void* 
 }
 
 // ---- decode-sized fusions (a decoder layer's MLP and projections at M <= 64; core/operators/moe.py:402-449 is the op chain) ----
-extern "C" int mojo_hip_swiglu_rows(const void* gate, const void* up, void* out, int64_t rows, int64_t cols, int64_t ld_gate,
-                                    int64_t ld_up, int64_t ld_out, int dtype, float swiglu_limit, mojo_stream_t stream);
-extern "C" int mojo_hip_residual_add_rmsnorm(const void* hidden, const void* residual, const void* weight, void* normed_out,
-                                             void* sum_out, int64_t rows, int64_t dim, int dtype, float eps, mojo_stream_t stream);
+// mojo_hip_swiglu_rows / mojo_hip_residual_add_rmsnorm (swiglu.hip, rmsnorm.hip) without their own launch note: the history of
+// the entry points below is their GEMM route (an unfused route is the one without a fused tag)
+namespace mojo {
+int swiglu_rows(const void* gate, const void* up, void* out, int64_t rows, int64_t cols, int64_t ld_gate, int64_t ld_up,
+                int64_t ld_out, int dtype, float swiglu_limit, mojo_stream_t stream, bool tagged);
+int residual_add_rmsnorm(const void* hidden, const void* residual, const void* weight, void* normed_out, void* sum_out,
+                         int64_t rows, int64_t dim, int dtype, float eps, mojo_stream_t stream, bool tagged);
+}  // namespace mojo
 
 extern "C" int64_t mojo_hip_gemm_swiglu_workspace_bytes(int64_t m, int64_t k, int64_t inter) {
   return 64 + m * 2 * inter * 2 + mojo_hip_gemm_workspace_bytes(m, k, 2 * inter);
@@ -408,7 +412,7 @@ extern "C" int mojo_hip_gemm_swiglu(const void* input, const void* weight, void*
   const int64_t ws2_bytes = workspace_bytes - (ws2 - static_cast<char*>(workspace));
   int rc = mojo_hip_gemm(input, weight, nullptr, gu, m, k, 2 * inter, lda, 2 * inter, 1, w_n_stride, dtype, ws2, ws2_bytes, stream);
   if (rc) return rc;
-  return mojo_hip_swiglu_rows(gu, gu + inter * 2, out, m, inter, 2 * inter, 2 * inter, ldc, dtype, 0.f, stream);
+  return swiglu_rows(gu, gu + inter * 2, out, m, inter, 2 * inter, 2 * inter, ldc, dtype, 0.f, stream, false);
 }
 
 extern "C" int64_t mojo_hip_gemm_residual_rmsnorm_workspace_bytes(int64_t m, int64_t k, int64_t n) {
@@ -453,5 +457,5 @@ extern "C" int mojo_hip_gemm_residual_rmsnorm(const void* input, const void* wei
   }
   int rc = mojo_hip_gemm(input, weight, bias, p, m, k, n, lda, n, w_k_stride, w_n_stride, dtype, ws2, ws2_bytes, stream);
   if (rc) return rc;
-  return mojo_hip_residual_add_rmsnorm(p, residual, norm_weight, normed_out, sum_out, m, n, dtype, eps, stream);
+  return residual_add_rmsnorm(p, residual, norm_weight, normed_out, sum_out, m, n, dtype, eps, stream, false);
 }

@@ -293,20 +293,22 @@ static int launch_norm_quant(const NormQuantArgs& a, hipStream_t s) {
                     (!a.weight || aligned_to(a.weight, 16)) && (!a.smooth || aligned_to(a.smooth, 16));
   int64_t blocks = a.rows > 256 * 32 ? 256 * 32 : a.rows;
   const long long moved = a.rows * static_cast<long long>(a.dim) * (static_cast<long long>(sizeof(T)) * (1 + (a.residual ? 1 : 0) + (a.out_sum ? 1 : 0)) + 1);
+  const bool nt = wide && stream_nt(moved);             // (the scalar form has no non-temporal twin)
   // a row per wave: dynamic quant (no normalisation: no sum of squares) of many rows that fit one wave's registers
   if (wide && !a.weight && a.dim / WIDE <= 4 * 64 && a.rows >= 2048) {
     blocks = ceil_div(a.rows, 4);
     if (blocks > 256 * 32) blocks = 256 * 32;
-    if (stream_nt(moved)) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true, 64>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+    if (nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true, 64>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, false, 64>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
     MOJO_CHECK_LAUNCH("norm_quant");
-    note_launch("norm_quant:row_per_wave");
+    note_launch("norm_quant:wide:tpr64:%s", nt ? "nt" : "cached");
     return MOJO_OK;
   }
-  if (wide && stream_nt(moved)) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+  if (nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   else if (wide) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((norm_quant_kernel<T, 1, 8>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   MOJO_CHECK_LAUNCH("norm_quant");
+  note_launch("norm_quant:%s:tpr256:%s", wide ? "wide" : "scalar", nt ? "nt" : "cached");
   return MOJO_OK;
 }
 

@@ -97,9 +97,11 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const T* hidden /* may ali
   }
 }
 
+struct RmsForm { int vec, tpr; bool nt; };   // the template choice a launch took (its mojo_hip_last_launch() tag)
+
 template <typename T, int VEC>
-static void launch_rms(const void* hidden, const void* residual, const void* weight, void* normed, void* summed,
-                       int64_t rows, int64_t dim, float eps, hipStream_t s) {
+static RmsForm launch_rms(const void* hidden, const void* residual, const void* weight, void* normed, void* summed,
+                          int64_t rows, int64_t dim, float eps, hipStream_t s) {
   const int64_t n_vec = dim / VEC;
   const T* h = static_cast<const T*>(hidden);
   const T* r = static_cast<const T*>(residual);
@@ -118,22 +120,42 @@ static void launch_rms(const void* hidden, const void* residual, const void* wei
   if (tpr == 64) go(std::integral_constant<int, 64>{}, ceil_div(rows, 4));          // short rows: one wave per row, 4 rows per block
   else if (tpr == 128) go(std::integral_constant<int, 128>{}, ceil_div(rows, 2));   // two waves per row, two rows per block
   else go(std::integral_constant<int, 256>{}, rows);
+  return {VEC, tpr, nt};
 }
 
 template <typename T>
 static int dispatch_rms(const void* hidden, const void* residual, const void* weight, void* normed, void* summed,
-                        int64_t rows, int64_t dim, float eps, hipStream_t s) {
+                        int64_t rows, int64_t dim, float eps, hipStream_t s, bool tagged) {
   constexpr int WIDE = 16 / sizeof(T);
   auto ok = [&](int vec) {
     const size_t a = vec * sizeof(T);
     return dim % vec == 0 && aligned_to(hidden, a) && aligned_to(weight, a) && aligned_to(normed, a) &&
            (!residual || aligned_to(residual, a)) && (!summed || aligned_to(summed, a));
   };
-  if (ok(WIDE)) launch_rms<T, WIDE>(hidden, residual, weight, normed, summed, rows, dim, eps, s);
-  else if (ok(2)) launch_rms<T, 2>(hidden, residual, weight, normed, summed, rows, dim, eps, s);
-  else launch_rms<T, 1>(hidden, residual, weight, normed, summed, rows, dim, eps, s);
+  RmsForm f;
+  if (ok(WIDE)) f = launch_rms<T, WIDE>(hidden, residual, weight, normed, summed, rows, dim, eps, s);
+  else if (ok(2)) f = launch_rms<T, 2>(hidden, residual, weight, normed, summed, rows, dim, eps, s);
+  else f = launch_rms<T, 1>(hidden, residual, weight, normed, summed, rows, dim, eps, s);
   MOJO_CHECK_LAUNCH("residual_add_rmsnorm");
+  if (tagged) note_launch("rmsnorm:vec%d:tpr%d:%s", f.vec, f.tpr, f.nt ? "nt" : "cached");
   return MOJO_OK;
+}
+
+// `tagged == false`: the unfused tail of mojo_hip_gemm_residual_rmsnorm (gemm_api.hip), whose launch history is its GEMM
+// route alone (tests/golden/gemm_routes.json pins it); every other caller notes the form.
+int residual_add_rmsnorm(const void* hidden, const void* residual, const void* weight, void* normed_out, void* sum_out,
+                         int64_t rows, int64_t dim, int dtype, float eps, mojo_stream_t stream, bool tagged) {
+  if (rows == 0) return MOJO_OK;
+  MOJO_REQUIRE(hidden && weight && normed_out, MOJO_EINVAL, "rmsnorm: null pointer");
+  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "rmsnorm: bad shape rows=%lld dim=%lld",
+               (long long)rows, (long long)dim);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case MOJO_F32: return dispatch_rms<float>(hidden, residual, weight, normed_out, sum_out, rows, dim, eps, s, tagged);
+    case MOJO_F16: return dispatch_rms<f16_t>(hidden, residual, weight, normed_out, sum_out, rows, dim, eps, s, tagged);
+    case MOJO_BF16: return dispatch_rms<bf16_t>(hidden, residual, weight, normed_out, sum_out, rows, dim, eps, s, tagged);
+    default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "rmsnorm: dtype %d not supported", dtype);
+  }
 }
 
 }  // namespace mojo
@@ -143,15 +165,5 @@ using namespace mojo;
 extern "C" int mojo_hip_residual_add_rmsnorm(const void* hidden, const void* residual, const void* weight,
                                              void* normed_out, void* sum_out, int64_t rows, int64_t dim, int dtype,
                                              float eps, mojo_stream_t stream) {
-  if (rows == 0) return MOJO_OK;
-  MOJO_REQUIRE(hidden && weight && normed_out, MOJO_EINVAL, "rmsnorm: null pointer");
-  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "rmsnorm: bad shape rows=%lld dim=%lld",
-               (long long)rows, (long long)dim);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case MOJO_F32: return dispatch_rms<float>(hidden, residual, weight, normed_out, sum_out, rows, dim, eps, s);
-    case MOJO_F16: return dispatch_rms<f16_t>(hidden, residual, weight, normed_out, sum_out, rows, dim, eps, s);
-    case MOJO_BF16: return dispatch_rms<bf16_t>(hidden, residual, weight, normed_out, sum_out, rows, dim, eps, s);
-    default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "rmsnorm: dtype %d not supported", dtype);
-  }
+  return residual_add_rmsnorm(hidden, residual, weight, normed_out, sum_out, rows, dim, dtype, eps, stream, true);
 }

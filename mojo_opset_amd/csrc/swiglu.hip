@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void swiglu_rows_kernel(const T* __restrict__ 
 
 template <typename T>
 static int launch_swiglu_rows(const void* gate, const void* up, void* out, int64_t rows, int64_t cols, int64_t ld_gate,
-                              int64_t ld_up, int64_t ld_out, float limit, hipStream_t s) {
+                              int64_t ld_up, int64_t ld_out, float limit, hipStream_t s, bool tagged) {
   constexpr int WIDE = 16 / sizeof(T);
   const bool wide = cols % WIDE == 0 && ld_gate % WIDE == 0 && ld_up % WIDE == 0 && ld_out % WIDE == 0 &&
                     aligned_to(gate, 16) && aligned_to(up, 16) && aligned_to(out, 16);
@@ -90,6 +90,7 @@ static int launch_swiglu_rows(const void* gate, const void* up, void* out, int64
                        static_cast<const T*>(up), static_cast<T*>(out), rows, static_cast<int>(cols), ld_gate, ld_up, ld_out,
                        limit);
   MOJO_CHECK_LAUNCH("swiglu_rows");
+  if (tagged) note_launch("swiglu_rows:%s", wide ? "wide" : "scalar");
   return MOJO_OK;
 }
 
@@ -101,9 +102,10 @@ static int launch_swiglu(const void* gate, const void* up, void* out, int64_t n,
   constexpr int UNROLL = 4;
   int64_t blocks = ceil_div(n_vec, 256 * UNROLL);
   if (blocks > 256 * 16) blocks = 256 * 16;
+  const bool nt = wide && stream_nt(3 * n * static_cast<long long>(sizeof(T)));   // (the scalar form has no non-temporal twin)
   if (wide) {
     const T* g_ = static_cast<const T*>(gate); const T* u_ = static_cast<const T*>(up); T* o_ = static_cast<T*>(out);
-    if (stream_nt(3 * n * static_cast<long long>(sizeof(T))))
+    if (nt)
       hipLaunchKernelGGL((swiglu_kernel<T, WIDE, UNROLL, true>), dim3(blocks), dim3(256), 0, s, g_, u_, o_, n_vec, limit);
     else
       hipLaunchKernelGGL((swiglu_kernel<T, WIDE, UNROLL, false>), dim3(blocks), dim3(256), 0, s, g_, u_, o_, n_vec, limit);
@@ -112,7 +114,24 @@ static int launch_swiglu(const void* gate, const void* up, void* out, int64_t n,
                        static_cast<const T*>(up), static_cast<T*>(out), n_vec, limit);
   }
   MOJO_CHECK_LAUNCH("swiglu");
+  note_launch("swiglu:%s:%s", wide ? "wide" : "scalar", nt ? "nt" : "cached");
   return MOJO_OK;
+}
+
+// `tagged == false`: the unfused tail of mojo_hip_gemm_swiglu (gemm_api.hip), whose launch history is its GEMM route alone
+// (tests/golden/gemm_routes.json pins it); every other caller notes the form.
+int swiglu_rows(const void* gate, const void* up, void* out, int64_t rows, int64_t cols, int64_t ld_gate, int64_t ld_up,
+                int64_t ld_out, int dtype, float swiglu_limit, mojo_stream_t stream, bool tagged) {
+  if (rows == 0 || cols == 0) return MOJO_OK;
+  MOJO_REQUIRE(gate && up && out && rows > 0 && cols > 0 && cols < (1LL << 31), MOJO_EINVAL, "swiglu_rows: bad arguments");
+  MOJO_REQUIRE(ld_gate >= cols && ld_up >= cols && ld_out >= cols, MOJO_EINVAL, "swiglu_rows: row stride smaller than the row");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case MOJO_F32: return launch_swiglu_rows<float>(gate, up, out, rows, cols, ld_gate, ld_up, ld_out, swiglu_limit, s, tagged);
+    case MOJO_F16: return launch_swiglu_rows<f16_t>(gate, up, out, rows, cols, ld_gate, ld_up, ld_out, swiglu_limit, s, tagged);
+    case MOJO_BF16: return launch_swiglu_rows<bf16_t>(gate, up, out, rows, cols, ld_gate, ld_up, ld_out, swiglu_limit, s, tagged);
+    default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "swiglu_rows: dtype %d not supported", dtype);
+  }
 }
 
 }  // namespace mojo
@@ -135,14 +154,5 @@ extern "C" int mojo_hip_swiglu(const void* gate, const void* up, void* out, int6
 extern "C" int mojo_hip_swiglu_rows(const void* gate, const void* up, void* out, int64_t rows, int64_t cols,
                                     int64_t ld_gate, int64_t ld_up, int64_t ld_out, int dtype, float swiglu_limit,
                                     mojo_stream_t stream) {
-  if (rows == 0 || cols == 0) return MOJO_OK;
-  MOJO_REQUIRE(gate && up && out && rows > 0 && cols > 0 && cols < (1LL << 31), MOJO_EINVAL, "swiglu_rows: bad arguments");
-  MOJO_REQUIRE(ld_gate >= cols && ld_up >= cols && ld_out >= cols, MOJO_EINVAL, "swiglu_rows: row stride smaller than the row");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case MOJO_F32: return launch_swiglu_rows<float>(gate, up, out, rows, cols, ld_gate, ld_up, ld_out, swiglu_limit, s);
-    case MOJO_F16: return launch_swiglu_rows<f16_t>(gate, up, out, rows, cols, ld_gate, ld_up, ld_out, swiglu_limit, s);
-    case MOJO_BF16: return launch_swiglu_rows<bf16_t>(gate, up, out, rows, cols, ld_gate, ld_up, ld_out, swiglu_limit, s);
-    default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "swiglu_rows: dtype %d not supported", dtype);
-  }
+  return swiglu_rows(gate, up, out, rows, cols, ld_gate, ld_up, ld_out, dtype, swiglu_limit, stream, true);
 }
