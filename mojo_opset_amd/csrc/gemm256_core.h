@@ -930,9 +930,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs a, Epi epi) {
 }
 
 // shared precondition checks (bytes along K); eb = element bytes
+inline bool gemm256_k_ok(int64_t k, int eb) { return k >= KT_BYTES / eb && k % (KT_BYTES / eb) == 0; }   // whole K-tiles (also what a workspace query can ask)
 inline bool gemm256_layout_ok(const GemmArgs& a, int eb) {
-  const int bk = KT_BYTES / eb, al = 16 / eb;
-  if (a.K < bk || a.K % bk != 0 || a.N < al) return false;
+  const int al = 16 / eb;
+  if (!gemm256_k_ok(a.K, eb) || a.N < al) return false;
   if (a.lda % al != 0) return false;
   if (!aligned_to(a.A, 16) || !aligned_to(a.W, 16)) return false;
   if (a.w_n == 1) {                                   // [K,N]

@@ -20,9 +20,7 @@ int gemm_tile128_forced() { return g128::forced_choice(); }      // MOJO_HIP_GEM
 // gemm_rows128_prefers_tile128, the latter against the weight-streaming kernels) says so; MOJO_HIP_GEMM_TILE128 = 1 / 0: wherever they
 // apply / never.
 bool gemm_tile128_use(const GemmArgs& a, int dtype, int64_t m_total, bool model_prefers) {
-  if (!gemm_tile128_ok(a, dtype)) return false;
-  const int f = g128::forced_choice();
-  return f < 0 ? model_prefers : f == 1;
+  return gemm_tile128_ok(a, dtype) && g128::choose(model_prefers);
 }
 
 int launch_gemm_tile128(const GemmArgs& a, int dtype, int64_t m_total, hipStream_t s) {

@@ -457,6 +457,7 @@ inline int forced_choice() {
   if (MOJO_SWITCH("MOJO_HIP_GEMM_SPLITK", 0) > 1) return 0;         // a forced split alone is a split of the 256 kernel
   return -1;
 }
+inline bool choose(bool model_prefers) { const int f = forced_choice(); return f < 0 ? model_prefers : f == 1; }
 
 }  // namespace g128
 }  // namespace mojo

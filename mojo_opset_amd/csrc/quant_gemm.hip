@@ -407,8 +407,7 @@ static bool quant_gemv_ok(int64_t m, const GemmArgs& a) {
 }
 
 template <typename TO, bool FP8>
-static int launch_quant_gemv(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m, hipStream_t s) {
-  const int mv = m <= 1 ? 1 : (m <= 2 ? 2 : 4);
+static int launch_quant_gemv(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m, int mv /* QuantPlan::gemv_rows */, hipStream_t s) {
   const unsigned blocks = static_cast<unsigned>(ceil_div(a.N, 8));
   const size_t lds = static_cast<size_t>(mv) * a.K;
   const uint8_t* A = static_cast<const uint8_t*>(a.A);
@@ -427,8 +426,11 @@ static int launch_quant_gemv(const GemmArgs& a, const float* rs, const bf16_t* c
   return MOJO_OK;
 }
 
+static bool quant_skinny_shape_ok(int64_t m, int64_t k, int64_t n) {   // (the half quant_max_splitk can ask: no layout, no pointers)
+  return m <= 128 && k > 0 && k % 256 == 0 && n % 64 == 0;
+}
 static bool quant_skinny_ok(int64_t m, const GemmArgs& a) {
-  return m <= 128 && a.w_k == 1 && a.w_n == a.K && a.K % 256 == 0 && a.N % 64 == 0 && a.lda == a.K && a.ldc == a.N &&
+  return quant_skinny_shape_ok(m, a.K, a.N) && a.w_k == 1 && a.w_n == a.K && a.lda == a.K && a.ldc == a.N &&
          aligned_to(a.A, 16) && aligned_to(a.W, 16) && aligned_to(a.C, 8);
 }
 
@@ -468,10 +470,6 @@ static QuantSkinnyPlan quant_skinny_plan(int k, int n, int64_t m, bool wide = tr
   if (any.nw != 4 && (any.cost <= 0.75 * narrow.cost || (m > 64 && any.cost < 0.999 * narrow.cost))) return any;
   return narrow;
 }
-static int quant_skinny_splitk(int k, int n, int64_t m) {            // (workspace sizing: the larger of the two plans' splits)
-  const int a = quant_skinny_plan(k, n, m, true).sk, b = quant_skinny_plan(k, n, m, false).sk;
-  return a > b ? a : b;
-}
 
 // Split launches of every 8-bit kernel: sum the K slices' int32 / fp32 slabs in slice order, apply the scales, store C.
 template <typename TO>
@@ -500,21 +498,33 @@ static int launch_quant_dequant(const GemmArgs& a, bool fp8, const float* rs, co
   return fp8 ? launch(g256::PolF8{}) : launch(g256::PolI8{});
 }
 
+// What one mojo_hip_quant_gemm call launches (plan_quant_gemm, below): run_quant sets the split's fields of GemmArgs from it and
+// switches over the route; the launchers take their shapes from it and decide nothing.  Routes: the v_dot4 GEMV (M <= 4), the
+// weight-streaming kernel (<= 128 rows, [N,K] weights), 128-row tiles, the 256 x 256 kernel, one output per thread.
+struct QuantPlan {
+  enum Route { GEMV, STREAM, TILES128, TILES256, GENERIC } route = GENERIC;
+  int splitk = 1;            // > 1: the slices' int32 / fp32 accumulators go to slabs
+  int waves = 4;             // STREAM: waves per workgroup (4, 6, 7 or 8; wider than 4 for bf16 output only)
+  int gemv_rows = 1;         // GEMV: 1, 2 or 4 rows per pass over the weight
+  int stage_rows = 0;        // TILES256, unsplit: row-staged stores (gemm256_core.h)
+  bool finalize = false;     // launch_quant_finalize follows (sums the slabs in slice order, applies the scales)
+};
+
 template <typename TO, bool FP8>
-static int launch_quant_skinny(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m, void* slab_ws, hipStream_t s) {
+static int launch_quant_skinny(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m, QuantPlan& plan, void* slab_ws, hipStream_t s) {
   constexpr bool kWide = std::is_same<TO, bf16_t>::value;   // (other output types: four-wave workgroups only — compile time)
-  const QuantSkinnyPlan plan = quant_skinny_plan(a.K, a.N, m, kWide);
-  const int sk = plan.sk;
+  const int sk = plan.splitk;
   // More than 64 rows run as two row blocks of 64 (grid.z): a 128-row workgroup needs 104 KiB of LDS (one workgroup of four
   // waves per CU) and reads its activation fragments from LDS eight times per weight byte; two 64-row workgroups fit a CU
   // together, and the second reads the weight lines the first just pulled into L2.
-  const dim3 grid(static_cast<unsigned>((a.N / 16 + plan.nw - 1) / plan.nw), static_cast<unsigned>(sk), m > 64 ? 2u : 1u);
+  const dim3 grid(static_cast<unsigned>((a.N / 16 + plan.waves - 1) / plan.waves), static_cast<unsigned>(sk), m > 64 ? 2u : 1u);
   const uint8_t* A = static_cast<const uint8_t*>(a.A);
   const uint8_t* W = static_cast<const uint8_t*>(a.W);
   TO* C = static_cast<TO*>(a.C);
   const int M = static_cast<int>(m);
 #ifdef MOJO_HIP_BUILD_EXPERIMENTS
-  const int slot = sk > 1 && plan.nw == 4 ? splitk_take_slot(static_cast<int64_t>(grid.x) * grid.z) : -1;   // K slices combined inside the launch
+  const int slot = sk > 1 && plan.waves == 4 ? splitk_take_slot(static_cast<int64_t>(grid.x) * grid.z) : -1;   // K slices combined inside the launch
+  if (slot >= 0) plan.finalize = false;
 #else
   const int slot = -1;
 #endif
@@ -522,8 +532,8 @@ static int launch_quant_skinny(const GemmArgs& a, const float* rs, const bf16_t*
 #define SKINNY_NW(MT_, NT_)                                                                                   \
   do {                                                                                                        \
     if constexpr (kWide) {                                                                                    \
-      switch (plan.nw) { case 6: SKINNY(MT_, NT_, 6); break; case 7: SKINNY(MT_, NT_, 7); break;               \
-                         case 8: SKINNY(MT_, NT_, 8); break; default: SKINNY(MT_, NT_, 4); break; }            \
+      switch (plan.waves) { case 6: SKINNY(MT_, NT_, 6); break; case 7: SKINNY(MT_, NT_, 7); break;            \
+                            case 8: SKINNY(MT_, NT_, 8); break; default: SKINNY(MT_, NT_, 4); break; }         \
     } else {                                                                                                  \
       SKINNY(MT_, NT_, 4);                                                                                    \
     }                                                                                                         \
@@ -532,8 +542,7 @@ static int launch_quant_skinny(const GemmArgs& a, const float* rs, const bf16_t*
 #undef SKINNY_NW
 #undef SKINNY
   MOJO_CHECK_LAUNCH("quant_gemm(skinny)");
-  note_launch("quant_skinny:waves%d:splitk%d", plan.nw, sk);
-  if (sk > 1 && slot < 0) return launch_quant_finalize(slab_ws, sk, m, a.N, FP8, rs, cs, C, s);
+  note_launch("quant_skinny:waves%d:splitk%d", plan.waves, sk);
   return MOJO_OK;
 }
 
@@ -556,10 +565,11 @@ static int quant_splitk(int64_t m, int k, int n) {
 // it).  Measured, both kernels forced in one process, 80 shapes per dtype (profiles/r5_quant_tile128_ab.txt): M 1024 x 4096 x 4096
 // int8 39 -> 19 us, M 512 x 2048 x 7168 48 -> 12 us; over the grid the rule is 63 % faster (geometric mean) than the 256 x 256
 // kernel alone and within 0.7 % of always picking the faster form.
+static bool quant_tile128_k_ok(int64_t k) { return k >= 128 && k % 128 == 0; }                 // (the shape half: quant_max_splitk asks it too)
 static bool quant_tile128_ok(int64_t m, const GemmArgs& a, int out_elt_bytes, bool fp8) {
   const bool layout = (a.w_k == 1 && a.w_n % 16 == 0) ||                                      // [N,K] (trans_weight)
                       (!fp8 && a.w_n == 1 && a.w_k % 16 == 0 && a.N % 16 == 0 && a.N >= 16);    // [K,N], int8: transposed byte reads
-  return (m > 64 || a.w_n == 1) && layout && a.K >= 128 && a.K % 128 == 0 && a.lda % 16 == 0 && a.ldc % 4 == 0 &&   // (<= 128 rows with [N,K] weights never get here: the weight-streaming kernel)
+  return (m > 64 || a.w_n == 1) && layout && quant_tile128_k_ok(a.K) && a.lda % 16 == 0 && a.ldc % 4 == 0 &&   // (<= 128 rows with [N,K] weights never get here: the weight-streaming kernel)
          aligned_to(a.A, 16) && aligned_to(a.W, 16) && aligned_to(a.C, 4 * out_elt_bytes);
 }
 // The 128 x 128 tiles' own K split (gemm_api.hip, gemm_tile128_splitk: the same model — a K-tile is 128 bytes of K in both
@@ -605,53 +615,73 @@ static bool quant_prefers_tile128(int64_t m, int k, int n, bool w_nmajor, int* s
   return t128 < 1.2 * t256;
 }
 
+// Row-staged stores of an unsplit 256 x 256 launch (gemm256_core.h): 16-bit outputs in whole 16-byte pieces of a row.
+static int quant_stage_rows(const GemmArgs& a, int out_elt_bytes) {
+  return (MOJO_SWITCH("MOJO_HIP_GEMM_STAGE_ROWS", 1) != 0 && out_elt_bytes == 2 && a.ldc % 8 == 0 && aligned_to(a.C, 16)) ? 1 : 0;
+}
+// The route of one mojo_hip_quant_gemm call, decided once: the first form whose preconditions hold and whose switch allows it,
+// with its K split.  (A forced MOJO_HIP_GEMM_SPLITK is taken unclamped by quant_splitk / quant_skinny_plan: ADVICE item 6's clamp
+// to the route's K-tiles would go into those two, so that quant_max_splitk follows.)
+static QuantPlan plan_quant_gemm(const GemmArgs& a, int64_t m, bool fp8, int out_elt_bytes, bool out_bf16) {
+  QuantPlan p;
+  int sk128 = 1;
+  if (quant_gemv_ok(m, a) && (gemm_skinny_mask() & SKINNY_GEMV)) {
+    p.route = QuantPlan::GEMV; p.gemv_rows = m <= 1 ? 1 : (m <= 2 ? 2 : 4);
+  } else if (quant_skinny_ok(m, a) && (gemm_skinny_mask() & SKINNY_UNIFORM)) {
+    const QuantSkinnyPlan sp = quant_skinny_plan(a.K, a.N, m, out_bf16);
+    p.route = QuantPlan::STREAM; p.splitk = sp.sk; p.waves = sp.nw;
+  } else if (quant_tile128_ok(m, a, out_elt_bytes, fp8) && g128::choose(quant_prefers_tile128(m, a.K, a.N, a.w_n == 1, &sk128))) {
+    p.route = QuantPlan::TILES128;                       // (a forced MOJO_HIP_GEMM_TILE128 takes the model's split too)
+    if (a.ldc == a.N) p.splitk = sk128;                  // (the finalize writes a dense [M, N])
+  } else if (g256::gemm256_layout_ok(a, 1)) {
+    p.route = QuantPlan::TILES256; p.splitk = quant_splitk(m, a.K, a.N);
+    if (p.splitk == 1) p.stage_rows = quant_stage_rows(a, out_elt_bytes);
+  }
+  p.finalize = p.splitk > 1;
+  return p;
+}
+// What mojo_hip_quant_gemm_workspace_bytes sizes: the largest split plan_quant_gemm may take for this shape.  The query knows no
+// layout, dtype, leading dimension or alignment, so it is an upper bound over them: every split candidate of the planner, each
+// behind the shape half of its route's predicate.
+static int quant_max_splitk(int64_t m, int64_t k, int64_t n) {
+  if (m <= 0) return 1;
+  const int ki = static_cast<int>(k), ni = static_cast<int>(n);
+  int sk = 1;
+  if (g256::gemm256_k_ok(k, 1)) sk = std::max(sk, quant_splitk(m, ki, ni));                                        // TILES256
+  if (quant_skinny_shape_ok(m, k, n))                                                                              // STREAM, bf16 or another output
+    sk = std::max({sk, quant_skinny_plan(ki, ni, m, true).sk, quant_skinny_plan(ki, ni, m, false).sk});
+  double t;
+  if (quant_tile128_k_ok(k))                                                                                       // TILES128, either layout
+    sk = std::max({sk, quant_tile128_splitk(m, ki, ni, false, &t), quant_tile128_splitk(m, ki, ni, true, &t)});
+  return sk;
+}
+
 template <typename TO>
 static int run_quant(GemmArgs a, const float* rs, const bf16_t* cs, int64_t m, int quant_dtype, void* slab_ws,
                      hipStream_t s) {
   const bool fp8 = quant_dtype == MOJO_F8E4M3;
-  if (quant_gemv_ok(m, a) && (gemm_skinny_mask() & SKINNY_GEMV))
-    return fp8 ? launch_quant_gemv<TO, true>(a, rs, cs, m, s) : launch_quant_gemv<TO, false>(a, rs, cs, m, s);
-  if (quant_skinny_ok(m, a) && (gemm_skinny_mask() & SKINNY_UNIFORM))
-    return fp8 ? launch_quant_skinny<TO, true>(a, rs, cs, m, slab_ws, s) : launch_quant_skinny<TO, false>(a, rs, cs, m, slab_ws, s);
-  if (quant_tile128_ok(m, a, sizeof(TO), fp8)) {
-    const int f = g128::forced_choice();
-    int sk128 = 1;
-    const bool prefers = quant_prefers_tile128(m, a.K, a.N, a.w_n == 1, &sk128);
-    if (f < 0 ? prefers : f == 1) {
-      if (sk128 > 1 && a.ldc == a.N) {                 // (the finalize writes a dense [M, N]; mojo_hip_quant_gemm_workspace_bytes covers the slabs)
-        a.splitk = sk128; a.slab = slab_ws; a.slab_rows = static_cast<int>(m);
-      }
-      const int rc = launch_quant_dequant<true, TO>(a, fp8, rs, cs, m, s);
-      if (rc || a.splitk == 1) return rc;
-      return launch_quant_finalize(slab_ws, a.splitk, m, a.N, fp8, rs, cs, static_cast<TO*>(a.C), s);
+  QuantPlan p = plan_quant_gemm(a, m, fp8, sizeof(TO), std::is_same<TO, bf16_t>::value);
+  a.splitk = p.splitk; a.stage_rows = p.stage_rows;
+  if (p.splitk > 1) { a.slab = slab_ws; a.slab_rows = static_cast<int>(m); }   // (mojo_hip_quant_gemm_workspace_bytes covers the slabs)
+  int rc = MOJO_OK;
+  switch (p.route) {
+    case QuantPlan::GEMV: rc = fp8 ? launch_quant_gemv<TO, true>(a, rs, cs, m, p.gemv_rows, s) : launch_quant_gemv<TO, false>(a, rs, cs, m, p.gemv_rows, s); break;
+    case QuantPlan::STREAM: rc = fp8 ? launch_quant_skinny<TO, true>(a, rs, cs, m, p, slab_ws, s) : launch_quant_skinny<TO, false>(a, rs, cs, m, p, slab_ws, s); break;
+    case QuantPlan::TILES128: rc = launch_quant_dequant<true, TO>(a, fp8, rs, cs, m, s); break;
+    case QuantPlan::TILES256: rc = launch_quant_dequant<false, TO>(a, fp8, rs, cs, m, s); break;
+    case QuantPlan::GENERIC: {
+      const int64_t blocks = std::min<int64_t>(ceil_div(m * a.N, 256), 256 * 32);
+      auto* fn = fp8 ? quant_gemm_generic_kernel<TO, true> : quant_gemm_generic_kernel<TO, false>;
+      hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, s, static_cast<const uint8_t*>(a.A), static_cast<const uint8_t*>(a.W), rs, cs,
+                         static_cast<TO*>(a.C), m, a.K, a.N, a.w_k, a.w_n);
+      MOJO_CHECK_LAUNCH("quant_gemm_generic");
+      note_launch("quant_generic");
+      break;
     }
   }
-  if (g256::gemm256_layout_ok(a, 1)) {
-    const int sk = quant_splitk(m, a.K, a.N);
-    if (sk > 1) {
-      a.splitk = sk; a.slab = slab_ws; a.slab_rows = static_cast<int>(m);
-      const int rc = launch_quant_dequant<false, TO>(a, fp8, rs, cs, m, s);
-      return rc ? rc : launch_quant_finalize(slab_ws, sk, m, a.N, fp8, rs, cs, static_cast<TO*>(a.C), s);
-    }
-    const bool no_stage = MOJO_SWITCH("MOJO_HIP_GEMM_STAGE_ROWS", 1) == 0;
-    a.stage_rows = (!no_stage && sizeof(TO) == 2 && a.ldc % 8 == 0 && aligned_to(a.C, 16)) ? 1 : 0;   // row-staged stores (gemm256_core.h)
-    return launch_quant_dequant<false, TO>(a, fp8, rs, cs, m, s);
-  }
-  int64_t blocks = ceil_div(m * a.N, 256);
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  const uint8_t* A = static_cast<const uint8_t*>(a.A);
-  const uint8_t* W = static_cast<const uint8_t*>(a.W);
-  if (fp8)
-    hipLaunchKernelGGL((quant_gemm_generic_kernel<TO, true>), dim3(blocks), dim3(256), 0, s, A, W, rs, cs,
-                       static_cast<TO*>(a.C), m, a.K, a.N, a.w_k, a.w_n);
-  else
-    hipLaunchKernelGGL((quant_gemm_generic_kernel<TO, false>), dim3(blocks), dim3(256), 0, s, A, W, rs, cs,
-                       static_cast<TO*>(a.C), m, a.K, a.N, a.w_k, a.w_n);
-  MOJO_CHECK_LAUNCH("quant_gemm_generic");
-  note_launch("quant_generic");
-  return MOJO_OK;
+  if (rc || !p.finalize) return rc;
+  return launch_quant_finalize(slab_ws, p.splitk, m, a.N, fp8, rs, cs, static_cast<TO*>(a.C), s);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------
 // MojoQuantExperts' grouped product (mojo_hip_group_quant_gemm): ragged groups of int8 rows against int8 [G, N, K] weights,
@@ -795,8 +825,7 @@ static int group_quant_ragged_mt(int64_t m_total, int groups) {
   return mean <= 16 ? 1 : (mean <= 32 ? 2 : 4);
 }
 template <typename TO>
-static int launch_group_quant_ragged(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m_total, hipStream_t s) {
-  const int mt = group_quant_ragged_mt(m_total, a.G);
+static int launch_group_quant_ragged(const GemmArgs& a, const float* rs, const bf16_t* cs, int64_t m_total, int mt /* tile height / 16 */, hipStream_t s) {
   const dim3 grid(static_cast<unsigned>(a.N / 64), 1u, static_cast<unsigned>(m_total / (mt * 16) + a.G));   // z: an upper bound on the tiles
   const uint8_t* A = static_cast<const uint8_t*>(a.A);
   const uint8_t* W = static_cast<const uint8_t*>(a.W);
@@ -805,7 +834,6 @@ static int launch_group_quant_ragged(const GemmArgs& a, const float* rs, const b
   if (mt == 1) RAGGED(1); else if (mt == 2) RAGGED(2); else RAGGED(4);
 #undef RAGGED
   MOJO_CHECK_LAUNCH("group_quant_gemm(ragged)");
-  note_launch("group_quant_ragged:rows%d", mt * 16);
   return MOJO_OK;
 }
 
@@ -820,68 +848,83 @@ static bool group_quant_prefers_tile128(int64_t m_total, int64_t n, int64_t grou
   const int64_t rows = std::max<int64_t>(1, m_total / groups);
   return rows <= 128 || groups * ceil_div(rows, 256) * ceil_div(n, 256) < 128;
 }
-// K split of the grouped 256 x 256 launch: QuantGemm's rule on the total rows; a forced split (MOJO_HIP_GEMM_SPLITK) is cut to what
-// the slabs' 16-byte stores (N % 4 == 0) and the K-tiles there are allow.
-static int group_quant_splitk(int64_t m_total, int k, int n) {
-  if (m_total <= 0 || n % 4 != 0 || k < 128) return 1;
-  const int sk = quant_splitk(m_total, k, n), nkt = k / 128;
+// K split of the grouped 256 x 256 launch, the only grouped route that splits (so this is also what
+// mojo_hip_group_quant_gemm_workspace_bytes sizes, behind the K rule of that route's predicate): QuantGemm's rule on the total rows;
+// a forced split (MOJO_HIP_GEMM_SPLITK) is cut to what the slabs' 16-byte stores (N % 4 == 0) and the K-tiles there are allow.
+static int group_quant_splitk(int64_t m_total, int64_t k, int64_t n) {
+  if (m_total <= 0 || n % 4 != 0 || !g256::gemm256_k_ok(k, 1)) return 1;
+  const int sk = quant_splitk(m_total, static_cast<int>(k), static_cast<int>(n)), nkt = static_cast<int>(k / 128);
   return sk > nkt ? nkt : sk;
 }
 
 static int64_t group_quant_prefix_bytes(int64_t groups) { return (GEMM_WS_INTS(static_cast<int>(groups)) * 4 + 64 + 15) / 16 * 16; }
 
+// What one mojo_hip_group_quant_gemm call launches: the tile height its prefix arrays are built for, the route, and the
+// epilogue's store forms.
+struct GroupQuantPlan {
+  enum Route { RAGGED, TILES128, TILES256, GENERIC } route = GENERIC;
+  int prefix_rows = 256;     // 16 / 32 / 64 (RAGGED, by the mean rows per group), 128 or 256
+  int splitk = 1;            // TILES256: + group_quant_finalize_kernel
+  bool vec4 = false;         // four outputs per store
+  int stage_rows = 0;        // TILES256, unsplit: row-staged stores (gemm256_core.h)
+};
+static GroupQuantPlan plan_group_quant_gemm(const GemmArgs& a, int64_t m_total, int out_elt_bytes) {
+  GroupQuantPlan p;
+  if (group_quant_ragged_ok(a, m_total) && (gemm_skinny_mask() & SKINNY_RAGGED)) {
+    p.route = GroupQuantPlan::RAGGED; p.prefix_rows = group_quant_ragged_mt(m_total, a.G) * 16;
+  } else if (group_quant_tile128_ok(a, out_elt_bytes) && g128::choose(group_quant_prefers_tile128(m_total, a.N, a.G))) {
+    p.route = GroupQuantPlan::TILES128; p.prefix_rows = 128; p.vec4 = true;
+  } else if (g256::gemm256_layout_ok(a, 1)) {
+    p.route = GroupQuantPlan::TILES256; p.splitk = group_quant_splitk(m_total, a.K, a.N);
+    p.vec4 = a.ldc % 4 == 0 && aligned_to(a.C, 4 * out_elt_bytes);
+    if (p.splitk == 1) p.stage_rows = quant_stage_rows(a, out_elt_bytes);
+  }
+  return p;
+}
+
 template <typename TO>
 static int run_group_quant(GemmArgs a, const float* rs, const bf16_t* cs, const void* counts, int counts_i64, int64_t m, void* slab_ws,
                            int32_t* ws, hipStream_t s) {
+  const GroupQuantPlan p = plan_group_quant_gemm(a, m, sizeof(TO));
   GemmTail tail;
   tail.C = a.C; tail.ld_bytes = a.ldc * static_cast<long long>(sizeof(TO)); tail.row_bytes = a.N * static_cast<long long>(sizeof(TO));
-  auto prefix = [&](int bm) { return launch_group_prefix(counts, counts_i64, a.G, bm, m, ws, ws + (a.G + 1), s, tail); };
-  if (group_quant_ragged_ok(a, m) && (gemm_skinny_mask() & SKINNY_RAGGED)) {
-    if (const int rc = prefix(group_quant_ragged_mt(m, a.G) * 16)) return rc;
-    return launch_group_quant_ragged<TO>(a, rs, cs, m, s);
-  }
-  if (group_quant_tile128_ok(a, sizeof(TO))) {
-    const int f = g128::forced_choice();
-    if (f < 0 ? group_quant_prefers_tile128(m, a.N, a.G) : f == 1) {
-      if (const int rc = prefix(128)) return rc;
-      EpilogueGroupDequant<TO> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, a.N, true};
-      const int rc = g128::launch<g256::PolI8>(a, epi, m, s);
-      if (!rc) {
-        char shape[160];                                   // (the core's own note: "gemm128:128x128:NK")
-        snprintf(shape, sizeof(shape), "%s", mojo_hip_last_launch());
-        note_launch("group_quant_tile128:%s", shape);
-      }
-      return rc;
+  if (const int rc = launch_group_prefix(counts, counts_i64, a.G, p.prefix_rows, m, ws, ws + (a.G + 1), s, tail)) return rc;
+  a.splitk = p.splitk; a.stage_rows = p.stage_rows;
+  if (p.splitk > 1) { a.slab = slab_ws; a.slab_rows = static_cast<int>(m); }
+  const EpilogueGroupDequant<TO> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, a.N, p.vec4};
+  switch (p.route) {
+    case GroupQuantPlan::RAGGED:
+      if (const int rc = launch_group_quant_ragged<TO>(a, rs, cs, m, p.prefix_rows / 16, s)) return rc;
+      note_launch("group_quant_ragged:rows%d", p.prefix_rows);
+      break;
+    case GroupQuantPlan::TILES128: {
+      if (const int rc = g128::launch<g256::PolI8>(a, epi, m, s)) return rc;
+      char shape[160];                                     // (the core's own note: "gemm128:128x128:NK")
+      snprintf(shape, sizeof(shape), "%s", mojo_hip_last_launch());
+      note_launch("group_quant_tile128:%s", shape);
+      break;
     }
-  }
-  if (g256::gemm256_layout_ok(a, 1)) {
-    if (const int rc = prefix(256)) return rc;
-    const int sk = group_quant_splitk(m, a.K, a.N);
-    const bool vec4 = a.ldc % 4 == 0 && aligned_to(a.C, 4 * sizeof(TO));
-    EpilogueGroupDequant<TO> epi{static_cast<TO*>(a.C), a.ldc, rs, cs, a.N, vec4};
-    if (sk > 1) {
-      a.splitk = sk; a.slab = slab_ws; a.slab_rows = static_cast<int>(m);
+    case GroupQuantPlan::TILES256:
       if (const int rc = g256::gemm256_launch<g256::PolI8>(a, epi, m, s)) return rc;
-      int64_t blocks = ceil_div(m * a.N / 4, 256);
-      if (blocks > 256 * 8) blocks = 256 * 8;
-      hipLaunchKernelGGL((group_quant_finalize_kernel<TO>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, static_cast<const int*>(slab_ws), sk, m,
-                         a.N, a.row_start, a.G, rs, cs, static_cast<TO*>(a.C));
-      MOJO_CHECK_LAUNCH("group_quant_gemm(finalize)");
-      note_launch("group_quant256:splitk%d", sk);
-      return MOJO_OK;
+      if (p.splitk > 1) {
+        const int64_t blocks = std::min<int64_t>(ceil_div(m * a.N / 4, 256), 256 * 8);
+        hipLaunchKernelGGL((group_quant_finalize_kernel<TO>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, static_cast<const int*>(slab_ws),
+                           p.splitk, m, a.N, a.row_start, a.G, rs, cs, static_cast<TO*>(a.C));
+        MOJO_CHECK_LAUNCH("group_quant_gemm(finalize)");
+        note_launch("group_quant256:splitk%d", p.splitk);
+      } else {
+        note_launch("group_quant256:%s", p.stage_rows ? "staged" : "direct");
+      }
+      break;
+    case GroupQuantPlan::GENERIC: {
+      const int64_t blocks = std::min<int64_t>(ceil_div(m * a.N, 256), 256 * 32);
+      hipLaunchKernelGGL((group_quant_generic_kernel<TO>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, static_cast<const int8_t*>(a.A),
+                         static_cast<const int8_t*>(a.W), rs, cs, static_cast<TO*>(a.C), m, a.K, a.N, a.row_start, a.G);
+      MOJO_CHECK_LAUNCH("group_quant_gemm(generic)");
+      note_launch("group_quant_generic");
+      break;
     }
-    a.stage_rows = (MOJO_SWITCH("MOJO_HIP_GEMM_STAGE_ROWS", 1) != 0 && sizeof(TO) == 2 && a.ldc % 8 == 0 && aligned_to(a.C, 16)) ? 1 : 0;
-    const int rc = g256::gemm256_launch<g256::PolI8>(a, epi, m, s);
-    if (!rc) note_launch("group_quant256:%s", a.stage_rows ? "staged" : "direct");
-    return rc;
   }
-  if (const int rc = prefix(256)) return rc;
-  int64_t blocks = ceil_div(m * a.N, 256);
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL((group_quant_generic_kernel<TO>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, static_cast<const int8_t*>(a.A),
-                     static_cast<const int8_t*>(a.W), rs, cs, static_cast<TO*>(a.C), m, a.K, a.N, a.row_start, a.G);
-  MOJO_CHECK_LAUNCH("group_quant_gemm(generic)");
-  note_launch("group_quant_generic");
   return MOJO_OK;
 }
 
@@ -890,19 +933,7 @@ static int run_group_quant(GemmArgs a, const float* rs, const bf16_t* cs, const 
 using namespace mojo;
 
 extern "C" int64_t mojo_hip_quant_gemm_workspace_bytes(int64_t m, int64_t k, int64_t n) {
-  // the largest split any path may choose for this shape (the skinny path needs [N,K] weights, which is not known here)
-  int sk = (k > 0 && k % 128 == 0) ? quant_splitk(m, static_cast<int>(k), static_cast<int>(n)) : 1;
-  if (m <= 128 && k > 0 && k % 256 == 0 && n % 64 == 0) {
-    const int s2 = quant_skinny_splitk(static_cast<int>(k), static_cast<int>(n), m);
-    if (s2 > sk) sk = s2;
-  }
-  if (k > 0 && k % 128 == 0) {                          // the 128-row tiles' own split, either weight layout
-    double t;
-    for (int kn = 0; kn < 2; ++kn) {
-      const int s3 = quant_tile128_splitk(m, static_cast<int>(k), static_cast<int>(n), kn != 0, &t);
-      if (s3 > sk) sk = s3;
-    }
-  }
+  const int sk = quant_max_splitk(m, k, n);
   return 64 + (sk > 1 ? static_cast<int64_t>(sk) * m * n * 4 : 0);
 }
 
@@ -940,7 +971,7 @@ extern "C" int mojo_hip_quant_gemm(const void* input, const void* weight, const 
 
 extern "C" int64_t mojo_hip_group_quant_gemm_workspace_bytes(int64_t m_total, int64_t k, int64_t n, int64_t num_groups) {
   if (num_groups < 1) num_groups = 1;
-  const int sk = (k > 0 && k % 128 == 0) ? group_quant_splitk(m_total, static_cast<int>(k), static_cast<int>(n)) : 1;
+  const int sk = group_quant_splitk(m_total, k, n);
   return group_quant_prefix_bytes(num_groups) + (sk > 1 ? static_cast<int64_t>(sk) * m_total * n * 4 : 0);
 }
 

@@ -6,15 +6,18 @@ prefill chunk, both weight layouts and the shapes where every route and its fall
 changes that should not move a route are checked on the hardware.  Routes do not depend on the values: floating-point and
 8-bit operands are uninitialised; index inputs (block tables, context lengths) are valid.
 
-    PYTHONPATH=. python tests/test_hip_gemm_routes.py     # rewrite the table from the library in use (a deliberate route change)
+    PYTHONPATH=. python tests/test_hip_gemm_routes.py [op ...]   # rewrite the table (or only the named sections) from the
+                                                                 # library in use: a deliberate route change, or a new section
+                                                                 # recorded from the library BEFORE the change it is to pin
 """
 import json
 import os
+import sys
 
 import pytest
 import torch
 
-from hip_utils import DEV, launches_of
+from hip_utils import DEV, launches_of, switch_env
 from mojo_opset_amd.backends.hip import lib as L
 from mojo_opset_amd.backends.hip.operators.gemm import (dense_gemm, dense_gemm_residual_rmsnorm, dense_gemm_swiglu,
                                                         qkv_rope_store)
@@ -124,8 +127,50 @@ def quant_cases():
             yield case(m, 4096, 4096, True, qdtype, F16)
 
 
+def group_quant_cases():
+    """The experts' int8 product: every leg of its route (ragged weight stream at the three tile heights, 128-row tiles, the
+    256 x 256 kernel row-staged, direct and split, the generic kernel), then the switches that force a leg."""
+    def case(groups, m, k, n, odtype=BF16, tag="", **env):
+        def run():
+            x, w = _tensor((m, k), torch.int8), _tensor((groups, n, k), torch.int8)
+            s_in, s_w = _tensor((m,), F32), _tensor((groups, n), BF16)
+            counts = torch.full((groups,), m // groups, dtype=torch.int32)
+            counts[0] += m - int(counts.sum())
+            counts = counts.to(DEV)
+            out = torch.empty(m, n, dtype=odtype, device=DEV)
+            lib = L.load()
+            with switch_env(**env):
+                ws = torch.empty(lib.mojo_hip_group_quant_gemm_workspace_bytes(m, k, n, groups), dtype=torch.uint8, device=DEV)
+                L.check(lib.mojo_hip_group_quant_gemm(L.ptr(x), L.ptr(w), L.ptr(s_in), L.ptr(s_w), L.ptr(out), L.ptr(counts), 0,
+                                                      m, k, n, groups, 1, L.dtype_code(odtype), L.ptr(ws), ws.numel(),
+                                                      L.stream_of(x)), "group_quant_gemm")
+            return out
+
+        def workspace():
+            with switch_env(**env):
+                return L.load().mojo_hip_group_quant_gemm_workspace_bytes(m, k, n, groups)
+        return f"{str(odtype)[6:]}:{groups}g:{m}x{k}x{n}{':' + tag if tag else ''}", run, workspace
+
+    for groups, m, k, n in ((4, 64, 256, 64), (4, 100, 256, 64), (4, 256, 256, 64),        # ragged: 16-, 32-, 64-row tiles
+                            (4, 400, 128, 128),                                             # 128-row tiles (mean 100 rows, K % 256 != 0)
+                            (8, 2048, 256, 4096),                                           # 128 tiles of 256 x 256: unsplit
+                            (8, 1032, 1024, 4096),                                          # 80 tiles over 8 K-tiles: split
+                            (4, 400, 96, 128)):                                             # K % 128 != 0: generic
+        yield case(groups, m, k, n)
+    for odtype in (F16, F32):
+        yield case(8, 2048, 256, 4096, odtype)
+        yield case(8, 1032, 1024, 4096, odtype)
+        yield case(4, 400, 128, 128, odtype)
+    for tag, tile128, splitk in (("256", "0", "1"), ("tile128", "1", None), ("tile128x256", "256", None), ("splitk", "0", "3"),
+                                 ("default", None, None)):                                  # (test_hip_quant_moe.py: TILE_LEGS)
+        yield case(8, 2048, 256, 4096, BF16, tag, MOJO_HIP_GEMM_TILE128=tile128, MOJO_HIP_GEMM_SPLITK=splitk)
+    yield case(4, 64, 256, 64, BF16, "skinny29", MOJO_HIP_GEMM_SKINNY="29")                 # the ragged bit off
+    yield case(8, 1032, 1024, 4096, BF16, "splitk40", MOJO_HIP_GEMM_SPLITK="40")            # a forced split past the K-tiles
+    yield case(8, 2048, 256, 4096, BF16, "nostage", MOJO_HIP_GEMM_STAGE_ROWS="0")
+
+
 CASES = {"gemm": gemm_cases, "gemm_residual_rmsnorm": resnorm_cases, "qkv_rope_store": qkv_cases,
-         "gemm_swiglu": swiglu_cases, "quant_gemm": quant_cases}
+         "gemm_swiglu": swiglu_cases, "quant_gemm": quant_cases, "group_quant_gemm": group_quant_cases}
 
 
 def routes(op):
@@ -145,7 +190,9 @@ def test_routes_match_the_table(op):
 
 
 if __name__ == "__main__":
-    table = {op: routes(op) for op in sorted(CASES)}
+    with open(TABLE) as f:
+        table = json.load(f) if sys.argv[1:] else {}
+    table.update({op: routes(op) for op in sorted(sys.argv[1:] or CASES)})
     with open(TABLE, "w") as f:
         json.dump(table, f, indent=1, sort_keys=True)
         f.write("\n")
