@@ -362,6 +362,28 @@ int mojo_hip_paged_prefill_swa(const void* query, const void* key_cache, const v
                                int layout_abab, int dtype, void* workspace, int64_t workspace_bytes,
                                int64_t local_window, int64_t global_window, mojo_stream_t stream);
 
+/* ---- MojoSWA (core/operators/attention.py:747-838): packed var-len queries [total_q_tokens][q_heads][head_dim] against
+ *      CONTIGUOUS packed keys and values [total_kv_tokens][kv_heads][head_dim] — no cache, no table.  Sequence b owns query
+ *      rows [cu_q_lens[b], cu_q_lens[b+1]) and K/V rows [cu_total_seq_lens[b], cu_total_seq_lens[b+1]); cu_q_lens[0] == 0,
+ *      cu_total_seq_lens[0] may be positive, kv_len >= q_len per sequence.  Causal, with the visibility rule and the
+ *      windows of mojo_hip_paged_prefill_swa (local_window < 0: none, global_window <= 0: none; neither: plain var-len
+ *      flash attention).  key and value share kv_token_stride and kv_head_stride (elements, multiples of 8; head_dim dense;
+ *      both bases 16-byte aligned), so views into a fused QKV projection are read in place; offsets are 64-bit.  The kernel
+ *      is the paged prefill's with the row of a key computed, not looked up: the same bits as mojo_hip_paged_prefill_gqa /
+ *      _swa on the same tokens at the same key split.  Hints, workspace and key split as there, the key capacity being
+ *      min(max_kv_len_hint, total_kv_tokens).  Rows of sequences without keys and rows at or past cu_q_lens[batch] are
+ *      zeros.  Every cu_total_seq_lens entry is clamped to [0, total_kv_tokens] by the kernel: no read leaves the tensors. */
+int64_t mojo_hip_swa_packed_workspace_bytes(int64_t total_q_tokens, int64_t total_kv_tokens, int64_t batch,
+                                            int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                                            int64_t max_q_len_hint, int64_t max_kv_len_hint, int64_t local_window,
+                                            int64_t global_window);
+int mojo_hip_swa_packed(const void* query, const void* key, const void* value, const int32_t* cu_q_lens,
+                        const int32_t* cu_total_seq_lens, void* out, int64_t total_q_tokens,
+                        int64_t total_kv_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                        int64_t kv_token_stride, int64_t kv_head_stride, int64_t max_q_len_hint,
+                        int64_t max_kv_len_hint, float softmax_scale, int layout_abab, int dtype, void* workspace,
+                        int64_t workspace_bytes, int64_t local_window, int64_t global_window, mojo_stream_t stream);
+
 /* ---- MojoPagedDecodeNstepSWA (experimental/operators/attention.py:1154-1262): `steps` query rows per sequence (draft
  *      verification, multi-token prediction) in one pass over the paged cache.  The arguments of mojo_hip_paged_decode_swa
  *      plus `steps`; query and out are [batch][steps][q_heads][head_dim] dense, total_seq_lens counts the `steps` new tokens.

@@ -5,8 +5,9 @@ from typing import Optional
 import torch
 
 from ....core.operators.attention import (MojoPagedDecodeGQA, MojoPagedDecodeNstepSWA, MojoPagedDecodeSWA,
-                                          MojoPagedPrefillGQA, MojoPagedPrefillSWA, assert_nstep_query,
-                                          assert_paged_decode_contract, assert_paged_prefill_contract)
+                                          MojoPagedPrefillGQA, MojoPagedPrefillSWA, MojoSWA, assert_nstep_query,
+                                          assert_paged_decode_contract, assert_paged_prefill_contract,
+                                          assert_swa_packed_contract)
 from .... import switches
 from .. import lib as L
 
@@ -124,6 +125,7 @@ _DECODE_SWA = ("mojo_hip_paged_decode_swa_workspace_bytes", "mojo_hip_paged_deco
 _DECODE_NSTEP = ("mojo_hip_paged_decode_nstep_workspace_bytes", "mojo_hip_paged_decode_nstep")
 _PREFILL_GQA = ("mojo_hip_paged_prefill_gqa_workspace_bytes", "mojo_hip_paged_prefill_gqa")
 _PREFILL_SWA = ("mojo_hip_paged_prefill_swa_workspace_bytes", "mojo_hip_paged_prefill_swa")
+_SWA_PACKED = ("mojo_hip_swa_packed_workspace_bytes", "mojo_hip_swa_packed")
 
 
 class HIPPagedDecodeGQA(MojoPagedDecodeGQA):
@@ -259,3 +261,70 @@ class HIPPagedPrefillSWA(MojoPagedPrefillSWA):
         _check_16bit_caches("HIPPagedPrefillSWA", query, key_cache, value_cache)
         return _paged_prefill(self, "HIPPagedPrefillSWA", _PREFILL_SWA, query, key_cache, value_cache, cu_q_lens,
                               block_table, softmax_scale, cu_total_seq_lens, max_q_len, max_total_seq_len, windows=windows)
+
+
+def _kv_in_place(key, value) -> bool:
+    """K and V can be read where they are: one set of strides, dense in head_dim, token and head strides multiples of 8
+    elements (16-byte rows), both bases 16-byte aligned.  Views into a fused QKV projection qualify."""
+    return (key.stride() == value.stride() and key.stride(2) == 1 and key.stride(0) % 8 == 0 and key.stride(1) % 8 == 0
+            and key.data_ptr() % 16 == 0 and value.data_ptr() % 16 == 0)
+
+
+class HIPSWA(MojoSWA):
+    """Packed var-len attention over contiguous K/V: the paged prefill kernel with the row of a key computed
+    (``(cu_total_seq_lens[b] + key) * token stride``, 64-bit) where the paged ops look it up — no table, no page-id loads,
+    no hole scan.  The same bits as `HIPPagedPrefillSWA` / `HIPPagedPrefillGQA` on the same tokens at the same key split.
+
+    K and V are read in place when they share strides, are dense in ``head_dim``, have token and head strides that are
+    multiples of 8 elements and 16-byte aligned bases (views into a fused QKV buffer do); otherwise both are made contiguous.
+    No host sync, capture-safe; ``max_q_len`` / ``max_total_seq_len`` are the upper-bound hints of the paged prefill.
+
+    Contract: ``cu_q_lens[0] == 0``; ``cu_total_seq_lens[0]`` may be positive; ``kv_len >= q_len`` per sequence.  Beyond the
+    reference: rows of a sequence with ``kv_len <= 0`` and rows at or past ``cu_q_lens[-1]`` are zeros.
+    ``MOJO_HIP_VALIDATE=1`` (a host sync) raises ``ValueError`` for arrays that decrease, ends past ``Tq`` / ``Tk``,
+    ``kv_len < q_len`` and a length above its hint.  Without it such a call is computed as the paged prefill computes the same
+    lengths: a length above its hint is truncated to the hint (query rows past it are zeros, keys past it unseen), the
+    ``q_len - kv_len`` leading rows of a sequence with fewer keys than queries see no key and hold no defined value, and
+    every ``cu_total_seq_lens`` entry is clamped to ``[0, Tk]`` by the kernel, so no read leaves the tensors."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key, value, cu_q_lens, cu_total_seq_lens, softmax_scale: Optional[float] = None, *,
+                max_q_len: Optional[int] = None, max_total_seq_len: Optional[int] = None):
+        what = "HIPSWA"
+        assert_swa_packed_contract(query, key, value, cu_q_lens, cu_total_seq_lens)
+        if not self.is_causal:
+            raise NotImplementedError(f"{what} supports causal attention only")
+        windows = _swa_windows(self, what)
+        L.require_cuda(query, key, value, cu_q_lens, cu_total_seq_lens)
+        tokens, hq, dim = query.shape
+        kv_tokens, hkv = key.shape[:2]
+        batch = cu_q_lens.shape[0] - 1
+        hint_q = int(max_q_len) if max_q_len else 0
+        hint_kv = int(max_total_seq_len) if max_total_seq_len else 0
+        if _validate_tables() and batch > 0:
+            q_lens, kv_lens = cu_q_lens[1:] - cu_q_lens[:-1], cu_total_seq_lens[1:] - cu_total_seq_lens[:-1]
+            if int(cu_q_lens[0]) != 0 or int(cu_total_seq_lens[0]) < 0 or bool((q_lens < 0).any()) or bool((kv_lens < 0).any()):
+                raise ValueError(f"{what}: cu_q_lens must start at 0 and both cumulative arrays must be non-decreasing")
+            if int(cu_q_lens[-1]) > tokens or int(cu_total_seq_lens[-1]) > kv_tokens:
+                raise ValueError(f"{what}: the cumulative lengths end past the query ({tokens}) or key ({kv_tokens}) tokens")
+            if bool((kv_lens < q_lens).any()):
+                raise ValueError(f"{what}: a sequence has fewer keys than queries (kv_len >= q_len is the contract)")
+            if (hint_q and int(q_lens.max()) > hint_q) or (hint_kv and int(kv_lens.max()) > hint_kv):
+                raise ValueError(f"{what}: a sequence's length exceeds its max_q_len / max_total_seq_len hint")
+        q = query if query.is_contiguous() else query.contiguous()
+        if tokens == 0:
+            return torch.empty_like(q)
+        if kv_tokens == 0:                                 # no key anywhere: every row reads as zeros
+            return torch.zeros_like(q)
+        k, v = (key, value) if _kv_in_place(key, value) else (key.contiguous(), value.contiguous())
+        cu_q, cu_kv = cu_q_lens.contiguous(), cu_total_seq_lens.contiguous()
+        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
+        out = torch.empty_like(q)
+        lib = L.load()
+        ws_bytes = getattr(lib, _SWA_PACKED[0])(tokens, kv_tokens, batch, hq, hkv, dim, hint_q, hint_kv, *windows)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes > 0 else None
+        L.check(getattr(lib, _SWA_PACKED[1])(
+            L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(cu_q), L.ptr(cu_kv), L.ptr(out), tokens, kv_tokens, batch, hq, hkv, dim,
+            k.stride(0), k.stride(1), hint_q, hint_kv, scale, 1 if self.gqa_layout == "ABAB" else 0,
+            L.dtype_code(q.dtype), L.ptr(ws), ws_bytes, *windows, L.stream_of(q)), what)
+        return out

@@ -2,7 +2,7 @@ from .activation import MojoSwiGLU
 from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
                         MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
                         MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
-                        MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant)
+                        MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
 from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
@@ -44,3 +44,6 @@ BEYOND_SURVEY_OPS = EXTENDED_OPS + KV_INT8_OPS + KV_INT8_SWA_OPS + QUANT_MOE_OPS
 NSTEP_OPS = ("MojoPagedDecodeNstepSWA",)
 # the n-step decode over the int8 cache: a set of its own for the same reason (golden: tests/nstep_kv_int8_golden.py)
 NSTEP_KV_INT8_OPS = ("MojoPagedDecodeNstepSWAWithKVDequant",)
+# packed var-len attention over contiguous K/V (the reference's core `MojoSWA`): a set of its own likewise (golden:
+# tests/swa_packed_golden.py)
+PACKED_ATTN_OPS = ("MojoSWA",)

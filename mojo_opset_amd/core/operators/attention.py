@@ -3,7 +3,7 @@
 Constructor arguments, contracts and `forward` signatures follow
 `mojo_opset/core/operators/attention.py` (`MojoPagedDecodeGQA` :113-232,
 `MojoPagedPrefillGQA` :315-451, contracts :12-37, `MojoPagedPrefillSWA` :533-650,
-`MojoPagedDecodeSWA` :653-744) and `mojo_opset/experimental/operators/attention.py` (`MojoPagedDecodeNstepSWA`
+`MojoPagedDecodeSWA` :653-744, `MojoSWA` :747-838) and `mojo_opset/experimental/operators/attention.py` (`MojoPagedDecodeNstepSWA`
 :1154-1262).  The classes are API-only; see `core/operator.py` for why the golden `forward` is not here.
 """
 from typing import Optional
@@ -144,6 +144,33 @@ class MojoPagedPrefillSWA(_PagedSWABase, MojoOperator):
 
     forward(query [T,Hq,D], key_cache, value_cache, cu_q_lens [B+1] i32, block_table [B,nb] i32,
             softmax_scale=None, cu_total_seq_lens=None, *, max_q_len=None, max_total_seq_len=None) -> [T,Hq,D]
+    """
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,
+                 local_window_size: Optional[int] = None):
+        super().__init__()
+        self._init_swa(is_causal, gqa_layout, global_window_size, local_window_size)
+
+
+def assert_swa_packed_contract(query, key, value, cu_q_lens, cu_total_seq_lens) -> None:
+    """int32 `[B+1]` cumulative lengths (reference :785-786) and packed 3-D query / key / value of one head_dim and dtype."""
+    assert isinstance(cu_q_lens, torch.Tensor) and isinstance(cu_total_seq_lens, torch.Tensor)
+    assert cu_q_lens.dtype == torch.int32
+    assert cu_total_seq_lens.dtype == torch.int32
+    assert cu_q_lens.dim() == 1 and cu_q_lens.shape[0] >= 1 and cu_total_seq_lens.shape == cu_q_lens.shape
+    assert query.dim() == 3 and key.dim() == 3 and value.shape == key.shape
+    assert key.shape[2] == query.shape[2] and key.shape[1] > 0 and query.shape[1] % key.shape[1] == 0
+    assert query.dtype == key.dtype == value.dtype
+
+
+class MojoSWA(_PagedSWABase, MojoOperator):
+    """Packed var-len queries against CONTIGUOUS packed keys and values (no cache, no table): the attention of a first
+    prefill.  Sequence ``b`` owns query rows ``[cu_q_lens[b], cu_q_lens[b+1])`` and K/V rows
+    ``[cu_total_seq_lens[b], cu_total_seq_lens[b+1])``; causal offset ``kv_len - q_len`` and the visibility rule of
+    `MojoPagedDecodeSWA` for every query row.  With no window it is plain var-len flash attention.
+
+    forward(query [Tq,Hq,D], key [Tk,Hkv,D], value [Tk,Hkv,D], cu_q_lens [B+1] i32, cu_total_seq_lens [B+1] i32,
+            softmax_scale=None) -> [Tq,Hq,D]
     """
 
     def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", global_window_size: Optional[int] = None,

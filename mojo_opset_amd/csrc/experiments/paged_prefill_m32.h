@@ -1,6 +1,6 @@
 // prefill_m32_kernel: prefill_kernel's decomposition (4 waves x 32 rows per workgroup, two workgroups per CU, 64-key tiles
 // double-buffered by LDS-DMA, lazy reference maximum, key split) on v_mfma_f32_32x32x16 instead of v_mfma_f32_16x16x32,
-// head_dim 128.  Included by paged_prefill_gqa.hip behind prefill_kernel in an EXPERIMENTS build (MOJO_HIP_BUILD_EXPERIMENTS=1;
+// head_dim 128.  Included by paged_prefill_body.h behind prefill_kernel in an EXPERIMENTS build (MOJO_HIP_BUILD_EXPERIMENTS=1;
 // MOJO_HIP_PREFILL_M32=1 selects it per call).  Parity-green on the whole prefill suite, measured 4-5 % SLOWER than prefill_kernel
 // on every bench case (round 4, A/B in one process: 4x2048 867 vs 906 TF, 1x16384 1 053 vs 1 103, 16 ragged 642 vs 663).
 //

@@ -1,5 +1,5 @@
 // prefill_pp_kernel: MojoPagedPrefillGQA with the two waves of every SIMD held in OPPOSITE phases (round 3).
-// Included by paged_prefill_gqa.hip behind prefill_kernel (shares PrefillArgs, pf_mfma, the tile constants and the formulation).
+// Included by paged_prefill_body.h behind prefill_kernel (shares PrefillArgs, pf_mfma, the tile constants and the formulation).
 //
 // prefill_kernel runs two independent 4-wave workgroups per CU.  A wave's tile is QK^T (matrix pipe) -> softmax (vector
 // unit, a long dependent chain) -> PV (matrix pipe), and nothing orders the two workgroups of a CU against each other: the
