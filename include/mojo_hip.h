@@ -26,7 +26,8 @@ extern "C" {
 
 typedef void* mojo_stream_t;
 
-enum mojo_dtype { MOJO_F32 = 0, MOJO_F16 = 1, MOJO_BF16 = 2, MOJO_I8 = 3, MOJO_F8E4M3 = 4 };
+enum mojo_dtype { MOJO_F32 = 0, MOJO_F16 = 1, MOJO_BF16 = 2, MOJO_I8 = 3, MOJO_F8E4M3 = 4,
+                  MOJO_I32 = 5 /* int32 GEMM accumulators: mojo_hip_dequant_swiglu_quant only */ };
 
 enum mojo_status {
   MOJO_OK = 0,
@@ -577,6 +578,44 @@ int mojo_hip_residual_add_rmsnorm_quant(const void* hidden, const void* residual
                                         const float* smooth_scale, void* out_q, void* out_sum, float* out_normed,
                                         float* out_scale, int64_t rows, int64_t dim, int dtype, int quant_dtype,
                                         float q_min, float eps, mojo_stream_t stream);
+
+/* ---- The dense W8A8 quantiser ops (QUANT_DENSE_OPS).  Every per-column vector (weight, bias, smooth_scale, scale,
+ *      weight_scale, quant_scale) and activation_scale are fp32; nothing synchronises with the host.
+ *      rmsnorm_quant (core/operators/normalization.py:136-213): residual_add_rmsnorm_quant's arithmetic and kernels with
+ *      no residual and no sum output; its launch tags start with `rmsnorm_quant`.
+ *      layernorm_quant (:216-305, :536-646): s = hidden [+ residual, rounded to the input dtype; residual nullable],
+ *      y = layer_norm(s.float(), weight, bias, eps) [* smooth_scale, nullable] in fp32 (mean and biased variance over the
+ *      row; weight and bias both given or both NULL), scale = max(amax|y|, 1e-12) / q_max (127 or 448),
+ *      q = clamp(round_half_even(y / scale), q_min, q_max) as int8 or as float8_e4m3fn of that integer.  out_sum (T,
+ *      nullable) receives s — for BOTH norm_pos of MojoResidualAddLayerNormQuant.  out_scale is fp32 [rows].
+ *      static_quant (core/operators/quantize.py:9-74): q[i] = clamp(round_half_even(float(x[i]) / scale[i % scale_len]),
+ *      -128, 127) as int8 (or +-448 as float8_e4m3fn); n a multiple of scale_len; input dtype in {f32, f16, bf16}.
+ *      dequant (:77-117): out[i] = round_to_out_dtype(float(q[i]) * scale[...]); input MOJO_I8 or MOJO_F8E4M3; out_dtype in
+ *      {f32, f16, bf16}.  token_dim == 0: scale[i % scale_len] (a tensor of trailing dimensions); token_dim > 0: per-token
+ *      scale[i / token_dim] (rows of token_dim elements, scale_len == n / token_dim).
+ *      dequant_swiglu_quant (:250-354): x [rows, 2 * hidden] of dtype MOJO_I32 (GEMM accumulators), f32, f16 or bf16;
+ *      y = float(x) * weight_scale[e] ([E, 2 * hidden]) [* activation_scale[row], nullable] [+ bias, nullable: [2 * hidden],
+ *      or [E, 2 * hidden] when bias_is_grouped]; z = silu(y[hidden:]) * y[:hidden] (activate_left != 0: silu(y[:hidden]) *
+ *      y[hidden:]) * quant_scale[e] ([E, hidden]); scale = max(amax|z|, 1e-12) / 127; q = clamp(round_half_even(z / scale),
+ *      -128, 127).  e is the row's expert: rows sorted by expert, token_count int32 / int64 [E] on the device, scanned inside
+ *      the kernel (negative counts read as zero); rows at or past sum(token_count): int8 zeros, scale 1.  token_count NULL:
+ *      num_experts must be 1 and that expert owns every row.  out_q int8 [rows, hidden], out_scale fp32 [rows]; at most
+ *      1024 experts.                                                                                                    */
+int mojo_hip_rmsnorm_quant(const void* hidden, const float* weight, const float* smooth_scale, void* out_q,
+                           float* out_scale, int64_t rows, int64_t dim, int dtype, int quant_dtype, float q_min,
+                           float eps, mojo_stream_t stream);
+int mojo_hip_layernorm_quant(const void* hidden, const void* residual, const float* weight, const float* bias,
+                             const float* smooth_scale, void* out_q, void* out_sum, float* out_scale, int64_t rows,
+                             int64_t dim, int dtype, int quant_dtype, float q_min, float eps, mojo_stream_t stream);
+int mojo_hip_static_quant(const void* input, const float* scale, void* out_q, int64_t n, int64_t scale_len, int dtype,
+                          int quant_dtype, mojo_stream_t stream);
+int mojo_hip_dequant(const void* input, const float* scale, void* out, int64_t n, int64_t scale_len, int64_t token_dim,
+                     int in_dtype, int out_dtype, mojo_stream_t stream);
+int mojo_hip_dequant_swiglu_quant(const void* x, const float* weight_scale, const float* activation_scale,
+                                  const float* bias, int bias_is_grouped, const float* quant_scale,
+                                  const void* token_count, int token_count_is_i64, void* out_q, float* out_scale,
+                                  int64_t rows, int64_t hidden, int64_t num_experts, int activate_left, int dtype,
+                                  mojo_stream_t stream);
 
 /* ---- MojoQuantExperts / MojoMoEDynamicQuant (core/operators/moe.py:452-667, quantize.py:178-247): W8A8 experts.
  *      group_quant_gemm: out[rows of g] = round_out( float(A8[rows of g] @ W8[g]^T) * weight_scale[g][n] * input_scale[m] )

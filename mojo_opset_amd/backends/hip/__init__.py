@@ -12,6 +12,8 @@ from .operators.compute_with_comm import (HIPAllGatherGemm, HIPGemmAll2All, HIPG
                                           HIPGemmReduceScatter)
 from .operators.moe import (HIPExperts, HIPMoE, HIPMoECombine, HIPMoEDispatch, HIPMoEGating, HIPQuantExperts,  # noqa: F401
                             HIPQuantMoE)
-from .operators.quantize import HIPDynamicQuant, HIPMoEDynamicQuant, HIPResidualAddRMSNormQuant  # noqa: F401
+from .operators.quantize import (HIPDequant, HIPDequantSwiGLUQuant, HIPDynamicQuant, HIPLayerNormQuant,  # noqa: F401
+                                 HIPMoEDynamicQuant, HIPResidualAddLayerNormQuant, HIPResidualAddRMSNormQuant,
+                                 HIPRMSNormQuant, HIPStaticQuant)
 from .operators.sampling import (HIPApplyPenaltiesTempurate, HIPJoinProbRejectSampling, HIPRejectSampling,  # noqa: F401
                                  HIPTopKSampling, HIPTopPFilter, HIPTopPSampling)

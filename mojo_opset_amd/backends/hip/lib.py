@@ -14,10 +14,10 @@ import torch
 _PKG = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 DEFAULT_LIB = os.path.join(_PKG, "lib", "libmojo_hip.so")
 
-MOJO_F32, MOJO_F16, MOJO_BF16, MOJO_I8, MOJO_F8E4M3 = 0, 1, 2, 3, 4
+MOJO_F32, MOJO_F16, MOJO_BF16, MOJO_I8, MOJO_F8E4M3, MOJO_I32 = 0, 1, 2, 3, 4, 5
 _DTYPE_CODE = {
     torch.float32: MOJO_F32, torch.float16: MOJO_F16, torch.bfloat16: MOJO_BF16,
-    torch.int8: MOJO_I8, torch.float8_e4m3fn: MOJO_F8E4M3,
+    torch.int8: MOJO_I8, torch.float8_e4m3fn: MOJO_F8E4M3, torch.int32: MOJO_I32,
 }
 
 MOJO_EINVAL, MOJO_EUNSUPPORTED, MOJO_ELAUNCH, MOJO_EWORKSPACE = -1, -2, -3, -4
@@ -124,6 +124,11 @@ SIGNATURES = {
     "mojo_hip_group_quant_gemm_workspace_bytes": (c_int64, [_I, _I, _I, _I]),
     "mojo_hip_group_quant_gemm": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _I, _I, _I, _I, c_int, c_int, _P, _I, _P]),
     "mojo_hip_moe_dynamic_quant": (c_int, [_P, _P, _P, c_int, _P, _P, _I, _I, _I, c_int, c_int, _P]),
+    "mojo_hip_rmsnorm_quant": (c_int, [_P, _P, _P, _P, _P, _I, _I, c_int, c_int, c_float, c_float, _P]),
+    "mojo_hip_layernorm_quant": (c_int, [_P] * 8 + [_I, _I, c_int, c_int, c_float, c_float, _P]),
+    "mojo_hip_static_quant": (c_int, [_P, _P, _P, _I, _I, c_int, c_int, _P]),
+    "mojo_hip_dequant": (c_int, [_P, _P, _P, _I, _I, _I, c_int, c_int, _P]),
+    "mojo_hip_dequant_swiglu_quant": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, _I, _I, _I, c_int, c_int, _P]),
     "mojo_hip_sampling_max_k": (c_int64, []),
     "mojo_hip_sampling_workspace_bytes": (c_int64, [_I, _I, _I, _I]),
     "mojo_hip_top_p_filter": (c_int, [_P, _P, _P, _I, _I, _I, c_float, _I, c_float, _I, c_int, _P, _I, _P]),

@@ -12,7 +12,8 @@ from .mlp import MojoSwiGLUMLP
 from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts, MojoQuantMoE
 from .normalization import MojoResidualAddRMSNorm, MojoRMSNorm, MojoRMSNormInplace
 from .position_embedding import MojoApplyRoPE, MojoRotaryEmbedding
-from .quantize import MojoDynamicQuant, MojoMoEDynamicQuant, MojoResidualAddRMSNormQuant
+from .quantize import (MojoDequant, MojoDequantSwiGLUQuant, MojoDynamicQuant, MojoLayerNormQuant, MojoMoEDynamicQuant,
+                       MojoResidualAddLayerNormQuant, MojoResidualAddRMSNormQuant, MojoRMSNormQuant, MojoStaticQuant)
 from .sampling import (MojoApplyPenaltiesTempurate, MojoJoinProbRejectSampling, MojoRejectSampling, MojoTopKSampling,
                        MojoTopPFilter, MojoTopPSampling)
 
@@ -47,3 +48,7 @@ NSTEP_KV_INT8_OPS = ("MojoPagedDecodeNstepSWAWithKVDequant",)
 # packed var-len attention over contiguous K/V (the reference's core `MojoSWA`): a set of its own likewise (golden:
 # tests/swa_packed_golden.py)
 PACKED_ATTN_OPS = ("MojoSWA",)
+# the activation ops between the GEMMs of a dense W8A8 decoder layer: norm + quant, static quant, dequant and the fc1 -> fc2
+# stage.  A set of its own likewise (golden: tests/quant_dense_golden.py)
+QUANT_DENSE_OPS = ("MojoRMSNormQuant", "MojoLayerNormQuant", "MojoResidualAddLayerNormQuant", "MojoStaticQuant", "MojoDequant",
+                   "MojoDequantSwiGLUQuant")

@@ -12,9 +12,25 @@
 // operations (no FMA contraction, no reciprocal): with the same row statistics the quantised bytes equal the golden's.
 //
 // Algorithmic bytes per element: dynamic quant elt + 1; norm+quant (pre) 3*elt + 1 (+ weight, smooth once).
+//
+// MojoRMSNormQuant (normalization.py:136-213) is the norm+quant arithmetic with no residual and no sum output: the same kernel
+// with residual == nullptr, behind an entry point of its own (mojo_hip_rmsnorm_quant) whose launch tags say `rmsnorm_quant`.
+//
+// MojoLayerNormQuant / MojoResidualAddLayerNormQuant (normalization.py:216-305, :536-646): layernorm_quant_kernel, the centred
+// form of the same design.  Three reductions over the register-resident row: the sum (mean), the sum of squared deviations
+// from that mean (biased variance; not E[x^2] - mean^2, which cancels), the row maximum.  rstd = 1 / sqrt(var + eps) with the
+// IEEE division and square root.  The elementwise form: torch's CPU layer_norm, fed the statistics it reports itself
+// (native_layer_norm), is reproduced bit for bit by
+//     y = fma((x - mean) * rstd, w, b)          (affine)          y = (x - mean) * rstd          (no affine)
+// on every element of 64 rows of 128, 257, 1000, 4096 and 20000 columns; with a separately rounded `* w` then `+ b` 23 % of the
+// elements differ in the last place, and the scaled form (x * rstd + (-mean * rstd)) * w + b misses about a third with and
+// without the affine pair.  So the last multiply-add is ONE fused operation here, on purpose, and the only one.  The
+// statistics themselves differ from torch's in summation order (last place of mean and rstd), which is what the test bound
+// of one quantisation step on at most 2e-3 of the elements covers.
 #include <math.h>
 
 #include "common.h"
+#include "quant_common.h"
 
 namespace mojo {
 
@@ -33,33 +49,6 @@ struct NormQuantArgs {
   int fp8;                   // 0: int8, 1: float8_e4m3fn
   int tiny_scale_is_one;     // MojoDynamicQuant's `where(scale < 1e-6, 1.0, scale)`
 };
-
-__device__ __forceinline__ float block_max256(float x, float* smem) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) smem[wave] = x;
-  __syncthreads();
-  const float r = fmaxf(fmaxf(smem[0], smem[1]), fmaxf(smem[2], smem[3]));
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ unsigned char to_fp8_e4m3(float v) {
-  // v_cvt_pk_fp8_f32: OCP e4m3 (the "fn" format) on gfx950, round to nearest even
-  const int packed = __builtin_amdgcn_cvt_pk_fp8_f32(v, v, 0, false);
-  return static_cast<unsigned char>(packed & 0xff);
-}
-
-// round_half_even(y / scale), bit-identical to the IEEE division, at the price of one multiply for almost every element:
-// t = y * (1/scale) is within a few ulp of the true quotient, so rint(t) can only differ from rint(y / scale) when t sits
-// within that distance of a rounding boundary (k + 0.5); only those elements take the real division.  |t| <= ~448.
-__device__ __forceinline__ float round_quotient(float y, float scale, float inv_scale) {
-  const float t = y * inv_scale;
-  const float r = rintf(t);
-  if (fabsf(fabsf(t - r) - 0.5f) < 1e-3f) return rintf(__fdiv_rn(y, scale));
-  return r;
-}
 
 // TPR = threads per row: 256 (a row per workgroup) or 64 (a row per WAVE, four rows per workgroup, no LDS and no barrier:
 // dynamic quant only — the row maximum is exact in any order, a sum of squares is not).  Many short rows on a workgroup each
@@ -284,8 +273,192 @@ __global__ __launch_bounds__(256) void norm_quant_kernel(NormQuantArgs a) {
   }
 }
 
+struct LayerNormQuantArgs {
+  const void* hidden;        // [rows, dim] T
+  const void* residual;      // [rows, dim] T or nullptr
+  const float* weight;       // [dim] fp32, or nullptr together with bias (elementwise_affine = False)
+  const float* bias;         // [dim] fp32 or nullptr
+  const float* smooth;       // [dim] fp32 or nullptr
+  void* out_q;               // [rows, dim] int8 / fp8
+  void* out_sum;             // [rows, dim] T or nullptr: hidden + residual (both norm_pos)
+  float* out_scale;          // [rows]
+  int64_t rows;
+  int dim;
+  float eps, q_max, q_min;
+  int fp8;
+};
+
+// LayerNorm + quant: a row per 256-thread workgroup, the row's (summed) x in registers from the first load to the quantised
+// store; rows of more than CACHE * 256 vectors re-read (and re-add) what does not fit.  The wide forms are held to 128 VGPRs
+// (four workgroups per CU, norm_quant_kernel's occupancy): left alone hipcc hoists the weight, bias and smooth loads of all
+// four cached vectors at once and takes 136-143 (three workgroups), with no spill either way.
+template <typename T, int VEC, int CACHE, bool NT>
+__global__ __launch_bounds__(256, VEC > 1 ? 4 : 1) void layernorm_quant_kernel(LayerNormQuantArgs a) {
+  typedef typename vec_of<T, VEC>::type V;
+  __shared__ float red[4];
+  const int n_vec = a.dim / VEC;
+  const int tid = threadIdx.x;
+  const T* hidden = static_cast<const T*>(a.hidden);
+  const T* residual = static_cast<const T*>(a.residual);
+  T* out_sum = static_cast<T*>(a.out_sum);
+  unsigned char* out_q = static_cast<unsigned char*>(a.out_q);
+  const float dim_f = static_cast<float>(a.dim);
+
+  for (int64_t row = blockIdx.x; row < a.rows; row += gridDim.x) {
+    const int64_t base = row * a.dim;
+    auto load_sum = [&](int v, float (&f)[VEC]) {              // x of vector v (hidden + residual rounded to T), as floats
+      V x = NT ? load_vec_nt<T, VEC>(hidden + base + v * VEC) : load_vec<T, VEC>(hidden + base + v * VEC);
+      if (residual) {
+        const V r = NT ? load_vec_nt<T, VEC>(residual + base + v * VEC) : load_vec<T, VEC>(residual + base + v * VEC);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+          vset<T, VEC>(x, j, elt<T>::from_f(elt<T>::to_f(vget<T, VEC>(x, j)) + elt<T>::to_f(vget<T, VEC>(r, j))));
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) f[j] = elt<T>::to_f(vget<T, VEC>(x, j));
+      return x;
+    };
+    // ---- pass 1: the row into registers, its sum ------------------------------------------------------------------------
+    float y[CACHE][VEC];
+    float sum = 0.f;
+    {
+      V xr[CACHE];                                             // batched loads, clamped index (norm_quant_kernel, pass 1)
+#pragma unroll
+      for (int c = 0; c < CACHE; ++c) xr[c] = NT ? load_vec_nt<T, VEC>(hidden + base + min(tid + c * 256, n_vec - 1) * VEC) : load_vec<T, VEC>(hidden + base + min(tid + c * 256, n_vec - 1) * VEC);
+      if (residual) {
+        V rr[CACHE];
+#pragma unroll
+        for (int c = 0; c < CACHE; ++c) rr[c] = NT ? load_vec_nt<T, VEC>(residual + base + min(tid + c * 256, n_vec - 1) * VEC) : load_vec<T, VEC>(residual + base + min(tid + c * 256, n_vec - 1) * VEC);
+#pragma unroll
+        for (int c = 0; c < CACHE; ++c)
+#pragma unroll
+          for (int j = 0; j < VEC; ++j)
+            vset<T, VEC>(xr[c], j, elt<T>::from_f(elt<T>::to_f(vget<T, VEC>(xr[c], j)) + elt<T>::to_f(vget<T, VEC>(rr[c], j))));
+      }
+      if (out_sum) {
+#pragma unroll
+        for (int c = 0; c < CACHE; ++c)
+          if (tid + c * 256 < n_vec) { if (NT) store_vec_nt<T, VEC>(out_sum + base + (tid + c * 256) * VEC, xr[c]); else store_vec<T, VEC>(out_sum + base + (tid + c * 256) * VEC, xr[c]); }
+      }
+#pragma unroll
+      for (int c = 0; c < CACHE; ++c) {
+        const bool live = tid + c * 256 < n_vec;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          y[c][j] = live ? elt<T>::to_f(vget<T, VEC>(xr[c], j)) : 0.f;
+          sum += y[c][j];
+        }
+      }
+    }
+    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
+      float f[VEC];
+      const V x = load_sum(v, f);
+      if (out_sum) { if (NT) store_vec_nt<T, VEC>(out_sum + base + v * VEC, x); else store_vec<T, VEC>(out_sum + base + v * VEC, x); }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) sum += f[j];
+    }
+    sum = block_sum<4>(sum, red);
+    __syncthreads();
+    const float mean = __fdiv_rn(sum, dim_f);
+    // ---- pass 2: the sum of squared deviations -------------------------------------------------------------------------
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < CACHE; ++c) {
+      if (tid + c * 256 < n_vec) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const float d = __fsub_rn(y[c][j], mean);
+          ss = fmaf(d, d, ss);
+        }
+      }
+    }
+    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
+      float f[VEC];
+      load_sum(v, f);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float d = __fsub_rn(f[j], mean);
+        ss = fmaf(d, d, ss);
+      }
+    }
+    ss = block_sum<4>(ss, red);
+    __syncthreads();
+    const float rstd = __fdiv_rn(1.0f, sqrtf(__fadd_rn(__fdiv_rn(ss, dim_f), a.eps)));
+    // ---- pass 3: y, row maximum ------------------------------------------------------------------------------------------
+    auto finish = [&](int v, float (&f)[VEC]) {                // x -> y of vector v (v < n_vec)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) f[j] = __fmul_rn(__fsub_rn(f[j], mean), rstd);
+      if (a.weight) {
+        float w[VEC], b[VEC];
+        load_f32_vec<VEC>(a.weight, v, w);
+        load_f32_vec<VEC>(a.bias, v, b);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) f[j] = fmaf(f[j], w[j], b[j]);       // fused on purpose: the header comment
+      }
+      if (a.smooth) {
+        float sm[VEC];
+        load_f32_vec<VEC>(a.smooth, v, sm);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) f[j] = __fmul_rn(f[j], sm[j]);
+      }
+    };
+    float amax = 0.f;
+#pragma unroll
+    for (int c = 0; c < CACHE; ++c) {
+      finish(min(tid + c * 256, n_vec - 1), y[c]);             // (clamped: no branch around the loads; dead slots are unused)
+      if (tid + c * 256 < n_vec) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(y[c][j]));
+      }
+    }
+    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
+      float f[VEC];
+      load_sum(v, f);
+      finish(v, f);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(f[j]));
+    }
+    amax = block_max256(amax, red);
+    const float scale = __fdiv_rn(fmaxf(amax, 1e-12f), a.q_max);
+    if (tid == 0) a.out_scale[row] = scale;
+    const float inv_scale = __fdiv_rn(1.0f, scale);
+    // ---- pass 4: quantise -------------------------------------------------------------------------------------------------
+#pragma unroll
+    for (int c = 0; c < CACHE; ++c) {
+      const int v = tid + c * 256;
+      if (v < n_vec) quantise_store<VEC, NT>(out_q + base + v * VEC, y[c], scale, inv_scale, a.q_min, a.q_max, a.fp8);
+    }
+    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
+      float f[VEC];
+      load_sum(v, f);
+      finish(v, f);
+      quantise_store<VEC, NT>(out_q + base + v * VEC, f, scale, inv_scale, a.q_min, a.q_max, a.fp8);
+    }
+  }
+}
+
 template <typename T>
-static int launch_norm_quant(const NormQuantArgs& a, hipStream_t s) {
+static int launch_layernorm_quant(const LayerNormQuantArgs& a, hipStream_t s) {
+  constexpr int WIDE = 16 / sizeof(T);
+  const size_t al = WIDE * sizeof(T);
+  const bool wide = a.dim % WIDE == 0 && aligned_to(a.hidden, al) && (!a.residual || aligned_to(a.residual, al)) &&
+                    (!a.out_sum || aligned_to(a.out_sum, al)) && aligned_to(a.out_q, WIDE) &&
+                    (!a.weight || (aligned_to(a.weight, 16) && aligned_to(a.bias, 16))) && (!a.smooth || aligned_to(a.smooth, 16));
+  const unsigned blocks = static_cast<unsigned>(a.rows > 256 * 32 ? 256 * 32 : a.rows);
+  const long long moved = a.rows * static_cast<long long>(a.dim) * (static_cast<long long>(sizeof(T)) * (1 + (a.residual ? 1 : 0) + (a.out_sum ? 1 : 0)) + 1);
+  const bool nt = wide && stream_nt(moved);             // (the scalar form has no non-temporal twin)
+  if (nt) hipLaunchKernelGGL((layernorm_quant_kernel<T, WIDE, 4, true>), dim3(blocks), dim3(256), 0, s, a);
+  else if (wide) hipLaunchKernelGGL((layernorm_quant_kernel<T, WIDE, 4, false>), dim3(blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((layernorm_quant_kernel<T, 1, 8, false>), dim3(blocks), dim3(256), 0, s, a);
+  MOJO_CHECK_LAUNCH("layernorm_quant");
+  const int cached_vecs = wide ? 4 * 256 : 8 * 256;
+  note_launch("layernorm_quant:%s:%s:%s", wide ? "wide" : "scalar", a.dim / (wide ? WIDE : 1) <= cached_vecs ? "resident" : "reread",
+              nt ? "nt" : "cached");
+  return MOJO_OK;
+}
+
+template <typename T>
+static int launch_norm_quant(const NormQuantArgs& a, hipStream_t s, const char* op) {
   constexpr int WIDE = 16 / sizeof(T);
   const size_t al = WIDE * sizeof(T);
   const bool wide = a.dim % WIDE == 0 && aligned_to(a.hidden, al) && (!a.residual || aligned_to(a.residual, al)) &&
@@ -301,22 +474,23 @@ static int launch_norm_quant(const NormQuantArgs& a, hipStream_t s) {
     if (nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true, 64>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, false, 64>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
     MOJO_CHECK_LAUNCH("norm_quant");
-    note_launch("norm_quant:wide:tpr64:%s", nt ? "nt" : "cached");
+    note_launch("%s:wide:tpr64:%s", op, nt ? "nt" : "cached");
     return MOJO_OK;
   }
   if (nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   else if (wide) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((norm_quant_kernel<T, 1, 8>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   MOJO_CHECK_LAUNCH("norm_quant");
-  note_launch("norm_quant:%s:tpr256:%s", wide ? "wide" : "scalar", nt ? "nt" : "cached");
+  note_launch("%s:%s:tpr256:%s", op, wide ? "wide" : "scalar", nt ? "nt" : "cached");
   return MOJO_OK;
 }
 
-static int dispatch_norm_quant(const NormQuantArgs& a, int dtype, hipStream_t s) {
+// `op`: the first field of the launch tag (`norm_quant` for the two ops that have always come here)
+static int dispatch_norm_quant(const NormQuantArgs& a, int dtype, hipStream_t s, const char* op = "norm_quant") {
   switch (dtype) {
-    case MOJO_F32: return launch_norm_quant<float>(a, s);
-    case MOJO_F16: return launch_norm_quant<f16_t>(a, s);
-    case MOJO_BF16: return launch_norm_quant<bf16_t>(a, s);
+    case MOJO_F32: return launch_norm_quant<float>(a, s, op);
+    case MOJO_F16: return launch_norm_quant<f16_t>(a, s, op);
+    case MOJO_BF16: return launch_norm_quant<bf16_t>(a, s, op);
     default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "norm_quant: dtype %d not supported", dtype);
   }
 }
@@ -358,4 +532,49 @@ extern "C" int mojo_hip_residual_add_rmsnorm_quant(const void* hidden, const voi
   a.q_min = q_min;
   a.tiny_scale_is_one = 0;
   return dispatch_norm_quant(a, dtype, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mojo_hip_rmsnorm_quant(const void* hidden, const float* weight, const float* smooth_scale, void* out_q,
+                                      float* out_scale, int64_t rows, int64_t dim, int dtype, int quant_dtype, float q_min,
+                                      float eps, mojo_stream_t stream) {
+  if (rows == 0) return MOJO_OK;
+  MOJO_REQUIRE(hidden && weight && out_q && out_scale, MOJO_EINVAL, "rmsnorm_quant: null pointer");
+  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "rmsnorm_quant: bad shape rows=%lld dim=%lld",
+               (long long)rows, (long long)dim);
+  MOJO_REQUIRE(quant_dtype == MOJO_I8 || quant_dtype == MOJO_F8E4M3, MOJO_EUNSUPPORTED,
+               "rmsnorm_quant: quant dtype %d (int8 / fp8-e4m3 only)", quant_dtype);
+  NormQuantArgs a{};
+  a.hidden = hidden; a.weight = weight; a.smooth = smooth_scale; a.out_q = out_q; a.out_scale = out_scale;
+  a.rows = rows; a.dim = static_cast<int>(dim);
+  a.eps = eps; a.fp8 = quant_dtype == MOJO_F8E4M3;
+  a.q_max = a.fp8 ? 448.f : 127.f;
+  a.q_min = q_min;
+  a.tiny_scale_is_one = 0;
+  return dispatch_norm_quant(a, dtype, static_cast<hipStream_t>(stream), "rmsnorm_quant");
+}
+
+extern "C" int mojo_hip_layernorm_quant(const void* hidden, const void* residual, const float* weight, const float* bias,
+                                        const float* smooth_scale, void* out_q, void* out_sum, float* out_scale, int64_t rows,
+                                        int64_t dim, int dtype, int quant_dtype, float q_min, float eps, mojo_stream_t stream) {
+  if (rows == 0) return MOJO_OK;
+  MOJO_REQUIRE(hidden && out_q && out_scale, MOJO_EINVAL, "layernorm_quant: null pointer");
+  MOJO_REQUIRE((weight == nullptr) == (bias == nullptr), MOJO_EINVAL, "layernorm_quant: weight and bias come together or not at all");
+  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "layernorm_quant: bad shape rows=%lld dim=%lld",
+               (long long)rows, (long long)dim);
+  MOJO_REQUIRE(quant_dtype == MOJO_I8 || quant_dtype == MOJO_F8E4M3, MOJO_EUNSUPPORTED,
+               "layernorm_quant: quant dtype %d (int8 / fp8-e4m3 only)", quant_dtype);
+  LayerNormQuantArgs a{};
+  a.hidden = hidden; a.residual = residual; a.weight = weight; a.bias = bias; a.smooth = smooth_scale;
+  a.out_q = out_q; a.out_sum = out_sum; a.out_scale = out_scale;
+  a.rows = rows; a.dim = static_cast<int>(dim);
+  a.eps = eps; a.fp8 = quant_dtype == MOJO_F8E4M3;
+  a.q_max = a.fp8 ? 448.f : 127.f;
+  a.q_min = q_min;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case MOJO_F32: return launch_layernorm_quant<float>(a, s);
+    case MOJO_F16: return launch_layernorm_quant<f16_t>(a, s);
+    case MOJO_BF16: return launch_layernorm_quant<bf16_t>(a, s);
+    default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "layernorm_quant: dtype %d not supported", dtype);
+  }
 }

@@ -17,10 +17,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "moe_row_expert.h"
 
 namespace mojo {
-
-constexpr int MOE_QUANT_MAX_EXPERTS = 1024;
 
 __device__ __forceinline__ float moe_quant_block_max(float x, float* smem) {
 #pragma unroll
@@ -41,26 +40,8 @@ __global__ __launch_bounds__(256) void moe_quant_kernel(const T* __restrict__ x,
   constexpr int CACHE = 4;
   __shared__ long long s_start[MOE_QUANT_MAX_EXPERTS + 1];
   __shared__ float red[4];
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid < 64) {                                            // exclusive scan of the counts, clamped to the rows there are
-    long long carry = 0;
-    for (int base = 0; base < E; base += 64) {
-      const int g = base + lane;
-      long long c = 0;
-      if (g < E) c = counts_i64 ? static_cast<long long>(static_cast<const int64_t*>(counts)[g]) : static_cast<long long>(static_cast<const int32_t*>(counts)[g]);
-      if (c < 0) c = 0;
-      long long incl = c;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const long long v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-      }
-      if (g < E) s_start[g] = min(carry + incl - c, static_cast<long long>(rows));
-      carry += __shfl(incl, 63);
-    }
-    if (lane == 0) s_start[E] = min(carry, static_cast<long long>(rows));
-  }
-  __syncthreads();
+  const int tid = threadIdx.x;
+  moe_scan_counts(counts, counts_i64, E, rows, s_start);           // (moe_row_expert.h)
   const int64_t live = s_start[E];
   const int n_vec = dim / VEC;
   const int64_t in_ld = GLU ? 2 * static_cast<int64_t>(dim) : dim;
@@ -76,11 +57,7 @@ __global__ __launch_bounds__(256) void moe_quant_kernel(const T* __restrict__ x,
       if (tid == 0) out_scale[row] = 1.0f;
       continue;
     }
-    int lo = 0, hi = E;                                      // largest e with s_start[e] <= row
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_start[mid] <= row) lo = mid; else hi = mid;
-    }
+    const int lo = moe_expert_of_row(s_start, E, row);       // largest e with s_start[e] <= row
     const T* x_row = x + row * in_ld;
     const float* sm_row = smooth + static_cast<int64_t>(lo) * dim;
     auto load_y = [&](int v, float (&f)[VEC]) {
