@@ -45,8 +45,10 @@ struct DequantSwigluQuantArgs {
 template <typename T> struct acc_elt { static __device__ __forceinline__ float to_f(T v) { return elt<T>::to_f(v); } };
 template <> struct acc_elt<int32_t> { static __device__ __forceinline__ float to_f(int32_t v) { return static_cast<float>(v); } };
 
-// The 16-bit wide forms are held to 168 VGPRs (three workgroups per CU instead of two; they take 171-173 left alone, and fit
-// without a spill); the 32-bit ones, whose loads are twice as many per output, would spill there and keep their 193.
+// The 16-bit wide forms are held to 168 VGPRs (three workgroups per CU instead of two) and take 159; the 32-bit ones, whose
+// loads are twice as many per output, take 153 uncapped.  The thread's place in the row is the plain threadIdx.x: hidden per
+// row (row_thread_per_row) the forms need 131 and 119 VGPRs, and the 16-bit one, whose cap fixes its occupancy either way,
+// measured 1-2 % slower for the offsets it recomputes (8192 x 14336 bf16, 8 groups: 181.2 us against 178.9).
 template <typename T, int VEC, int CACHE, bool NT>
 __global__ __launch_bounds__(256, (VEC > 1 && sizeof(T) == 2) ? 3 : 1) void dequant_swiglu_quant_kernel(DequantSwigluQuantArgs a) {
   typedef typename vec_of<T, VEC>::type VT;
@@ -63,12 +65,8 @@ __global__ __launch_bounds__(256, (VEC > 1 && sizeof(T) == 2) ? 3 : 1) void dequ
   const T* x = static_cast<const T*>(a.x);
   for (int64_t row = blockIdx.x; row < a.rows; row += gridDim.x) {
     unsigned char* q_row = reinterpret_cast<unsigned char*>(a.out_q) + row * H;
-    if (row >= live) {                                         // no expert owns the row
-      for (int v = tid; v < n_vec; v += 256) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) q_row[v * VEC + j] = 0;
-      }
-      if (tid == 0) a.out_scale[row] = 1.0f;
+    if (row >= live) {
+      moe_zero_unowned_row<VEC>(q_row, a.out_scale + row, n_vec);
       continue;
     }
     const int e = a.counts ? moe_expert_of_row(s_start, a.experts, row) : 0;
@@ -80,8 +78,7 @@ __global__ __launch_bounds__(256, (VEC > 1 && sizeof(T) == 2) ? 3 : 1) void dequ
     const float act = has_act ? a.act_scale[row] : 1.0f;
     const bool left_gate = a.activate_left != 0;
     auto load_z = [&](int v, float (&f)[VEC]) {                // z of vector v (v < n_vec)
-      const VT l = NT ? load_vec_nt<T, VEC>(x_row + v * VEC) : load_vec<T, VEC>(x_row + v * VEC);
-      const VT r = NT ? load_vec_nt<T, VEC>(x_row + H + v * VEC) : load_vec<T, VEC>(x_row + H + v * VEC);
+      const VT l = load_vec_as<T, VEC, NT>(x_row + v * VEC), r = load_vec_as<T, VEC, NT>(x_row + H + v * VEC);
       float wl[VEC], wr[VEC], sq[VEC];
       load_f32_vec<VEC>(ws, v, wl);
       load_f32_vec<VEC>(ws + H, v, wr);
@@ -110,36 +107,7 @@ __global__ __launch_bounds__(256, (VEC > 1 && sizeof(T) == 2) ? 3 : 1) void dequ
         f[j] = __fmul_rn(__fmul_rn(s, u), sq[j]);
       }
     };
-    float z[CACHE][VEC];
-    float amax = 0.f;
-#pragma unroll
-    for (int c = 0; c < CACHE; ++c) {
-      load_z(min(tid + c * 256, n_vec - 1), z[c]);             // (clamped, no branch around the loads: they go out together)
-      if (tid + c * 256 < n_vec) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(z[c][j]));
-      }
-    }
-    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
-      float f[VEC];
-      load_z(v, f);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(f[j]));
-    }
-    amax = block_max256(amax, red);
-    const float scale = __fdiv_rn(fmaxf(amax, 1e-12f), 127.f);
-    if (tid == 0) a.out_scale[row] = scale;
-    const float inv_scale = __fdiv_rn(1.0f, scale);
-#pragma unroll
-    for (int c = 0; c < CACHE; ++c) {
-      const int v = tid + c * 256;
-      if (v < n_vec) quantise_store<VEC, NT>(q_row + v * VEC, z[c], scale, inv_scale, -128.f, 127.f, 0);
-    }
-    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
-      float f[VEC];
-      load_z(v, f);
-      quantise_store<VEC, NT>(q_row + v * VEC, f, scale, inv_scale, -128.f, 127.f, 0);
-    }
+    row_quant<VEC, CACHE, 256, NT>(q_row, a.out_scale + row, tid, n_vec, load_z, -128.f, 127.f, 0, 0, red);
   }
 }
 
@@ -148,17 +116,14 @@ static int launch_dequant_swiglu_quant(const DequantSwigluQuantArgs& a, hipStrea
   constexpr int WIDE = 16 / sizeof(T);                       // outputs per 16-byte vector of x
   constexpr int RESIDENT = 56;                               // floats of z a thread keeps
   const int H = a.hidden;
-  const bool wide = H % WIDE == 0 && aligned_to(a.x, 16) && aligned_to(a.weight_scale, 16) && aligned_to(a.quant_scale, 16) &&
-                    (!a.bias || aligned_to(a.bias, 16)) && aligned_to(a.out_q, WIDE);
   const long long moved = a.rows * static_cast<long long>(H) * (2 * static_cast<long long>(sizeof(T)) + 1);
-  const bool nt = wide && stream_nt(moved);                  // (the scalar form has no non-temporal twin)
-  const unsigned blocks = static_cast<unsigned>(a.rows > 256 * 32 ? 256 * 32 : a.rows);
-  if (nt) hipLaunchKernelGGL((dequant_swiglu_quant_kernel<T, WIDE, RESIDENT / WIDE, true>), dim3(blocks), dim3(256), 0, s, a);
-  else if (wide) hipLaunchKernelGGL((dequant_swiglu_quant_kernel<T, WIDE, RESIDENT / WIDE, false>), dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((dequant_swiglu_quant_kernel<T, 1, 16, false>), dim3(blocks), dim3(256), 0, s, a);
+  const RowLaunch f = row_launch({{a.x, 16}, {a.weight_scale, 16}, {a.quant_scale, 16}, {a.bias, 16}, {a.out_q, WIDE}}, a.rows, H, WIDE,
+                                 moved, RESIDENT / WIDE * 256, 16 * 256);
+  if (f.nt) hipLaunchKernelGGL((dequant_swiglu_quant_kernel<T, WIDE, RESIDENT / WIDE, true>), dim3(f.blocks), dim3(256), 0, s, a);
+  else if (f.wide) hipLaunchKernelGGL((dequant_swiglu_quant_kernel<T, WIDE, RESIDENT / WIDE, false>), dim3(f.blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((dequant_swiglu_quant_kernel<T, 1, 16, false>), dim3(f.blocks), dim3(256), 0, s, a);
   MOJO_CHECK_LAUNCH("dequant_swiglu_quant");
-  const int resident_cols = wide ? RESIDENT * 256 : 16 * 256;
-  note_launch("dequant_swiglu_quant:%s:%s:%s", wide ? "wide" : "scalar", H <= resident_cols ? "resident" : "reread", nt ? "nt" : "cached");
+  note_launch("dequant_swiglu_quant:%s:%s:%s", f.width, f.fit, f.policy);
   return MOJO_OK;
 }
 

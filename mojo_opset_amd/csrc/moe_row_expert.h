@@ -1,7 +1,7 @@
 // The expert of a row, found on the device from the per-expert row counts: what moe_quant_kernel (quant_moe.hip) and
 // dequant_swiglu_quant_kernel (dequant_swiglu_quant.hip) share.  The rows arrive sorted by expert; every workgroup scans the
 // counts into LDS (one wave, 64 counts per step) and searches the scan per row — no prefix launch, no host synchronisation.
-// Negative counts read as zero; the scan is clamped to the rows there are.
+// Negative counts read as zero; the scan is clamped to the rows there are; the rows past it get zeros and scale 1.
 #pragma once
 #include "common.h"
 
@@ -43,6 +43,16 @@ __device__ __forceinline__ int moe_expert_of_row(const long long* s_start, int E
     if (s_start[mid] <= row) lo = mid; else hi = mid;
   }
   return lo;
+}
+
+// A row at or past s_start[E], which no expert owns: int8 zeros and scale 1.  Called by every thread of the workgroup.
+template <int VEC>
+__device__ __forceinline__ void moe_zero_unowned_row(unsigned char* q_row, float* out_scale, int n_vec) {
+  for (int v = threadIdx.x; v < n_vec; v += 256) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) q_row[v * VEC + j] = 0;
+  }
+  if (threadIdx.x == 0) *out_scale = 1.0f;
 }
 
 }  // namespace mojo

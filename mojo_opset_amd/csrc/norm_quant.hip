@@ -55,70 +55,25 @@ struct NormQuantArgs {
 // cost ~2 ns of workgroup turnover per row (32 768 rows x 2048: 70 us for 200 MB; x 128: 54 us for 13 MB).
 template <typename T, int VEC, int CACHE, bool NT = false /* stream_nt(): activations by-pass the caches */, int TPR = 256>
 __global__ __launch_bounds__(256) void norm_quant_kernel(NormQuantArgs a) {
-  typedef typename vec_of<T, VEC>::type V;
   __shared__ float red[4];
   const int n_vec = a.dim / VEC;
-  const int tid = threadIdx.x % TPR;
   constexpr int RPB = 256 / TPR;                     // rows per workgroup at a time
-  const T* hidden = static_cast<const T*>(a.hidden);
-  const T* residual = static_cast<const T*>(a.residual);
-  T* out_sum = static_cast<T*>(a.out_sum);
   unsigned char* out_q = static_cast<unsigned char*>(a.out_q);
 
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * RPB + threadIdx.x / TPR; row < a.rows; row += static_cast<int64_t>(gridDim.x) * RPB) {
-    const int64_t base = row * a.dim;
-    // y of element (v, j); `from_cache` rows only ever take the first branch
+    const int tid = row_thread_per_row<TPR>();       // (per row: the fp32 wide forms take 98-106 VGPRs with the offsets held, 5 -> 4 workgroups per CU)
+    const SummedRow<T, VEC, NT> x{static_cast<const T*>(a.hidden), static_cast<const T*>(a.residual), static_cast<T*>(a.out_sum), row * a.dim};
+    // ---- pass 1: the row into registers, its sum of squares -----------------------------------------------------------
     float y[CACHE][VEC];
+    x.template fill<CACHE, TPR>(y, tid, n_vec);
     float ss = 0.f;
-    auto load_sum = [&](int v, float (&f)[VEC]) {
-      V x = NT ? load_vec_nt<T, VEC>(hidden + base + v * VEC) : load_vec<T, VEC>(hidden + base + v * VEC);
-      if (residual) {
-        const V r = NT ? load_vec_nt<T, VEC>(residual + base + v * VEC) : load_vec<T, VEC>(residual + base + v * VEC);
 #pragma unroll
-        for (int j = 0; j < VEC; ++j)
-          vset<T, VEC>(x, j, elt<T>::from_f(elt<T>::to_f(vget<T, VEC>(x, j)) + elt<T>::to_f(vget<T, VEC>(r, j))));
-      }
+    for (int c = 0; c < CACHE; ++c)
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) f[j] = elt<T>::to_f(vget<T, VEC>(x, j));
-      return x;
-    };
-    // ---- pass 1: sums, sum of squares ---------------------------------------------------------------------------
-    // The cached vectors are loaded in batches — all of hidden, then (one wave-uniform branch) all of residual — with
-    // the index clamped instead of a branch per vector: a branch around each load made hipcc wait for every vector before
-    // requesting the next (one 16-byte load in flight per lane, four dependent round trips per row).
-    {
-      V xr[CACHE];
-#pragma unroll
-      for (int c = 0; c < CACHE; ++c) xr[c] = NT ? load_vec_nt<T, VEC>(hidden + base + min(tid + c * TPR, n_vec - 1) * VEC) : load_vec<T, VEC>(hidden + base + min(tid + c * TPR, n_vec - 1) * VEC);
-      if (residual) {
-        V rr[CACHE];
-#pragma unroll
-        for (int c = 0; c < CACHE; ++c) rr[c] = NT ? load_vec_nt<T, VEC>(residual + base + min(tid + c * TPR, n_vec - 1) * VEC) : load_vec<T, VEC>(residual + base + min(tid + c * TPR, n_vec - 1) * VEC);
-#pragma unroll
-        for (int c = 0; c < CACHE; ++c)
-#pragma unroll
-          for (int j = 0; j < VEC; ++j)
-            vset<T, VEC>(xr[c], j, elt<T>::from_f(elt<T>::to_f(vget<T, VEC>(xr[c], j)) + elt<T>::to_f(vget<T, VEC>(rr[c], j))));
-      }
-      if (out_sum) {
-#pragma unroll
-        for (int c = 0; c < CACHE; ++c)
-          if (tid + c * TPR < n_vec) { if (NT) store_vec_nt<T, VEC>(out_sum + base + (tid + c * TPR) * VEC, xr[c]); else store_vec<T, VEC>(out_sum + base + (tid + c * TPR) * VEC, xr[c]); }
-      }
-#pragma unroll
-      for (int c = 0; c < CACHE; ++c) {
-        const bool live = tid + c * TPR < n_vec;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          y[c][j] = live ? elt<T>::to_f(vget<T, VEC>(xr[c], j)) : 0.f;           // clamped duplicates count as zeros
-          ss = fmaf(y[c][j], y[c][j], ss);
-        }
-      }
-    }
+      for (int j = 0; j < VEC; ++j) ss = fmaf(y[c][j], y[c][j], ss);
     for (int v = tid + CACHE * TPR; v < n_vec; v += TPR) {
       float f[VEC];
-      const V x = load_sum(v, f);
-      if (out_sum) { if (NT) store_vec_nt<T, VEC>(out_sum + base + v * VEC, x); else store_vec<T, VEC>(out_sum + base + v * VEC, x); }
+      x.load(v, f, true);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) ss = fmaf(f[j], f[j], ss);
     }
@@ -128,148 +83,30 @@ __global__ __launch_bounds__(256) void norm_quant_kernel(NormQuantArgs a) {
       __syncthreads();
       rstd = rsqrtf(ss / static_cast<float>(a.dim) + a.eps);
     }
-    // y = ((f * rstd) * w) [* smooth]: single IEEE multiplies, the golden's order
-    auto load_f32 = [&](const float* p, int v, float (&dst)[VEC]) {        // VEC floats of a per-column vector
-      if constexpr (VEC % 4 == 0) {
-#pragma unroll
-        for (int q = 0; q < VEC / 4; ++q) {
-          const f32x4 t = *reinterpret_cast<const f32x4*>(p + v * VEC + 4 * q);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) dst[4 * q + e] = t[e];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) dst[j] = p[v * VEC + j];
-      }
-    };
-    auto finish = [&](int v, float (&f)[VEC]) {
+    // ---- pass 2: y = ((x * rstd) * w) [* smooth], single IEEE multiplies in the golden's order; the row maximum ---------
+    auto finish = [&](int v, float (&f)[VEC], bool store_normed) {
       if (a.weight) {
         float w[VEC];
-        load_f32(a.weight, v, w);
+        load_f32_vec<VEC>(a.weight, v, w);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) f[j] = __fmul_rn(__fmul_rn(f[j], rstd), w[j]);
-        if (a.out_normed) {
+        if (store_normed && a.out_normed) {
 #pragma unroll
-          for (int j = 0; j < VEC; ++j) a.out_normed[base + v * VEC + j] = f[j];
+          for (int j = 0; j < VEC; ++j) a.out_normed[x.base + v * VEC + j] = f[j];
         }
       }
       if (a.smooth) {
         float sm[VEC];
-        load_f32(a.smooth, v, sm);
+        load_f32_vec<VEC>(a.smooth, v, sm);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) f[j] = __fmul_rn(f[j], sm[j]);
       }
     };
-    // ---- pass 2: y, row maximum ----------------------------------------------------------------------------------
-    float amax = 0.f;
-    // cached part: the per-column vectors are fetched in batches too (clamped index, one uniform branch per tensor)
-    if (a.weight) {
-      float w[CACHE][VEC];
-#pragma unroll
-      for (int c = 0; c < CACHE; ++c) load_f32(a.weight, min(tid + c * TPR, n_vec - 1), w[c]);
-#pragma unroll
-      for (int c = 0; c < CACHE; ++c)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) y[c][j] = __fmul_rn(__fmul_rn(y[c][j], rstd), w[c][j]);
-      if (a.out_normed) {
-#pragma unroll
-        for (int c = 0; c < CACHE; ++c)
-          if (tid + c * TPR < n_vec) {
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) a.out_normed[base + (tid + c * TPR) * VEC + j] = y[c][j];
-          }
-      }
-    }
-    if (a.smooth) {
-      float sm[CACHE][VEC];
-#pragma unroll
-      for (int c = 0; c < CACHE; ++c) load_f32(a.smooth, min(tid + c * TPR, n_vec - 1), sm[c]);
-#pragma unroll
-      for (int c = 0; c < CACHE; ++c)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) y[c][j] = __fmul_rn(y[c][j], sm[c][j]);
-    }
-#pragma unroll
-    for (int c = 0; c < CACHE; ++c) {
-      if (tid + c * TPR < n_vec) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(y[c][j]));
-      }
-    }
-    for (int v = tid + CACHE * TPR; v < n_vec; v += TPR) {
-      float f[VEC];
-      load_sum(v, f);
-      finish(v, f);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(f[j]));
-    }
-    if constexpr (TPR == 256) {
-      amax = block_max256(amax, red);
-    } else {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    }
-    float scale = __fdiv_rn(fmaxf(amax, 1e-12f), a.q_max);
-    if (a.tiny_scale_is_one && scale < 1e-6f) scale = 1.0f;
-    if (tid == 0) a.out_scale[row] = scale;
-    const float inv_scale = __fdiv_rn(1.0f, scale);
-    // ---- pass 3: quantise ------------------------------------------------------------------------------------------
-    auto emit = [&](int v, const float (&f)[VEC]) {
-      // round_half_even(y / scale) as rint(y * (1 / scale)); the exact-division fallback is decided once per VECTOR (a
-      // divergent branch per element costs more vector instructions than the arithmetic it guards).  |t - rint(t)| <= 0.5
-      // always, so "within 1e-3 of a rounding boundary" is "its maximum over the vector > 0.499".
-      float rq[VEC];
-      float near = 0.f;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float t = f[j] * inv_scale;
-        rq[j] = rintf(t);
-        near = fmaxf(near, fabsf(t - rq[j]));
-      }
-      if (near > 0.499f) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) rq[j] = round_quotient(f[j], scale, inv_scale);
-      }
-      unsigned char q[VEC];
-      if (a.fp8) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) q[j] = to_fp8_e4m3(fminf(fmaxf(rq[j], a.q_min), a.q_max));
-      } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j)
-          q[j] = static_cast<unsigned char>(static_cast<signed char>(static_cast<int>(fminf(fmaxf(rq[j], a.q_min), a.q_max))));
-      }
-      unsigned char* dst = out_q + base + v * VEC;
-      if constexpr (VEC == 8) {
-        u32x2 w;
-        w[0] = q[0] | (q[1] << 8) | (q[2] << 16) | (static_cast<unsigned>(q[3]) << 24);
-        w[1] = q[4] | (q[5] << 8) | (q[6] << 16) | (static_cast<unsigned>(q[7]) << 24);
-        if (NT) __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(dst)); else *reinterpret_cast<u32x2*>(dst) = w;
-      } else if constexpr (VEC == 4) {
-        *reinterpret_cast<unsigned*>(dst) = q[0] | (q[1] << 8) | (q[2] << 16) | (static_cast<unsigned>(q[3]) << 24);
-      } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) dst[j] = q[j];
-      }
-    };
-#pragma unroll
-    for (int c = 0; c < CACHE; ++c) {
-      const int v = tid + c * TPR;
-      if (v < n_vec) emit(v, y[c]);
-    }
-    for (int v = tid + CACHE * TPR; v < n_vec; v += TPR) {
-      float f[VEC];
-      load_sum(v, f);
-      // (the stored normed tensor was written in pass 2; write it again is harmless but wasteful: skip it)
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        float t = f[j];
-        if (a.weight) t = __fmul_rn(__fmul_rn(t, rstd), a.weight[v * VEC + j]);
-        if (a.smooth) t = __fmul_rn(t, a.smooth[v * VEC + j]);
-        f[j] = t;
-      }
-      emit(v, f);
-    }
+    const float amax = row_absmax<VEC, CACHE, TPR>(y, tid, n_vec, finish, [&](int v, float (&f)[VEC]) { x.load(v, f); finish(v, f, true); }, red);
+    // ---- pass 3: quantise (the tail's normed tensor was stored in pass 2) ---------------------------------------------
+    row_quantise<VEC, CACHE, TPR, NT>(out_q + x.base, a.out_scale + row, y, tid, n_vec,
+                                      [&](int v, float (&f)[VEC]) { x.load(v, f); finish(v, f, false); }, amax, a.q_min, a.q_max,
+                                      a.fp8, a.tiny_scale_is_one);
   }
 }
 
@@ -290,70 +127,30 @@ struct LayerNormQuantArgs {
 
 // LayerNorm + quant: a row per 256-thread workgroup, the row's (summed) x in registers from the first load to the quantised
 // store; rows of more than CACHE * 256 vectors re-read (and re-add) what does not fit.  The wide forms are held to 128 VGPRs
-// (four workgroups per CU, norm_quant_kernel's occupancy): left alone hipcc hoists the weight, bias and smooth loads of all
-// four cached vectors at once and takes 136-143 (three workgroups), with no spill either way.
+// (four workgroups per CU).  With the thread's place in the row taken per row they need 60 (fp32) to 99 (bf16) and the cap
+// does not bind; with the per-slot offsets held across the loop of rows they sit at the cap and spill 4 to 12 VGPRs, which
+// is why this kernel takes the place per row.
 template <typename T, int VEC, int CACHE, bool NT>
 __global__ __launch_bounds__(256, VEC > 1 ? 4 : 1) void layernorm_quant_kernel(LayerNormQuantArgs a) {
-  typedef typename vec_of<T, VEC>::type V;
   __shared__ float red[4];
   const int n_vec = a.dim / VEC;
-  const int tid = threadIdx.x;
-  const T* hidden = static_cast<const T*>(a.hidden);
-  const T* residual = static_cast<const T*>(a.residual);
-  T* out_sum = static_cast<T*>(a.out_sum);
   unsigned char* out_q = static_cast<unsigned char*>(a.out_q);
   const float dim_f = static_cast<float>(a.dim);
 
   for (int64_t row = blockIdx.x; row < a.rows; row += gridDim.x) {
-    const int64_t base = row * a.dim;
-    auto load_sum = [&](int v, float (&f)[VEC]) {              // x of vector v (hidden + residual rounded to T), as floats
-      V x = NT ? load_vec_nt<T, VEC>(hidden + base + v * VEC) : load_vec<T, VEC>(hidden + base + v * VEC);
-      if (residual) {
-        const V r = NT ? load_vec_nt<T, VEC>(residual + base + v * VEC) : load_vec<T, VEC>(residual + base + v * VEC);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j)
-          vset<T, VEC>(x, j, elt<T>::from_f(elt<T>::to_f(vget<T, VEC>(x, j)) + elt<T>::to_f(vget<T, VEC>(r, j))));
-      }
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) f[j] = elt<T>::to_f(vget<T, VEC>(x, j));
-      return x;
-    };
+    const int tid = row_thread_per_row<256>();               // (the comment above)
+    const SummedRow<T, VEC, NT> x{static_cast<const T*>(a.hidden), static_cast<const T*>(a.residual), static_cast<T*>(a.out_sum), row * a.dim};
     // ---- pass 1: the row into registers, its sum ------------------------------------------------------------------------
     float y[CACHE][VEC];
+    x.template fill<CACHE, 256>(y, tid, n_vec);
     float sum = 0.f;
-    {
-      V xr[CACHE];                                             // batched loads, clamped index (norm_quant_kernel, pass 1)
 #pragma unroll
-      for (int c = 0; c < CACHE; ++c) xr[c] = NT ? load_vec_nt<T, VEC>(hidden + base + min(tid + c * 256, n_vec - 1) * VEC) : load_vec<T, VEC>(hidden + base + min(tid + c * 256, n_vec - 1) * VEC);
-      if (residual) {
-        V rr[CACHE];
+    for (int c = 0; c < CACHE; ++c)
 #pragma unroll
-        for (int c = 0; c < CACHE; ++c) rr[c] = NT ? load_vec_nt<T, VEC>(residual + base + min(tid + c * 256, n_vec - 1) * VEC) : load_vec<T, VEC>(residual + base + min(tid + c * 256, n_vec - 1) * VEC);
-#pragma unroll
-        for (int c = 0; c < CACHE; ++c)
-#pragma unroll
-          for (int j = 0; j < VEC; ++j)
-            vset<T, VEC>(xr[c], j, elt<T>::from_f(elt<T>::to_f(vget<T, VEC>(xr[c], j)) + elt<T>::to_f(vget<T, VEC>(rr[c], j))));
-      }
-      if (out_sum) {
-#pragma unroll
-        for (int c = 0; c < CACHE; ++c)
-          if (tid + c * 256 < n_vec) { if (NT) store_vec_nt<T, VEC>(out_sum + base + (tid + c * 256) * VEC, xr[c]); else store_vec<T, VEC>(out_sum + base + (tid + c * 256) * VEC, xr[c]); }
-      }
-#pragma unroll
-      for (int c = 0; c < CACHE; ++c) {
-        const bool live = tid + c * 256 < n_vec;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          y[c][j] = live ? elt<T>::to_f(vget<T, VEC>(xr[c], j)) : 0.f;
-          sum += y[c][j];
-        }
-      }
-    }
+      for (int j = 0; j < VEC; ++j) sum += y[c][j];
     for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
       float f[VEC];
-      const V x = load_sum(v, f);
-      if (out_sum) { if (NT) store_vec_nt<T, VEC>(out_sum + base + v * VEC, x); else store_vec<T, VEC>(out_sum + base + v * VEC, x); }
+      x.load(v, f, true);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) sum += f[j];
     }
@@ -374,7 +171,7 @@ __global__ __launch_bounds__(256, VEC > 1 ? 4 : 1) void layernorm_quant_kernel(L
     }
     for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
       float f[VEC];
-      load_sum(v, f);
+      x.load(v, f);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         const float d = __fsub_rn(f[j], mean);
@@ -384,7 +181,7 @@ __global__ __launch_bounds__(256, VEC > 1 ? 4 : 1) void layernorm_quant_kernel(L
     ss = block_sum<4>(ss, red);
     __syncthreads();
     const float rstd = __fdiv_rn(1.0f, sqrtf(__fadd_rn(__fdiv_rn(ss, dim_f), a.eps)));
-    // ---- pass 3: y, row maximum ------------------------------------------------------------------------------------------
+    // ---- pass 3: y, row maximum; pass 4: quantise -------------------------------------------------------------------------
     auto finish = [&](int v, float (&f)[VEC]) {                // x -> y of vector v (v < n_vec)
 #pragma unroll
       for (int j = 0; j < VEC; ++j) f[j] = __fmul_rn(__fsub_rn(f[j], mean), rstd);
@@ -402,86 +199,52 @@ __global__ __launch_bounds__(256, VEC > 1 ? 4 : 1) void layernorm_quant_kernel(L
         for (int j = 0; j < VEC; ++j) f[j] = __fmul_rn(f[j], sm[j]);
       }
     };
-    float amax = 0.f;
-#pragma unroll
-    for (int c = 0; c < CACHE; ++c) {
-      finish(min(tid + c * 256, n_vec - 1), y[c]);             // (clamped: no branch around the loads; dead slots are unused)
-      if (tid + c * 256 < n_vec) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(y[c][j]));
-      }
-    }
-    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
-      float f[VEC];
-      load_sum(v, f);
-      finish(v, f);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) amax = fmaxf(amax, fabsf(f[j]));
-    }
-    amax = block_max256(amax, red);
-    const float scale = __fdiv_rn(fmaxf(amax, 1e-12f), a.q_max);
-    if (tid == 0) a.out_scale[row] = scale;
-    const float inv_scale = __fdiv_rn(1.0f, scale);
-    // ---- pass 4: quantise -------------------------------------------------------------------------------------------------
-#pragma unroll
-    for (int c = 0; c < CACHE; ++c) {
-      const int v = tid + c * 256;
-      if (v < n_vec) quantise_store<VEC, NT>(out_q + base + v * VEC, y[c], scale, inv_scale, a.q_min, a.q_max, a.fp8);
-    }
-    for (int v = tid + CACHE * 256; v < n_vec; v += 256) {
-      float f[VEC];
-      load_sum(v, f);
-      finish(v, f);
-      quantise_store<VEC, NT>(out_q + base + v * VEC, f, scale, inv_scale, a.q_min, a.q_max, a.fp8);
-    }
+    auto y_of = [&](int v, float (&f)[VEC]) { x.load(v, f); finish(v, f); };
+    const float amax = row_absmax<VEC, CACHE, 256>(y, tid, n_vec, [&](int v, float (&f)[VEC], bool) { finish(v, f); }, y_of, red);
+    row_quantise<VEC, CACHE, 256, NT>(out_q + x.base, a.out_scale + row, y, tid, n_vec, y_of, amax, a.q_min, a.q_max, a.fp8, 0);
   }
+}
+
+// The launch form of both kernels: 4 vectors of 16 bytes per thread in registers, or 8 single elements.  `bias`: LayerNorm's.
+template <typename T, typename Args>
+static RowLaunch norm_row_launch(const Args& a, const float* bias = nullptr) {
+  constexpr int WIDE = 16 / sizeof(T);
+  const long long moved = a.rows * static_cast<long long>(a.dim) * (static_cast<long long>(sizeof(T)) * (1 + (a.residual ? 1 : 0) + (a.out_sum ? 1 : 0)) + 1);
+  return row_launch({{a.hidden, 16}, {a.residual, 16}, {a.out_sum, 16}, {a.out_q, WIDE}, {a.weight, 16}, {bias, 16}, {a.smooth, 16}},
+                    a.rows, a.dim, WIDE, moved, 4 * 256, 8 * 256);
 }
 
 template <typename T>
 static int launch_layernorm_quant(const LayerNormQuantArgs& a, hipStream_t s) {
   constexpr int WIDE = 16 / sizeof(T);
-  const size_t al = WIDE * sizeof(T);
-  const bool wide = a.dim % WIDE == 0 && aligned_to(a.hidden, al) && (!a.residual || aligned_to(a.residual, al)) &&
-                    (!a.out_sum || aligned_to(a.out_sum, al)) && aligned_to(a.out_q, WIDE) &&
-                    (!a.weight || (aligned_to(a.weight, 16) && aligned_to(a.bias, 16))) && (!a.smooth || aligned_to(a.smooth, 16));
-  const unsigned blocks = static_cast<unsigned>(a.rows > 256 * 32 ? 256 * 32 : a.rows);
-  const long long moved = a.rows * static_cast<long long>(a.dim) * (static_cast<long long>(sizeof(T)) * (1 + (a.residual ? 1 : 0) + (a.out_sum ? 1 : 0)) + 1);
-  const bool nt = wide && stream_nt(moved);             // (the scalar form has no non-temporal twin)
-  if (nt) hipLaunchKernelGGL((layernorm_quant_kernel<T, WIDE, 4, true>), dim3(blocks), dim3(256), 0, s, a);
-  else if (wide) hipLaunchKernelGGL((layernorm_quant_kernel<T, WIDE, 4, false>), dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((layernorm_quant_kernel<T, 1, 8, false>), dim3(blocks), dim3(256), 0, s, a);
+  const RowLaunch f = norm_row_launch<T>(a, a.bias);
+  if (f.nt) hipLaunchKernelGGL((layernorm_quant_kernel<T, WIDE, 4, true>), dim3(f.blocks), dim3(256), 0, s, a);
+  else if (f.wide) hipLaunchKernelGGL((layernorm_quant_kernel<T, WIDE, 4, false>), dim3(f.blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((layernorm_quant_kernel<T, 1, 8, false>), dim3(f.blocks), dim3(256), 0, s, a);
   MOJO_CHECK_LAUNCH("layernorm_quant");
-  const int cached_vecs = wide ? 4 * 256 : 8 * 256;
-  note_launch("layernorm_quant:%s:%s:%s", wide ? "wide" : "scalar", a.dim / (wide ? WIDE : 1) <= cached_vecs ? "resident" : "reread",
-              nt ? "nt" : "cached");
+  note_launch("layernorm_quant:%s:%s:%s", f.width, f.fit, f.policy);
   return MOJO_OK;
 }
 
 template <typename T>
 static int launch_norm_quant(const NormQuantArgs& a, hipStream_t s, const char* op) {
   constexpr int WIDE = 16 / sizeof(T);
-  const size_t al = WIDE * sizeof(T);
-  const bool wide = a.dim % WIDE == 0 && aligned_to(a.hidden, al) && (!a.residual || aligned_to(a.residual, al)) &&
-                    (!a.out_sum || aligned_to(a.out_sum, al)) && aligned_to(a.out_q, WIDE) &&
-                    (!a.weight || aligned_to(a.weight, 16)) && (!a.smooth || aligned_to(a.smooth, 16));
-  int64_t blocks = a.rows > 256 * 32 ? 256 * 32 : a.rows;
-  const long long moved = a.rows * static_cast<long long>(a.dim) * (static_cast<long long>(sizeof(T)) * (1 + (a.residual ? 1 : 0) + (a.out_sum ? 1 : 0)) + 1);
-  const bool nt = wide && stream_nt(moved);             // (the scalar form has no non-temporal twin)
+  const RowLaunch f = norm_row_launch<T>(a);
   // a row per wave: dynamic quant (no normalisation: no sum of squares) of many rows that fit one wave's registers
-  if (wide && !a.weight && a.dim / WIDE <= 4 * 64 && a.rows >= 2048) {
-    blocks = ceil_div(a.rows, 4);
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true, 64>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, false, 64>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+  if (f.wide && !a.weight && a.dim / WIDE <= 4 * 64 && a.rows >= 2048) {
+    const int64_t groups = ceil_div(a.rows, 4);
+    const unsigned blocks = static_cast<unsigned>(groups > 256 * 32 ? 256 * 32 : groups);
+    if (f.nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true, 64>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, false, 64>), dim3(blocks), dim3(256), 0, s, a);
     MOJO_CHECK_LAUNCH("norm_quant");
-    note_launch("%s:wide:tpr64:%s", op, nt ? "nt" : "cached");
+    note_launch("%s:wide:tpr64:%s", op, f.policy);
     return MOJO_OK;
   }
-  if (nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
-  else if (wide) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((norm_quant_kernel<T, 1, 8>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+  if (f.nt) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4, true>), dim3(f.blocks), dim3(256), 0, s, a);
+  else if (f.wide) hipLaunchKernelGGL((norm_quant_kernel<T, WIDE, 4>), dim3(f.blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((norm_quant_kernel<T, 1, 8>), dim3(f.blocks), dim3(256), 0, s, a);
   MOJO_CHECK_LAUNCH("norm_quant");
-  note_launch("%s:%s:tpr256:%s", op, wide ? "wide" : "scalar", nt ? "nt" : "cached");
+  note_launch("%s:%s:tpr256:%s", op, f.width, f.policy);
   return MOJO_OK;
 }
 
@@ -495,6 +258,20 @@ static int dispatch_norm_quant(const NormQuantArgs& a, int dtype, hipStream_t s,
   }
 }
 
+// The shape and quantised-dtype checks of every entry point, and the fields of its arguments that follow from them.
+template <typename Args>
+static int set_shape_and_range(Args& a, const char* op, int64_t rows, int64_t dim, int quant_dtype, float q_min, float eps) {
+  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "%s: bad shape rows=%lld dim=%lld", op, (long long)rows,
+               (long long)dim);
+  MOJO_REQUIRE(quant_dtype == MOJO_I8 || quant_dtype == MOJO_F8E4M3, MOJO_EUNSUPPORTED,
+               "%s: quant dtype %d (int8 / fp8-e4m3 only)", op, quant_dtype);
+  a.rows = rows; a.dim = static_cast<int>(dim);
+  a.eps = eps; a.fp8 = quant_dtype == MOJO_F8E4M3;
+  a.q_max = a.fp8 ? 448.f : 127.f;
+  a.q_min = q_min;
+  return MOJO_OK;
+}
+
 }  // namespace mojo
 
 using namespace mojo;
@@ -503,12 +280,10 @@ extern "C" int mojo_hip_dynamic_quant(const void* input, const float* inv_smooth
                                       int64_t rows, int64_t dim, int dtype, mojo_stream_t stream) {
   if (rows == 0) return MOJO_OK;
   MOJO_REQUIRE(input && out_q && out_scale, MOJO_EINVAL, "dynamic_quant: null pointer");
-  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "dynamic_quant: bad shape rows=%lld dim=%lld",
-               (long long)rows, (long long)dim);
   NormQuantArgs a{};
   a.hidden = input; a.smooth = inv_smooth_scale; a.out_q = out_q; a.out_scale = out_scale;
-  a.rows = rows; a.dim = static_cast<int>(dim);
-  a.eps = 0.f; a.q_max = 127.f; a.q_min = -128.f; a.fp8 = 0; a.tiny_scale_is_one = 1;
+  a.tiny_scale_is_one = 1;
+  if (const int rc = set_shape_and_range(a, "dynamic_quant", rows, dim, MOJO_I8, -128.f, 0.f)) return rc;
   return dispatch_norm_quant(a, dtype, static_cast<hipStream_t>(stream));
 }
 
@@ -519,18 +294,10 @@ extern "C" int mojo_hip_residual_add_rmsnorm_quant(const void* hidden, const voi
                                                    mojo_stream_t stream) {
   if (rows == 0) return MOJO_OK;
   MOJO_REQUIRE(hidden && weight && out_q && out_scale, MOJO_EINVAL, "rmsnorm_quant: null pointer");
-  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "rmsnorm_quant: bad shape rows=%lld dim=%lld",
-               (long long)rows, (long long)dim);
-  MOJO_REQUIRE(quant_dtype == MOJO_I8 || quant_dtype == MOJO_F8E4M3, MOJO_EUNSUPPORTED,
-               "rmsnorm_quant: quant dtype %d (int8 / fp8-e4m3 only)", quant_dtype);
   NormQuantArgs a{};
   a.hidden = hidden; a.residual = residual; a.weight = weight; a.smooth = smooth_scale;
   a.out_q = out_q; a.out_sum = out_sum; a.out_normed = out_normed; a.out_scale = out_scale;
-  a.rows = rows; a.dim = static_cast<int>(dim);
-  a.eps = eps; a.fp8 = quant_dtype == MOJO_F8E4M3;
-  a.q_max = a.fp8 ? 448.f : 127.f;
-  a.q_min = q_min;
-  a.tiny_scale_is_one = 0;
+  if (const int rc = set_shape_and_range(a, "rmsnorm_quant", rows, dim, quant_dtype, q_min, eps)) return rc;
   return dispatch_norm_quant(a, dtype, static_cast<hipStream_t>(stream));
 }
 
@@ -539,17 +306,9 @@ extern "C" int mojo_hip_rmsnorm_quant(const void* hidden, const float* weight, c
                                       float eps, mojo_stream_t stream) {
   if (rows == 0) return MOJO_OK;
   MOJO_REQUIRE(hidden && weight && out_q && out_scale, MOJO_EINVAL, "rmsnorm_quant: null pointer");
-  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "rmsnorm_quant: bad shape rows=%lld dim=%lld",
-               (long long)rows, (long long)dim);
-  MOJO_REQUIRE(quant_dtype == MOJO_I8 || quant_dtype == MOJO_F8E4M3, MOJO_EUNSUPPORTED,
-               "rmsnorm_quant: quant dtype %d (int8 / fp8-e4m3 only)", quant_dtype);
   NormQuantArgs a{};
   a.hidden = hidden; a.weight = weight; a.smooth = smooth_scale; a.out_q = out_q; a.out_scale = out_scale;
-  a.rows = rows; a.dim = static_cast<int>(dim);
-  a.eps = eps; a.fp8 = quant_dtype == MOJO_F8E4M3;
-  a.q_max = a.fp8 ? 448.f : 127.f;
-  a.q_min = q_min;
-  a.tiny_scale_is_one = 0;
+  if (const int rc = set_shape_and_range(a, "rmsnorm_quant", rows, dim, quant_dtype, q_min, eps)) return rc;
   return dispatch_norm_quant(a, dtype, static_cast<hipStream_t>(stream), "rmsnorm_quant");
 }
 
@@ -559,17 +318,10 @@ extern "C" int mojo_hip_layernorm_quant(const void* hidden, const void* residual
   if (rows == 0) return MOJO_OK;
   MOJO_REQUIRE(hidden && out_q && out_scale, MOJO_EINVAL, "layernorm_quant: null pointer");
   MOJO_REQUIRE((weight == nullptr) == (bias == nullptr), MOJO_EINVAL, "layernorm_quant: weight and bias come together or not at all");
-  MOJO_REQUIRE(rows > 0 && dim > 0 && dim < (1LL << 30), MOJO_EINVAL, "layernorm_quant: bad shape rows=%lld dim=%lld",
-               (long long)rows, (long long)dim);
-  MOJO_REQUIRE(quant_dtype == MOJO_I8 || quant_dtype == MOJO_F8E4M3, MOJO_EUNSUPPORTED,
-               "layernorm_quant: quant dtype %d (int8 / fp8-e4m3 only)", quant_dtype);
   LayerNormQuantArgs a{};
   a.hidden = hidden; a.residual = residual; a.weight = weight; a.bias = bias; a.smooth = smooth_scale;
   a.out_q = out_q; a.out_sum = out_sum; a.out_scale = out_scale;
-  a.rows = rows; a.dim = static_cast<int>(dim);
-  a.eps = eps; a.fp8 = quant_dtype == MOJO_F8E4M3;
-  a.q_max = a.fp8 ? 448.f : 127.f;
-  a.q_min = q_min;
+  if (const int rc = set_shape_and_range(a, "layernorm_quant", rows, dim, quant_dtype, q_min, eps)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (dtype) {
     case MOJO_F32: return launch_layernorm_quant<float>(a, s);

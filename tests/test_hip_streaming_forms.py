@@ -337,26 +337,78 @@ def test_dynamic_quant_rounding_boundaries_bit_exact(form, dtype):
     assert_tiny_rows_straddle(want_scale)
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("dim,form", [(1024, "vec16"), (1001, "scalar")])
-def test_moe_dynamic_quant_rounding_boundaries_bit_exact(dim, form, dtype):
-    """MojoMoEDynamicQuant divides; the boundary rows guard against the shortcut arriving there without its fallback."""
-    experts = 3
+def moe_boundary_rows(dim, dtype, experts=3):
+    """(y, inv, counts) of the MoE boundary tests: `boundary_rows` of ``dim`` columns as the smoothed values, power-of-two
+    smooth scales per expert and column (so y / inv and back is exact), the rows split over the first and the last expert."""
     y = boundary_rows(boundary_row_count(dim), dim, dtype, seed=dim)
     assert_boundary_input(y.float())
     g = torch.Generator().manual_seed(dim)
     inv = torch.tensor([1.0, 0.5, 0.25])[torch.randint(3, (experts, dim), generator=g)]
     counts = torch.tensor([y.shape[0] // 2, 0, y.shape[0] - y.shape[0] // 2], dtype=torch.int32)
-    x = (y.float() / inv.repeat_interleave(counts, dim=0)).to(dtype)
-    assert torch.equal(x.float() * inv.repeat_interleave(counts, dim=0), y.float())
-    ref = torch_cls("MojoMoEDynamicQuant")(experts, dim)
+    return y, inv, counts
+
+
+def check_moe_plain_boundaries(dim, form, dtype):
+    """MojoMoEDynamicQuant on `moe_boundary_rows`: the launch tag, and scale and bytes equal to the golden's."""
+    y, inv, counts = moe_boundary_rows(dim, dtype)
+    smooth_rows = inv.repeat_interleave(counts, dim=0)
+    x = (y.float() / smooth_rows).to(dtype)
+    assert torch.equal(x.float() * smooth_rows, y.float())
+    ref = torch_cls("MojoMoEDynamicQuant")(len(counts), dim)
     with torch.no_grad():
         ref.inv_smooth_scale.copy_(inv)
         want_q, want_scale = ref(x, counts)
-    op = hip_cls("MojoMoEDynamicQuant")(experts, dim).to(DEV)
+    op = hip_cls("MojoMoEDynamicQuant")(len(counts), dim).to(DEV)
     op.load_state_dict(ref.state_dict())
     q, scale = to_cpu(op(x.to(DEV), counts.to(DEV)))
     assert last_launch() == "moe_quant:plain:" + form, last_launch()
+    assert torch.equal(scale, want_scale) and torch.equal(q, want_q)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dim,form", [(1024, "vec16"), (1001, "scalar")])
+def test_moe_dynamic_quant_rounding_boundaries_bit_exact(dim, form, dtype):
+    """MojoMoEDynamicQuant takes the reciprocal shortcut; the boundary rows hold it to its exact-division fallback."""
+    check_moe_plain_boundaries(dim, form, dtype)
+
+
+# (dim for bf16 and fp16, dim for fp32, form): 1025 vectors, one past the 4 x 256 a workgroup keeps; 7 columns past the 1024
+MOE_REREAD = [(8200, 4100, "vec16"), (1031, 1031, "scalar")]
+# the glu form on the resident rows too
+MOE_GLU = MOE_REREAD + [(1024, 1024, "vec16"), (1001, 1001, "scalar")]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dim16,dim32,form", MOE_REREAD)
+def test_moe_dynamic_quant_reread_tail_rounding_boundaries_bit_exact(dim16, dim32, form, dtype):
+    """The boundary rows in rows longer than the register cache: the vectors past it are recomputed and quantised by the
+    tail loop, whose shortcut needs its fallback like the cached part's."""
+    check_moe_plain_boundaries(dim32 if dtype == F32 else dim16, form, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dim16,dim32,form", MOE_GLU)
+def test_moe_swiglu_quant_rounding_boundaries_bit_exact(dim16, dim32, form, dtype):
+    """The glu form on the same quotients: gate = 32, where silu is the identity in fp32 (expf(-32) is below half an ulp of
+    1, so 32 / (1 + expf(-32)) = 32), up = y / inv and the op's smooth scale inv / 32, all powers of two apart: silu(gate) *
+    up * (inv / 32) = y with no rounding anywhere, which the test asserts before it compares."""
+    from mojo_opset_amd.backends.hip.operators.quantize import moe_dynamic_quant
+    dim = dim32 if dtype == F32 else dim16
+    y, inv, counts = moe_boundary_rows(dim, dtype)
+    smooth = inv / 32
+    smooth_rows = smooth.repeat_interleave(counts, dim=0)
+    gate = torch.full(y.shape, 32.0).to(dtype)
+    up = (y.float() / inv.repeat_interleave(counts, dim=0)).to(dtype)
+    activated = torch.nn.functional.silu(gate.float()) * up.float()
+    assert torch.equal(activated * smooth_rows, y.float())
+    ref = torch_cls("MojoMoEDynamicQuant")(len(counts), dim)
+    with torch.no_grad():
+        ref.inv_smooth_scale.copy_(smooth)
+        want_q, want_scale = ref(activated, counts)
+    x = torch.cat([gate, up], dim=-1).contiguous()
+    q, scale = to_cpu(moe_dynamic_quant(x.to(DEV), smooth.to(DEV), counts.to(DEV), dim, True, "test"))
+    assert last_launch() == "moe_quant:swiglu:" + form, last_launch()
+    assert_tiny_rows_straddle(want_scale)
     assert torch.equal(scale, want_scale) and torch.equal(q, want_q)
 
 
