@@ -288,6 +288,11 @@ def _decode_decompressed(op, query, ckv_cache, kpe_cache, total_seq_lens, block_
     batch = query.shape[0]
     dev = query.device
     lens = total_seq_lens.to(torch.int32).clamp(min=0)          # (out of place: `.to` returns the caller's tensor when it is int32 already)
+    if block_tables.shape[1] > 0:
+        # the golden's `_mla_unpage` stops at the first negative page id and drops the tail (the un-page kernel would read page 0
+        # there): cut every sequence at that page, on the device (the leading non-negative ids, counted without a sync)
+        whole_pages = (torch.cumsum(block_tables < 0, dim=1) == 0).sum(dim=1, dtype=torch.int32)
+        lens = torch.minimum(lens, whole_pages * ckv_cache.shape[2])
     cu_kv = torch.zeros(batch + 1, dtype=torch.int32, device=dev)
     torch.cumsum(lens, 0, out=cu_kv[1:])
     cu_q = torch.arange(batch + 1, dtype=torch.int32, device=dev)
