@@ -385,6 +385,27 @@ int mojo_hip_swa_packed(const void* query, const void* key, const void* value, c
                         int64_t max_kv_len_hint, float softmax_scale, int layout_abab, int dtype, void* workspace,
                         int64_t workspace_bytes, int64_t local_window, int64_t global_window, mojo_stream_t stream);
 
+/* ---- MojoSdpa (core/operators/attention.py:456-504): bidirectional scaled-dot-product attention, query [batch][q_heads]
+ *      [q_len][head_dim] against key / value [batch][kv_heads][kv_len][head_dim], every row seeing every key; kv_len < q_len is
+ *      legal (cross-attention).  All four tensors are addressed by batch / head / token strides in elements (64-bit offsets,
+ *      non-negative multiples of 8; head_dim dense; bases 16-byte aligned); key and value share theirs.  q head h reads kv head
+ *      h / (q_heads / kv_heads) (the grouping of repeat_interleave).  mask_kind 0: no mask (mask = NULL).  1: boolean mask, one
+ *      byte per score, 0 hides the key.  2 / 3: a bias in the query's dtype / fp32, added to the scaled score (-inf allowed).
+ *      The mask is read in place as [batch][q_heads][q_len][kv_len] through its strides in elements; any of them may be 0
+ *      (a broadcast dimension), the last dimension is dense, and one (batch, head) plane stays below 2^31 elements.  A row
+ *      with no visible key stores zeros.  bf16 / fp16, head_dim 64 / 96 / 128, q_heads / kv_heads 1 / 2 / 4 / 8, lengths
+ *      below 2^30.  The kernel is the prefill's (mojo_hip_swa_packed) without its diagonal; workspace and key split as there,
+ *      sized on kv_len.  kv_len must be positive.  No host sync.                                                            */
+int64_t mojo_hip_sdpa_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len, int64_t kv_len,
+                                      int64_t head_dim);
+int mojo_hip_sdpa(const void* query, const void* key, const void* value, const void* mask, void* out, int64_t batch,
+                  int64_t q_heads, int64_t kv_heads, int64_t q_len, int64_t kv_len, int64_t head_dim,
+                  int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t out_batch_stride,
+                  int64_t out_head_stride, int64_t out_token_stride, int64_t kv_batch_stride, int64_t kv_head_stride,
+                  int64_t kv_token_stride, int mask_kind, int64_t mask_batch_stride, int64_t mask_head_stride,
+                  int64_t mask_row_stride, float softmax_scale, int dtype, void* workspace, int64_t workspace_bytes,
+                  mojo_stream_t stream);
+
 /* ---- MojoPagedDecodeNstepSWA (experimental/operators/attention.py:1154-1262): `steps` query rows per sequence (draft
  *      verification, multi-token prediction) in one pass over the paged cache.  The arguments of mojo_hip_paged_decode_swa
  *      plus `steps`; query and out are [batch][steps][q_heads][head_dim] dense, total_seq_lens counts the `steps` new tokens.

@@ -11,17 +11,18 @@ registers both into the reference.  The torch golden of every op, in ``__all__``
 package.  ``NSTEP_OPS`` (n-step paged decode) is a further set of package attributes the plugin registers; its torch golden
 is ``tests/nstep_golden.py``.  ``NSTEP_KV_INT8_OPS`` (the same over the int8 cache) is one more such set; its golden is
 ``tests/nstep_kv_int8_golden.py``.  ``PACKED_ATTN_OPS`` (`MojoSWA`: packed var-len attention over contiguous K/V) is another;
-its golden is ``tests/swa_packed_golden.py``.  ``QUANT_DENSE_OPS`` (the activation ops between the GEMMs of a dense W8A8 layer:
+its golden is ``tests/swa_packed_golden.py``.  ``FULL_ATTN_OPS`` (`MojoSdpa`: bidirectional attention with an optional mask) is
+another; its golden is ``tests/sdpa_golden.py``.  ``QUANT_DENSE_OPS`` (the activation ops between the GEMMs of a dense W8A8 layer:
 norm + quant, static quant, dequant, dequant -> SwiGLU -> quant) is one more; its golden is ``tests/quant_dense_golden.py``.
 """
 from .core import *  # noqa: F401,F403
 from .core import __all__ as _core_all
 from .core import (BEYOND_SURVEY_OPS, EXTENDED_OPS, KV_INT8_OPS, KV_INT8_SWA_OPS, NSTEP_KV_INT8_OPS, NSTEP_OPS,  # noqa: F401
-                   PACKED_ATTN_OPS, QUANT_DENSE_OPS, QUANT_MOE_OPS, SAMPLING_OPS)
+                   FULL_ATTN_OPS, PACKED_ATTN_OPS, QUANT_DENSE_OPS, QUANT_MOE_OPS, SAMPLING_OPS)
 from . import core as _core
 from . import backends  # noqa: F401  (registers HIP<Op> classes)
 from .paged_cache import PagedDummyCache  # noqa: E402  device-side block allocator (SURVEY §8 f4)
 
 __all__ = list(_core_all) + ["PagedDummyCache"]
-globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS + NSTEP_OPS + NSTEP_KV_INT8_OPS + PACKED_ATTN_OPS + QUANT_DENSE_OPS})   # beyond §8: not in __all__
+globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS + NSTEP_OPS + NSTEP_KV_INT8_OPS + PACKED_ATTN_OPS + FULL_ATTN_OPS + QUANT_DENSE_OPS})   # beyond §8: not in __all__
 __version__ = "0.1.0"

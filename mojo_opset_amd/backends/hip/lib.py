@@ -71,6 +71,8 @@ SIGNATURES = {
                                            c_float, c_int, c_int, _P, _I, _I, _I, _P]),
     "mojo_hip_swa_packed_workspace_bytes": (c_int64, [_I] * 10),
     "mojo_hip_swa_packed": (c_int, [_P] * 6 + [_I] * 10 + [c_float, c_int, c_int, _P, _I, _I, _I, _P]),
+    "mojo_hip_sdpa_workspace_bytes": (c_int64, [_I] * 6),
+    "mojo_hip_sdpa": (c_int, [_P] * 5 + [_I] * 15 + [c_int] + [_I] * 3 + [c_float, c_int, _P, _I, _P]),
     "mojo_hip_store_paged_kv_c8_plan": (c_int, [_P] * 7 + [_I] * 6 + [c_int, c_int] + [_I] * 5 + [_P]),
     "mojo_hip_store_paged_kv_c8_layout": (c_int, [_P] * 7 + [_I, _I, _P, _P] + [_I] * 6 + [c_int, c_int] + [_I] * 5 + [_P]),
     "mojo_hip_paged_decode_gqa_kv8_workspace_bytes": (c_int64, [_I] * 7),

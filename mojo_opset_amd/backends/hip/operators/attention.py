@@ -5,7 +5,7 @@ from typing import Optional
 import torch
 
 from ....core.operators.attention import (MojoPagedDecodeGQA, MojoPagedDecodeNstepSWA, MojoPagedDecodeSWA,
-                                          MojoPagedPrefillGQA, MojoPagedPrefillSWA, MojoSWA, assert_nstep_query,
+                                          MojoPagedPrefillGQA, MojoPagedPrefillSWA, MojoSdpa, MojoSWA, assert_nstep_query,
                                           assert_paged_decode_contract, assert_paged_prefill_contract,
                                           assert_swa_packed_contract)
 from .... import switches
@@ -126,6 +126,7 @@ _DECODE_NSTEP = ("mojo_hip_paged_decode_nstep_workspace_bytes", "mojo_hip_paged_
 _PREFILL_GQA = ("mojo_hip_paged_prefill_gqa_workspace_bytes", "mojo_hip_paged_prefill_gqa")
 _PREFILL_SWA = ("mojo_hip_paged_prefill_swa_workspace_bytes", "mojo_hip_paged_prefill_swa")
 _SWA_PACKED = ("mojo_hip_swa_packed_workspace_bytes", "mojo_hip_swa_packed")
+_SDPA = ("mojo_hip_sdpa_workspace_bytes", "mojo_hip_sdpa")
 
 
 class HIPPagedDecodeGQA(MojoPagedDecodeGQA):
@@ -328,3 +329,113 @@ class HIPSWA(MojoSWA):
             k.stride(0), k.stride(1), hint_q, hint_kv, scale, 1 if self.gqa_layout == "ABAB" else 0,
             L.dtype_code(q.dtype), L.ptr(ws), ws_bytes, *windows, L.stream_of(q)), what)
         return out
+
+
+def _sdpa_in_place(t) -> bool:
+    """A ``[B,H,S,D]`` tensor the kernel addresses where it is: dense in ``head_dim``, batch / head / token strides that are
+    multiples of 8 elements (16-byte rows), a 16-byte aligned base.  The token-major view (``[B,S,H,D]`` memory seen as
+    ``[B,H,S,D]``) and a contiguous tensor both qualify."""
+    return t.stride(3) == 1 and all(st % 8 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
+
+
+def _dense_aligned(t):
+    """A contiguous copy on a 16-byte boundary (a contiguous tensor on a misaligned base is copied too)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+_SDPA_DIMS, _SDPA_GROUPS = (64, 96, 128), (1, 2, 4, 8)
+
+
+class HIPSdpa(MojoSdpa):
+    """Bidirectional attention with an optional mask: the linear prefill kernel without its diagonal.  Every
+    row sees the keys ``[0, Sk)``; ``Sk < Sq`` is legal (cross-attention).
+
+    ``query`` is ``[B,Hq,Sq,D]`` (3-D: one batch entry), read in place as the token-major view (``x.view(b, s, n,
+    d).transpose(1, 2)``) or as a contiguous tensor, and the output has the query's form; anything else is made contiguous.
+    K and V are read in place under the rule of `_kv_in_place` (shared strides, dense ``head_dim``, 16-byte rows and bases),
+    otherwise copied.  ``enable_gqa=True`` groups heads as ``repeat_interleave`` does (AABB).
+
+    ``attn_mask`` must be broadcastable to ``[B,Hq,Sq,Sk]`` and is read in place through its own strides — a broadcast
+    dimension is never expanded; a mask whose last stride is not 1 is made contiguous.  Boolean: ``False`` hides the key.
+    Floating (the query's dtype or fp32): added to the scaled score, ``-inf`` allowed.
+
+    Envelope: bf16 / fp16, ``head_dim`` 64 / 96 / 128, ``Hq / Hkv`` 1 / 2 / 4 / 8, at most four dimensions; anything else raises
+    ``NotImplementedError``.  Beyond the reference: a row with no visible key (all ``False`` / ``-inf``) is zeros where torch
+    leaves NaN, and ``Sk == 0`` returns zeros.  No host sync, capture-safe."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key, value, attn_mask: Optional[torch.Tensor] = None):
+        what = "HIPSdpa"
+        if query.dim() > 4 or key.dim() > 4 or value.dim() > 4:
+            raise NotImplementedError(f"{what}: at most four dimensions [B,H,S,D], got {query.dim()}")
+        if query.dim() < 3 or key.dim() != query.dim() or value.dim() != query.dim():
+            raise RuntimeError(f"{what}: query, key and value must all be [B,H,S,D] or all [H,S,D]")
+        squeeze = query.dim() == 3
+        q, k, v = (t.unsqueeze(0) if squeeze else t for t in (query, key, value))
+        batch, hq, sq, dim = q.shape
+        hkv, sk = k.shape[1], k.shape[2]
+        if k.shape[0] != batch or k.shape[3] != dim or v.shape != k.shape:
+            raise RuntimeError(f"{what}: key {tuple(key.shape)} / value {tuple(value.shape)} do not match query "
+                               f"{tuple(query.shape)} in batch, head_dim or each other")
+        if hq != hkv and not (self.enable_gqa and hkv > 0 and hq % hkv == 0):
+            raise RuntimeError(f"{what}: {hq} query heads against {hkv} key/value heads "
+                               f"(enable_gqa={self.enable_gqa}: the counts must be equal, or a multiple with enable_gqa=True)")
+        if not (query.dtype == key.dtype == value.dtype):
+            raise RuntimeError(f"{what}: query, key and value must share a dtype, got {query.dtype}, {key.dtype}, {value.dtype}")
+        if query.dtype not in (torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"{what}: dtype {query.dtype} (bf16 / fp16)")
+        if dim not in _SDPA_DIMS:
+            raise NotImplementedError(f"{what}: head_dim {dim} {_SDPA_DIMS}")
+        if hq // hkv not in _SDPA_GROUPS:
+            raise NotImplementedError(f"{what}: {hq // hkv} query heads per kv head {_SDPA_GROUPS}")
+        mask, kind, m_strides = None, 0, (0, 0, 0)
+        if attn_mask is not None:
+            mask = attn_mask
+            if mask.dim() > 4:
+                raise NotImplementedError(f"{what}: a mask of {mask.dim()} dimensions (at most four)")
+            if mask.dtype == torch.bool:
+                kind = 1
+            elif mask.dtype == query.dtype:
+                kind = 2
+            elif mask.dtype == torch.float32:
+                kind = 3
+            else:
+                raise NotImplementedError(f"{what}: mask dtype {mask.dtype} (bool, {query.dtype} or float32)")
+            shape = (1,) * (4 - mask.dim()) + tuple(mask.shape)
+            if any(m != 1 and m != full for m, full in zip(shape, (batch, hq, sq, sk))):
+                raise RuntimeError(f"{what}: mask {tuple(attn_mask.shape)} is not broadcastable to {(batch, hq, sq, sk)}")
+            mask = mask.reshape(shape)
+            if shape[3] != sk:                             # one value per row: the only broadcast that is materialised
+                mask = mask.expand(shape[0], shape[1], shape[2], sk).contiguous()
+            elif mask.stride(3) != 1 and sk > 1:
+                mask = mask.contiguous()
+            # a broadcast dimension (size 1, or expanded by the caller) is addressed with stride 0
+            m_strides = tuple(0 if mask.shape[i] == 1 else mask.stride(i) for i in range(3))
+            if (sq - 1) * m_strides[2] + sk + 64 >= 1 << 31:
+                raise NotImplementedError(f"{what}: a (batch, head) plane of the mask must stay below 2^31 elements")
+        L.require_cuda(query, key, value, attn_mask)
+        if not _sdpa_in_place(q):
+            q = _dense_aligned(q)
+        if not (_sdpa_in_place(k) and _sdpa_in_place(v) and k.stride() == v.stride()):
+            k, v = _dense_aligned(k), _dense_aligned(v)
+        # the output in the query's form: token-major stays token-major, everything else is contiguous [B,H,S,D]
+        if sq > 1 and hq > 1 and q.stride(2) == hq * dim and q.stride(1) == dim:
+            out = torch.empty((batch, sq, hq, dim), dtype=q.dtype, device=q.device).transpose(1, 2)
+        else:
+            out = torch.empty((batch, hq, sq, dim), dtype=q.dtype, device=q.device)
+        if batch == 0 or hq == 0 or sq == 0:
+            return out[0] if squeeze else out
+        if sk == 0:                                        # no key anywhere: every row reads as zeros
+            out.zero_()
+            return out[0] if squeeze else out
+        scale = 1.0 / math.sqrt(dim) if self.scale is None else float(self.scale)
+        lib = L.load()
+        ws_bytes = getattr(lib, _SDPA[0])(batch, hq, hkv, sq, sk, dim)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes > 0 else None
+        L.check(getattr(lib, _SDPA[1])(
+            L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(mask), L.ptr(out), batch, hq, hkv, sq, sk, dim,
+            q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2),
+            k.stride(0), k.stride(1), k.stride(2), kind, *m_strides, scale, L.dtype_code(q.dtype),
+            L.ptr(ws), ws_bytes, L.stream_of(q)), what)
+        return out[0] if squeeze else out

@@ -2,7 +2,7 @@ from .activation import MojoSwiGLU
 from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
                         MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
                         MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
-                        MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoSWA)
+                        MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoSdpa, MojoSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
 from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
@@ -48,6 +48,9 @@ NSTEP_KV_INT8_OPS = ("MojoPagedDecodeNstepSWAWithKVDequant",)
 # packed var-len attention over contiguous K/V (the reference's core `MojoSWA`): a set of its own likewise (golden:
 # tests/swa_packed_golden.py)
 PACKED_ATTN_OPS = ("MojoSWA",)
+# bidirectional attention with an optional mask (the reference's core `MojoSdpa`): a set of its own likewise (golden:
+# tests/sdpa_golden.py)
+FULL_ATTN_OPS = ("MojoSdpa",)
 # the activation ops between the GEMMs of a dense W8A8 decoder layer: norm + quant, static quant, dequant and the fc1 -> fc2
 # stage.  A set of its own likewise (golden: tests/quant_dense_golden.py)
 QUANT_DENSE_OPS = ("MojoRMSNormQuant", "MojoLayerNormQuant", "MojoResidualAddLayerNormQuant", "MojoStaticQuant", "MojoDequant",

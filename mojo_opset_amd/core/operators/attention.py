@@ -3,7 +3,7 @@
 Constructor arguments, contracts and `forward` signatures follow
 `mojo_opset/core/operators/attention.py` (`MojoPagedDecodeGQA` :113-232,
 `MojoPagedPrefillGQA` :315-451, contracts :12-37, `MojoPagedPrefillSWA` :533-650,
-`MojoPagedDecodeSWA` :653-744, `MojoSWA` :747-838) and `mojo_opset/experimental/operators/attention.py` (`MojoPagedDecodeNstepSWA`
+`MojoPagedDecodeSWA` :653-744, `MojoSWA` :747-838, `MojoSdpa` :456-504) and `mojo_opset/experimental/operators/attention.py` (`MojoPagedDecodeNstepSWA`
 :1154-1262).  The classes are API-only; see `core/operator.py` for why the golden `forward` is not here.
 """
 from typing import Optional
@@ -177,6 +177,24 @@ class MojoSWA(_PagedSWABase, MojoOperator):
                  local_window_size: Optional[int] = None):
         super().__init__()
         self._init_swa(is_causal, gqa_layout, global_window_size, local_window_size)
+
+
+class MojoSdpa(MojoOperator):
+    """Bidirectional scaled-dot-product attention with an optional mask: every query row sees every key (no causal edge).
+
+    forward(query [B,Hq,Sq,D], key [B,Hkv,Sk,D], value [B,Hkv,Sk,D], attn_mask=None) -> [B,Hq,Sq,D]; 3-D tensors are one
+    batch entry.  ``scale=None`` is ``1 / sqrt(D)``.  ``enable_gqa=True`` lets ``Hq`` be a multiple of ``Hkv``: query head
+    ``h`` reads kv head ``h // (Hq // Hkv)`` (the grouping of ``repeat_interleave``).  ``attn_mask`` is broadcastable to
+    ``[B,Hq,Sq,Sk]``: boolean (``False`` hides the key) or floating (added to the scaled score, ``-inf`` allowed).
+    """
+
+    def __init__(self, scale: Optional[float] = None, enable_gqa: bool = False):
+        super().__init__()
+        self.scale = scale
+        self.enable_gqa = enable_gqa
+
+    def extra_repr(self) -> str:
+        return f"scale={self.scale!r}, enable_gqa={self.enable_gqa!r}"
 
 
 class _PagedGQAKVDequantBase:

@@ -29,8 +29,11 @@
 // rows [cu_kv[b], cu_kv[b + 1]).  Key j of the sequence is row cu_kv[b] + j: an address, not a lookup.  The page-id window,
 // its LDS copy, the hole scan and the scalar page-id load per tile are compiled out; everything else is the code below.
 //
-// This header is the whole prefill: kernels, launch chain and plan.  paged_prefill_gqa.hip instantiates the paged forms and
-// swa_packed.hip the linear ones (two translation units: the instance count doubled and they compile side by side).
+// FULL instances (MojoSdpa, sdpa.hip): linear, bidirectional — every row sees [0, kv_len) — with uniform lengths, strided
+// addressing and an optional mask; see SdpaArgs.
+//
+// This header is the whole prefill: kernels, launch chain and plan.  paged_prefill_gqa.hip instantiates the paged forms,
+// swa_packed.hip the linear ones and sdpa.hip the bidirectional ones (three translation units: they compile side by side).
 #pragma once
 #include <math.h>
 
@@ -70,6 +73,19 @@ struct PrefillArgs {
   // sliding window (the SWA instances only): key j is visible to the row at position p iff j <= p and (j >= p - local_win or
   // j < global_win).  No local window: local_win = -2^30 (no key qualifies); no global window: global_win = 0.
   int local_win = -(1 << 30), global_win = 0;
+};
+
+// FULL instances (MojoSdpa, sdpa.hip): bidirectional attention of uniform [Sq] x [Sk] per batch entry, every tensor addressed by
+// 64-bit batch / head / token strides (in elements); no cu_* arrays.  MASK instances read an additive bias or a boolean mask in
+// place: mask_kind 1 = bool (one byte, 0 = hidden), 2 = the query's dtype, 3 = fp32; strides in elements, any of them may be 0
+// (a broadcast dimension), last dimension dense.  mask_vec: every stride is a multiple of 4 elements and the base is aligned
+// to 4 elements, so the four keys a lane owns per 16-key step are one vector load.
+struct SdpaArgs : PrefillArgs {
+  int64_t q_bs = 0, q_hs = 0, q_ts = 0, o_bs = 0, o_hs = 0, o_ts = 0, kv_bs = 0;
+  int sq = 0, sk = 0;
+  const void* mask = nullptr;
+  int64_t m_bs = 0, m_hs = 0, m_rs = 0;
+  int mask_kind = 0, mask_vec = 0;
 };
 
 template <typename T> struct pf_mfma;
@@ -123,8 +139,12 @@ constexpr int PF_TABLE = 1024;                // block-table entries cached in L
 constexpr int PF_LDS = 4 * PF_TILE_BYTES + PF_TABLE * 4 + 16;    // K0 V0 K1 V1 | table slice | first negative page
 
 template <typename T, int G /* q heads per kv head */, int DK /* head_dim / 32 */, bool SPLIT = false /* key split, see PrefillArgs */,
-          bool SWA = false /* sliding window, see below */, bool LINEAR = false /* packed K/V, no pages (see the top) */>
-__global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
+          bool SWA = false /* sliding window, see below */, bool LINEAR = false /* packed K/V, no pages (see the top) */,
+          bool FULL = false /* no causal edge: every row sees [0, kv_len); strided addressing (SdpaArgs) */,
+          bool MASK = false /* FULL only: a bias / boolean mask per score */>
+__global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL, SdpaArgs, PrefillArgs> a) {
+  static_assert(!FULL || (LINEAR && !SWA), "the bidirectional instances are linear and take no window");
+  static_assert(!MASK || FULL, "a mask is read by the bidirectional instances only");
   typedef typename pf_mfma<T>::frag frag;
   constexpr int QPB = 128 / G;               // query positions per workgroup
   constexpr int DT = DK * 2;                 // 16-wide d tiles
@@ -140,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   // (key split: the slices of a block are consecutive workgroups; `wg` is the block's index in the unsplit order)
   const int ks = SPLIT ? static_cast<int>(blockIdx.x % a.ksplit) : 0;
   const int wg = SPLIT ? static_cast<int>(blockIdx.x / a.ksplit) : static_cast<int>(blockIdx.x);
-  if (wg >= a.n_qb * inner) {
+  if (!FULL && wg >= a.n_qb * inner) {                    // (FULL: no padding rows, the grid has no such workgroups)
     if (SPLIT && ks != 0) return;
     // Trailing workgroups zero the padding tokens behind the last sequence (rows no sequence owns must read as zeros);
     // they sit at the end of the grid, i.e. in the tail of the launch, and replace a memset of the whole output.
@@ -179,15 +199,20 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     }
   }
   // (asm scalar loads: left to hipcc the four bounds are vector loads, the cached-length pair behind a branch and a wait each)
-  const int32_t* pq = a.cu_q + b;
-  const int32_t* pk = (a.cu_kv ? a.cu_kv : a.cu_q) + b;
+  const int32_t* pq = FULL ? nullptr : a.cu_q + b;
+  const int32_t* pk = FULL ? nullptr : (a.cu_kv ? a.cu_kv : a.cu_q) + b;
   int q_start, q_end, kv_lo, kv_end;
+  if constexpr (FULL) {                                  // uniform lengths: kernel arguments, nothing to load
+    q_start = 0; q_end = a.sq; kv_lo = 0; kv_end = a.sk;
+  } else {
   asm volatile("s_load_dword %0, %1, 0x0" : "=s"(q_start) : "s"(pq) : "memory");
   asm volatile("s_load_dword %0, %1, 0x4" : "=s"(q_end) : "s"(pq) : "memory");
   asm volatile("s_load_dword %0, %1, 0x0" : "=s"(kv_lo) : "s"(pk) : "memory");
   asm volatile("s_load_dword %0, %1, 0x4" : "=s"(kv_end) : "s"(pk) : "memory");
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(q_start), "+s"(q_end), "+s"(kv_lo), "+s"(kv_end) : : "memory");
-  if constexpr (!LINEAR) {
+  }
+  if constexpr (FULL) {
+  } else if constexpr (!LINEAR) {
 #pragma unroll
     for (int j = 0; j < PF_TABLE / 256; ++j) asm volatile("" : "+v"(ids[j]));      // (the window's loads are requested up there, not where hipcc finds their first use)
   } else {
@@ -196,7 +221,16 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     kv_lo = min(max(kv_lo, 0), kv_end);
   }
   const int q_len = q_end - q_start;
-  const int kv_len = a.cu_kv ? kv_end - kv_lo : q_len;
+  const int kv_len = (FULL || a.cu_kv) ? kv_end - kv_lo : q_len;
+  // row `pos` of this sequence, head `head`, in the query and in the output (FULL: by strides, the two may differ)
+  auto q_row = [&](int pos, int head) -> const T* {
+    if constexpr (FULL) return static_cast<const T*>(a.q) + (b * a.q_bs + head * a.q_hs + pos * a.q_ts);
+    else return static_cast<const T*>(a.q) + (static_cast<int64_t>(q_start + pos) * a.hq + head) * a.dim;
+  };
+  auto out_row = [&](int pos, int head) -> T* {
+    if constexpr (FULL) return static_cast<T*>(a.out) + (b * a.o_bs + head * a.o_hs + pos * a.o_ts);
+    else return static_cast<T*>(a.out) + (static_cast<int64_t>(q_start + pos) * a.hq + head) * a.dim;
+  };
   // rows [pos0, pos1) of this sequence, the G heads of this kv-head, written as zeros
   auto zero_rows = [&](int pos0, int pos1) {
     typedef typename vec_of<T, 8>::type V8;
@@ -207,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     for (int i = threadIdx.x; i < (pos1 - pos0) * G * chunks8; i += 256) {
       const int c = i % chunks8, g = (i / chunks8) % G, pos = pos0 + i / (chunks8 * G);
       const int head = a.abab ? g * a.hkv + kvh : kvh * G + g;
-      *reinterpret_cast<V8*>(static_cast<T*>(a.out) + (static_cast<int64_t>(q_start + pos) * a.hq + head) * a.dim + c * 8) = z;
+      *reinterpret_cast<V8*>(out_row(pos, head) + c * 8) = z;
     }
   };
   // A sequence longer than the caller's max_q_len hint has rows no query block of this launch covers: they are written
@@ -218,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     if (ks == 0) zero_rows(qb * QPB, min(q_len, (qb + 1) * QPB));
     return;
   }
-  const int offset = kv_len - q_len;                     // query i sees keys 0 .. offset + i
+  const int offset = FULL ? 0 : kv_len - q_len;          // query i sees keys 0 .. offset + i (FULL: enters no bound)
 #ifdef PF_WG_STAMPS
   const unsigned long long wg_t0 = __builtin_readcyclecounter();
   if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) {
@@ -233,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   const int grp = lane >> 4, l15 = lane & 15;
 
   const int pos_hi = min(q_len, (qb + 1) * QPB) - 1;    // last query position of this block
-  int kv_hi = min(kv_len, offset + pos_hi + 1);          // keys [0, kv_hi) are visible to some row
+  int kv_hi = FULL ? kv_len : min(kv_len, offset + pos_hi + 1);   // keys [0, kv_hi) are visible to some row
   if (kv_hi < 1) kv_hi = 1;
   const int n_kb_all = (kv_hi + PF_KEYS - 1) / PF_KEYS;
   // Sliding window (MojoPagedPrefillSWA).  The rows of the block sit at positions [p_lo, p_hi]; together they see keys
@@ -293,7 +327,20 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     row_head[qt] = a.abab ? g * a.hkv + kvh : kvh * G + g;
     row_pos[qt] = pos;
     if (pos >= q_len) pos = q_len - 1;                   // clamp: computed, never stored
-    qptr[qt] = static_cast<const T*>(a.q) + (static_cast<int64_t>(q_start + pos) * a.hq + row_head[qt]) * a.dim;
+    qptr[qt] = q_row(pos, row_head[qt]);
+  }
+  // MASK: the 16 rows of a q tile share one head (QPB is a multiple of 16), so the mask's (batch, head) base is a scalar and
+  // the lane adds a 32-bit element offset: row * row stride (+ key).  The host bounds Sq * row stride + Sk below 2^31.
+  const char* mask_base[2] = {nullptr, nullptr};
+  unsigned mask_row[2] = {0u, 0u};
+  if constexpr (MASK) {
+    const int esz = a.mask_kind == 1 ? 1 : (a.mask_kind == 2 ? 2 : 4);
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      const int head_u = __builtin_amdgcn_readfirstlane(row_head[qt]);
+      mask_base[qt] = static_cast<const char*>(a.mask) + (b * a.m_bs + head_u * a.m_hs) * esz;
+      mask_row[qt] = static_cast<unsigned>(min(row_pos[qt], q_len - 1)) * static_cast<unsigned>(a.m_rs);
+    }
   }
   frag qf[2][DK];
 #pragma unroll
@@ -349,7 +396,8 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   // wave w fills keys [16w, 16w+16) of a tile with 4 LDS-DMA instructions per tensor (4 keys x 256 B each);
   // lane l: key l/16 of the four, LDS chunk position l%16
   // (LINEAR: the bases already stand on the sequence's first key, so a row is key * c_tok; 64-bit throughout)
-  const int64_t seq_base = kvh * a.c_head + (LINEAR ? static_cast<int64_t>(kv_lo) * a.c_tok : int64_t{0});
+  int64_t seq_base = kvh * a.c_head + (LINEAR ? static_cast<int64_t>(kv_lo) * a.c_tok : int64_t{0});
+  if constexpr (FULL) seq_base += b * a.kv_bs;
   const T* kbase = static_cast<const T*>(a.kc) + seq_base;
   const T* vbase = static_cast<const T*>(a.vc) + seq_base;
   const int chunks = a.dim / 8;
@@ -496,7 +544,8 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     u0 = min(max(r0 - gap_t, 0), n_vkb);
     n_whole = min(max(full_end / PF_KEYS - gap_t, u0), n_vkb) - u0;
   }
-  const int n_full = SWA ? min(n_whole, n_kb) : min(min(min(kv_len, offset + qb * QPB + 1), first_neg_key) / PF_KEYS, n_kb);
+  const int n_full = FULL ? min(kv_len / PF_KEYS, n_kb)
+                          : SWA ? min(n_whole, n_kb) : min(min(min(kv_len, offset + qb * QPB + 1), first_neg_key) / PF_KEYS, n_kb);
   const int n_fast = a.fast_stage ? n_full : 0;          // tiles [0, n_fast) may be staged the fast way
 
   if (kb_lo < n_kb) stage(rtile(kb_lo), kb_lo & 1);
@@ -519,9 +568,13 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   unsigned tacc = 0;
   unsigned long long t_prev = __builtin_readcyclecounter();
 #endif
-  auto key_block = [&](auto masked_tag, auto fast_tag, int kb) {
+  // (mask_tag, MASK instances: the mask's element kind — SdpaArgs::mask_kind — and whether its whole tiles take vector loads;
+  //  tile-invariant, so the key loops are chosen ONCE per workgroup, see `walk` below.  0 / false in every other instance.)
+  auto key_block = [&](auto masked_tag, auto fast_tag, auto mkind_tag, auto mvec_tag, int kb) {
     constexpr bool MASKED = decltype(masked_tag)::value;
     constexpr bool FAST = decltype(fast_tag)::value;     // the NEXT tile is complete and staged the fast way
+    constexpr int MKIND = decltype(mkind_tag)::value;
+    constexpr bool MVEC = decltype(mvec_tag)::value && !MASKED;   // (the masked variant of a FULL instance is the tail tile alone)
     if constexpr (FAST) { PF_STAMP(0); }
     const int buf = kb & 1;
     int64_t stage_base = 0;
@@ -530,9 +583,19 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     if constexpr (FAST) {
       page_ready(phys_next);
       stage_base = stage_fast_base(rtile(kb + 1), phys_next);
-      asm volatile("" : "+s"(stage_base));               // computed here, not sunk behind the reads
+      if constexpr (!MASK) asm volatile("" : "+s"(stage_base));   // computed here, not sunk behind the reads
       stage_k = reinterpret_cast<const char*>(kbase) + stage_base;
       stage_v = reinterpret_cast<const char*>(vbase) + stage_base;
+      if constexpr (MASK) {                                // (one of several loop sets: the bases' uniformity is stated, not inferred)
+        auto uniform_ptr = [](const char* p) -> const char* {
+          const uint64_t v = reinterpret_cast<uint64_t>(p);
+          const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
+          const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
+          return reinterpret_cast<const char*>((static_cast<uint64_t>(hi) << 32) | lo);
+        };
+        stage_k = uniform_ptr(stage_k);
+        stage_v = uniform_ptr(stage_v);
+      }
       asm volatile("" : "+s"(stage_k), "+s"(stage_v));
     }
     const lds_c* kt = smem + buf * 2 * PF_TILE_BYTES;
@@ -612,6 +675,44 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     }
     PF_QK(0) PF_QK(1) PF_QK(2) PF_QK(3)
 #undef PF_QK
+    // ---- MASK: this tile's bias / mask values, 16 per q tile and lane (keys key0 + 16 t + r of the lane's row), requested HERE:
+    // the K fragments have just died, so their registers take the raw values, and the round trip overlaps the drain of the 8 * DK
+    // MFMAs above.  Plain loads, so hipcc counts them on vmcnt together with the LDS-DMA of the next tile: the general staging
+    // was issued in front of them (a wait for them is vmcnt(0) and also waits for the DMA), the fast staging's pieces are issued
+    // behind them one at a time inside the softmax (the wait for q tile 1's values leaves the pieces issued so far in
+    // flight).  The closing vmcnt(0) of the tile covers both.  Whole tiles of a mask with 4-element-aligned rows take one vector
+    // load per 16-key step; the tail tile and any other mask take element loads, predicated on key < kv_len.
+    unsigned mraw[2][16];                                  // (vector loads of bool / 16-bit masks fill 1 / 2 registers per step)
+    if constexpr (MASK) {
+      const unsigned mkey = static_cast<unsigned>(rtile(kb) * PF_KEYS + 4 * grp);
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const size_t e = static_cast<size_t>(mask_row[qt] + mkey + 16 * t);
+          if constexpr (MVEC) {
+            if constexpr (MKIND == 1) {
+              mraw[qt][4 * t] = *reinterpret_cast<const unsigned*>(mask_base[qt] + e);
+            } else if constexpr (MKIND == 2) {
+              const uint2 v = *reinterpret_cast<const uint2*>(mask_base[qt] + e * 2);
+              mraw[qt][4 * t] = v.x; mraw[qt][4 * t + 1] = v.y;
+            } else {
+              const uint4 v = *reinterpret_cast<const uint4*>(mask_base[qt] + e * 4);
+              mraw[qt][4 * t] = v.x; mraw[qt][4 * t + 1] = v.y; mraw[qt][4 * t + 2] = v.z; mraw[qt][4 * t + 3] = v.w;
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              // (a key past kv_len is never read: the clamp keeps the address inside the row, the score is set to -inf below)
+              size_t er = e + r;
+              if constexpr (MASKED) er = min(er, static_cast<size_t>(mask_row[qt]) + static_cast<size_t>(kv_len - 1));
+              if constexpr (MKIND == 1) mraw[qt][4 * t + r] = *reinterpret_cast<const unsigned char*>(mask_base[qt] + er);
+              else if constexpr (MKIND == 2) mraw[qt][4 * t + r] = *reinterpret_cast<const unsigned short*>(mask_base[qt] + er * 2);
+              else mraw[qt][4 * t + r] = *reinterpret_cast<const unsigned*>(mask_base[qt] + er * 4);
+            }
+          }
+        }
+    }
     // ---- V^T fragments: transposed reads, 4 per d tile, issued in two batches of DT/2 d tiles.
     // Each batch is one asm statement (issue) + one wait statement naming every destination (hipcc must not touch
     // them in between); the waits are lgkmcnt(0) because scalar loads share the counter and return out of order.
@@ -687,6 +788,26 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     // queues behind the V^T reads just requested and cost ~300 cycles apiece, four times per tile.
     auto softmax_tile = [&](int qt) {
       f32x4 (&sc)[4] = s[qt];
+      if constexpr (MASK) {
+        // bias in the kernel's log2 units, fp32 (a hidden key of a boolean mask: -inf; a visible one: + 0, the score's own bits)
+        constexpr float LOG2E = 1.4426950408889634f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float bias;
+            if constexpr (MKIND == 1) {
+              const unsigned byte = MVEC ? (mraw[qt][4 * t] >> (8 * r)) & 0xffu : mraw[qt][4 * t + r];
+              bias = byte ? 0.f : -INFINITY;
+            } else if constexpr (MKIND == 2) {
+              const unsigned h = MVEC ? (mraw[qt][4 * t + (r >> 1)] >> (16 * (r & 1))) & 0xffffu : mraw[qt][4 * t + r];
+              bias = static_cast<float>(__builtin_bit_cast(T, static_cast<unsigned short>(h))) * LOG2E;
+            } else {
+              bias = __builtin_bit_cast(float, mraw[qt][4 * t + r]) * LOG2E;
+            }
+            sc[t][r] += bias;
+          }
+      }
       if constexpr (MASKED) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -694,7 +815,11 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
           for (int r = 0; r < 4; ++r) {
             const int key = key0 + 16 * t + r;
             if (has_hole && key >= first_neg_key) sc[t][r] = seed[qt];   // zero K rows: score 0 (relative to the reference)
-            if (key > offset + row_pos[qt] || key >= kv_len) sc[t][r] = -INFINITY;
+            if constexpr (FULL) {
+              if (key >= kv_len) sc[t][r] = -INFINITY;   // the tail tile: no causal edge
+            } else {
+              if (key > offset + row_pos[qt] || key >= kv_len) sc[t][r] = -INFINITY;
+            }
             if constexpr (SWA) {
               if (key >= a.global_win && key < offset + row_pos[qt] - a.local_win) sc[t][r] = -INFINITY;
             }
@@ -798,7 +923,27 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
     if constexpr (FAST) { PF_STAMP(9); }
   };
   int kb_i = kb_lo;
-  for (; kb_i + 1 < n_fast; ++kb_i) key_block(std::false_type{}, std::true_type{}, kb_i);     // the hot loop
+  // MASK: the three loops below exist once per mask kind and load form, and the workgroup takes one set (`walk`).
+  [[maybe_unused]] auto walk = [&](auto mkind_tag, auto mvec_tag) __attribute__((always_inline)) {
+    for (; kb_i + 1 < n_fast; ++kb_i) key_block(std::false_type{}, std::true_type{}, mkind_tag, mvec_tag, kb_i);
+    if (a.fast_stage) page_ready(phys_next);
+    for (; kb_i < n_full; ++kb_i) key_block(std::false_type{}, std::false_type{}, mkind_tag, mvec_tag, kb_i);
+    for (; kb_i < n_kb; ++kb_i) key_block(std::true_type{}, std::false_type{}, mkind_tag, mvec_tag, kb_i);
+  };
+  if constexpr (MASK) {
+    if (a.mask_vec) {
+      if (a.mask_kind == 1) walk(std::integral_constant<int, 1>{}, std::true_type{});
+      else if (a.mask_kind == 2) walk(std::integral_constant<int, 2>{}, std::true_type{});
+      else walk(std::integral_constant<int, 3>{}, std::true_type{});
+    } else {
+      if (a.mask_kind == 1) walk(std::integral_constant<int, 1>{}, std::false_type{});
+      else if (a.mask_kind == 2) walk(std::integral_constant<int, 2>{}, std::false_type{});
+      else walk(std::integral_constant<int, 3>{}, std::false_type{});
+    }
+  }
+  if constexpr (!MASK) {
+  constexpr std::integral_constant<int, 0> no_mask{};
+  for (; kb_i + 1 < n_fast; ++kb_i) key_block(std::false_type{}, std::true_type{}, no_mask, std::false_type{}, kb_i);     // the hot loop
   if (a.fast_stage) page_ready(phys_next);               // retire the last request before its register is reused
 #ifdef PF_STAMPS
   if (blockIdx.x < 8192) {
@@ -810,8 +955,9 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
 #ifdef PF_WG_STAMPS
   if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) { g_pf_stamps[blockIdx.x * 16 + 4] = kb_i; g_pf_stamps[blockIdx.x * 16 + 5] = n_kb; }
 #endif
-  for (; kb_i < n_full; ++kb_i) key_block(std::false_type{}, std::false_type{}, kb_i);
-  for (; kb_i < n_kb; ++kb_i) key_block(std::true_type{}, std::false_type{}, kb_i);
+  for (; kb_i < n_full; ++kb_i) key_block(std::false_type{}, std::false_type{}, no_mask, std::false_type{}, kb_i);
+  for (; kb_i < n_kb; ++kb_i) key_block(std::true_type{}, std::false_type{}, no_mask, std::false_type{}, kb_i);
+  }
   PF_WG_MARK(2);
 
   // ---- finish: reduce the row sums over the 4 lane groups, normalise, store ----------------------------------
@@ -840,7 +986,8 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
   typedef typename vec_of<T, 4>::type V4;
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
-    const float inv = 1.0f / (osum[qt][0] + xor_sum_16_32(lhole[qt]));
+    const float lsum = osum[qt][0] + xor_sum_16_32(lhole[qt]);
+    const float inv = (FULL && !(lsum > 0.f)) ? 0.f : 1.0f / lsum;   // (FULL: a row whose mask hides every key stores zeros)
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       V4 ov;
@@ -864,7 +1011,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
       const int g = r / QPB;
       const int head = a.abab ? g * a.hkv + kvh : kvh * G + g;
       const V8 v = *reinterpret_cast<const __attribute__((address_space(3))) V8*>(stage_o + row * OROW + ch * 16);
-      *reinterpret_cast<V8*>(static_cast<T*>(a.out) + (static_cast<int64_t>(q_start + pos) * a.hq + head) * a.dim + ch * 8) = v;
+      *reinterpret_cast<V8*>(out_row(pos, head) + ch * 8) = v;
     }
   }
   PF_WG_MARK(3);
@@ -879,8 +1026,13 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(PrefillArgs a) {
 // dependent loads: 43 us beside a 145 us attention launch.  Sixteen times the workgroups and the slices of an item loaded four
 // at a time before they are used.)
 constexpr int PF_MERGE_SPLIT = 16;
-template <typename T, int G>
-__global__ __launch_bounds__(256) void prefill_merge_kernel(PrefillArgs a) {
+template <bool FULL, int WHICH, typename A>
+static __device__ __forceinline__ int sdpa_len(const A& a) {    // Sq (0) / Sk (1) of a FULL instance's arguments
+  if constexpr (FULL) return WHICH ? a.sk : a.sq;
+  else return 0;
+}
+template <typename T, int G, bool FULL = false>
+__global__ __launch_bounds__(256) void prefill_merge_kernel(std::conditional_t<FULL, SdpaArgs, PrefillArgs> a) {
   constexpr int QPB = 128 / G;
   constexpr int ROWS = 128 / PF_MERGE_SPLIT;
   const int inner = a.hkv * a.batch;
@@ -888,9 +1040,9 @@ __global__ __launch_bounds__(256) void prefill_merge_kernel(PrefillArgs a) {
   const int qb = a.n_qb - 1 - wg / inner;
   const int rem = wg % inner;
   const int kvh = rem % a.hkv, b = (rem / a.hkv + a.skew * (wg / inner)) % a.batch;
-  const int q_start = a.cu_q[b];
-  const int q_len = a.cu_q[b + 1] - q_start;
-  const int kv_len = a.cu_kv ? a.cu_kv[b + 1] - a.cu_kv[b] : q_len;
+  const int q_start = FULL ? 0 : a.cu_q[b];
+  const int q_len = FULL ? sdpa_len<FULL, 0>(a) : a.cu_q[b + 1] - q_start;
+  const int kv_len = FULL ? sdpa_len<FULL, 1>(a) : (a.cu_kv ? a.cu_kv[b + 1] - a.cu_kv[b] : q_len);
   if (qb * QPB >= q_len || kv_len <= 0) return;          // (rows the attention launch zeroed or never owned)
   const int per_row = a.dim / 4;
   typedef typename vec_of<T, 4>::type V4;
@@ -927,7 +1079,8 @@ __global__ __launch_bounds__(256) void prefill_merge_kernel(PrefillArgs a) {
     V4 ov;
 #pragma unroll
     for (int e = 0; e < 4; ++e) ov[e] = static_cast<T>(num[e] * inv);
-    *reinterpret_cast<V4*>(static_cast<T*>(a.out) + (static_cast<int64_t>(q_start + pos) * a.hq + head) * a.dim + d0) = ov;
+    if constexpr (FULL) *reinterpret_cast<V4*>(static_cast<T*>(a.out) + (b * a.o_bs + head * a.o_hs + pos * a.o_ts) + d0) = ov;
+    else *reinterpret_cast<V4*>(static_cast<T*>(a.out) + (static_cast<int64_t>(q_start + pos) * a.hq + head) * a.dim + d0) = ov;
   }
 }
 
