@@ -25,9 +25,10 @@ constexpr int GATE_MAX_E = 1024;
 
 // One token: logits = sum of `parts` fp32 partials (stride `part_stride` floats), softmax over E, k rounds of wave-wide
 // arg-max (descending value, ties -> lowest expert id), gates renormalised over the selected.  Lane l holds experts
-// l, l+64, ...; all 64 lanes of the wave call this together.
+// l, l+64, ...; all 64 lanes of the wave call this together.  Partials `lo_from` .. are multiplied by `lo_scale`, an exact power
+// of two, as they are added (the matrix-core route's scaled w_lo slabs, see moe_gate_split_kernel; elsewhere parts / 1.f).
 __device__ __forceinline__ void gate_softmax_topk(const float* logits, int64_t part_stride, int parts, int experts, int top_k,
-                                                  int lane, int32_t* out_idx, float* out_gate) {
+                                                  int lane, int32_t* out_idx, float* out_gate, int lo_from, float lo_scale) {
   constexpr int PER = GATE_MAX_E / 64;
   float v[PER];
   float mx = -INFINITY;
@@ -36,8 +37,9 @@ __device__ __forceinline__ void gate_softmax_topk(const float* logits, int64_t p
     const int e = lane + 64 * i;
     if (e < experts) {
       float acc = 0.f;
-      for (int p = 0; p + 1 < parts; p += 2) acc += logits[e + p * part_stride] + logits[e + (p + 1) * part_stride];
-      if (parts & 1) acc += logits[e + (parts - 1) * part_stride];
+      for (int p = 0; p + 1 < parts; p += 2)
+        acc += logits[e + p * part_stride] * (p >= lo_from ? lo_scale : 1.f) + logits[e + (p + 1) * part_stride] * (p + 1 >= lo_from ? lo_scale : 1.f);
+      if (parts & 1) acc += logits[e + (parts - 1) * part_stride] * (parts - 1 >= lo_from ? lo_scale : 1.f);
       v[i] = acc;
     } else {
       v[i] = -INFINITY;
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(256) void moe_gating_kernel(const T* __restrict__ x
   for (int t = wave; t < tpw; t += 4) {
     const int64_t token = tok0 + t;
     if (token >= tokens) break;
-    gate_softmax_topk(s_logits + t * experts, part, 4, experts, top_k, lane, out_idx + token * top_k, out_gate + token * top_k);
+    gate_softmax_topk(s_logits + t * experts, part, 4, experts, top_k, lane, out_idx + token * top_k, out_gate + token * top_k, 4, 1.f);
   }
 }
 
@@ -277,7 +279,7 @@ __global__ __launch_bounds__(256) void moe_gate_reduce_select_kernel(const float
       if (e0 + 64 * q < experts) s_lg[wave * e_pad + e0 + 64 * q] = acc[q];
   }
   __syncthreads();
-  if (wave == 0) gate_softmax_topk(s_lg, e_pad, 4, experts, top_k, lane, out_idx + token * top_k, out_gate + token * top_k);
+  if (wave == 0) gate_softmax_topk(s_lg, e_pad, 4, experts, top_k, lane, out_idx + token * top_k, out_gate + token * top_k, 4, 1.f);
 }
 
 // Few tokens (a decode step): the router is a tiny product — T x H x E multiply-adds against an fp32 weight of 1-7 MB —
@@ -380,21 +382,27 @@ __global__ __launch_bounds__(256) void moe_gating_small_kernel(const T* __restri
   }
 }
 
-// large expert counts: logits come from the MFMA GEMM (x @ w_hi + x @ w_lo, `parts` fp32 slabs of [tokens, e_pad]);
-// one wave per token
+// large expert counts: logits come from the MFMA GEMM (x @ w_hi + x @ w_lo, `parts` fp32 slabs of [tokens, e_pad], the first half
+// of them hi, the second lo, the lo ones still scaled by 1 / lo_scale); one wave per token
 __global__ __launch_bounds__(256) void moe_gate_select_kernel(const float* __restrict__ logits, int64_t part_stride, int parts,
                                                               int e_pad, int32_t* __restrict__ out_idx,
                                                               float* __restrict__ out_gate, int64_t tokens, int experts,
-                                                              int top_k) {
+                                                              int top_k, float lo_scale) {
   const int lane = threadIdx.x & 63;
   const int64_t token = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (token >= tokens) return;
   gate_softmax_topk(logits + token * e_pad, part_stride, parts, experts, top_k, lane, out_idx + token * top_k,
-                    out_gate + token * top_k);
+                    out_gate + token * top_k, parts / 2, lo_scale);
 }
 
 // fp32 gate weight [hidden, E] -> hi + lo in the activation dtype, [hidden, e_pad] each (zero padded columns):
-// x @ w = x @ hi + x @ lo to ~2^-16 relative, which keeps the expert ranking of the fp32 product
+// x @ w = x @ hi + x @ lo to ~2^-16 relative, which keeps the expert ranking of the fp32 product.
+// fp16 stores lo * 2^11: |w - hi| <= 2^-11 |w| falls into fp16's subnormals (spacing 2^-24) from |w| < 2^-3 on and at
+// N(0, 0.0005) weights kept two bits — logits off by 1.3e-6 where the claim allows 1.6e-7, unexcused expert choices on the
+// device.  Scaled, |lo| <= |w| has hi's exponent range and all 11 bits; the select kernel multiplies the lo slabs
+// by 2^-11 as it adds them (exact).  bf16 has fp32's exponent range: shift 0, bits unchanged.
+template <typename T> struct gate_lo_shift { static constexpr int value = 0; };
+template <> struct gate_lo_shift<f16_t> { static constexpr int value = 11; };
 template <typename T>
 __global__ __launch_bounds__(256) void moe_gate_split_kernel(const float* __restrict__ w, T* __restrict__ hi, T* __restrict__ lo,
                                                              int hidden, int experts, int e_pad) {
@@ -405,7 +413,7 @@ __global__ __launch_bounds__(256) void moe_gate_split_kernel(const float* __rest
     const float v = e < experts ? w[h * experts + e] : 0.f;
     const T a = elt<T>::from_f(v);
     hi[i] = a;
-    lo[i] = elt<T>::from_f(v - elt<T>::to_f(a));
+    lo[i] = elt<T>::from_f((v - elt<T>::to_f(a)) * static_cast<float>(1 << gate_lo_shift<T>::value));
   }
 }
 
@@ -832,7 +840,7 @@ static int launch_gating(const void* x, const float* w, int32_t* idx, float* gat
 #undef GATE_EI
 #undef GATE_LAUNCH
   MOJO_CHECK_LAUNCH("moe_gating");
-  note_launch("moe_gating:general");
+  note_launch("moe_gating:general:tt%d:ei%d", tt, ei <= 1 ? 1 : ei <= 2 ? 2 : ei <= 4 ? 4 : ei <= 8 ? 8 : 16);   // the instance GATE_EI took
   return MOJO_OK;
 }
 
@@ -910,8 +918,9 @@ static int gating_mfma(const void* x, const float* w, int32_t* idx, float* gate,
     if (rc) return rc;
   }
   hipLaunchKernelGGL(moe_gate_select_kernel, dim3(static_cast<unsigned>(ceil_div(tokens, 4))), dim3(256), 0, s, logits, slab,
-                     sk2, e_pad, idx, gate, tokens, experts, top_k);
+                     sk2, e_pad, idx, gate, tokens, experts, top_k, 1.f / static_cast<float>(1 << gate_lo_shift<T>::value));
   MOJO_CHECK_LAUNCH("moe_gating(select)");
+  note_launch("moe_gating:mfma:sk%d", sk2);
   return MOJO_OK;
 }
 
@@ -945,7 +954,7 @@ extern "C" int mojo_hip_moe_gating(const void* hidden, const float* gate_weight,
     hipLaunchKernelGGL(moe_gate_reduce_select_kernel, dim3(static_cast<unsigned>(tokens)), dim3(256), static_cast<size_t>(4) * e_pad * sizeof(float), s,
                        slabs, tokens * e_pad, p.slices, e_pad, top_k_indices, top_k_gates, e, k);
     MOJO_CHECK_LAUNCH("moe_gating(select)");
-    note_launch("moe_gating:small");
+    note_launch("moe_gating:small:ep%d:slices%d", 1 << p.ep_log2, p.slices);
     return MOJO_OK;
   }
   if (gate_use_mfma(tokens, hidden_size, num_experts, dtype)) {
@@ -955,7 +964,6 @@ extern "C" int mojo_hip_moe_gating(const void* hidden, const float* gate_weight,
     MOJO_REQUIRE(tokens < (1LL << 31), MOJO_EUNSUPPORTED, "moe_gating: too many tokens");
     const int rc = dtype == MOJO_BF16 ? gating_mfma<bf16_t>(hidden, gate_weight, top_k_indices, top_k_gates, tokens, h, e, k, dtype, workspace, s)
                                       : gating_mfma<f16_t>(hidden, gate_weight, top_k_indices, top_k_gates, tokens, h, e, k, dtype, workspace, s);
-    if (rc == MOJO_OK) note_launch("moe_gating:mfma");
     return rc;
   }
   switch (dtype) {

@@ -329,10 +329,10 @@ def test_gating_eight_expert_kernel_agrees_with_general_kernel(k, hidden, tokens
     x = torch.rand(tokens, hidden, dtype=dtype, device=DEV)
     monkeypatch.setenv("MOJO_HIP_GATING", "2")                   # streaming kernels only (the E = 8 specialisation where it applies)
     idx_s, g_s = op(x)
-    assert last_launch() == ("moe_gating:e8" if hidden % 512 == 0 and tokens >= 32 else "moe_gating:general"), last_launch()
+    assert last_launch().startswith("moe_gating:e8" if hidden % 512 == 0 and tokens >= 32 else "moe_gating:general:"), last_launch()
     monkeypatch.setenv("MOJO_HIP_GATING", "1")                   # (the fixture makes the library re-read its switches)
     idx_g, g_g = op(x)
-    assert last_launch() == "moe_gating:general", last_launch()  # the general kernel really ran
+    assert last_launch().startswith("moe_gating:general:"), last_launch()  # the general kernel really ran
     same = idx_s == idx_g
     assert float(same.float().mean()) >= 0.999
     torch.testing.assert_close(g_s[same], g_g[same], atol=1e-5, rtol=1e-4)
@@ -357,10 +357,10 @@ def test_gating_mfma_route_agrees_with_vector_route(dtype, monkeypatch):
     x = torch.rand(tokens, hidden, dtype=dtype, device=DEV)
     monkeypatch.setenv("MOJO_HIP_GATING", "4")
     idx_m, g_m = op(x)
-    assert last_launch() == "moe_gating:mfma", last_launch()
+    assert last_launch().startswith("moe_gating:mfma:"), last_launch()
     monkeypatch.setenv("MOJO_HIP_GATING", "1")
     idx_v, g_v = op(x)
-    assert last_launch() == "moe_gating:general", last_launch()
+    assert last_launch().startswith("moe_gating:general:"), last_launch()
     same = idx_m == idx_v
     assert float(same.float().mean()) >= 0.999
     torch.testing.assert_close(g_m[same], g_v[same], atol=1e-4, rtol=1e-3)
@@ -381,11 +381,11 @@ def test_gating_few_token_kernel_matches_the_oracle(tokens, experts, k, hidden, 
     x = torch.rand(tokens, hidden).to(dtype)
     monkeypatch.setenv("MOJO_HIP_GATING", "3")
     idx_s, gate_s = to_cpu(op(x.to(DEV)))
-    assert last_launch() == "moe_gating:small", last_launch()
+    assert last_launch().startswith("moe_gating:small:"), last_launch()
     idx_w, gate_w = ref(x)
     monkeypatch.setenv("MOJO_HIP_GATING", "1")
     idx_g, gate_g = to_cpu(op(x.to(DEV)))
-    assert last_launch() == "moe_gating:general", last_launch()
+    assert last_launch().startswith("moe_gating:general:"), last_launch()
     # selections can only differ where two probabilities are closer than fp32 summation-order noise
     for idx_o, gate_o in ((idx_w.to(torch.int32), gate_w), (idx_g, gate_g)):
         same = (idx_s == idx_o).all(-1)
