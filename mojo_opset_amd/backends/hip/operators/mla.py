@@ -67,14 +67,29 @@ class _AbsorbedWeightCache:
         return torch.nn.Module._load_from_state_dict(self, *args, **kwargs)
 
 
+def _prepared(op, query, block_tables, softmax_scale):
+    """What both routes hand to their kernels: the token-major query, the row-contiguous tables, the sink as contiguous fp32
+    (or None), the softmax scale and the detached, contiguous ``kv_b_proj``.  Each is the caller's own tensor when it has
+    that form already (no copy); a strided parameter is copied per call (the repack cache is keyed on the original)."""
+    tq, heads, qk = query.shape
+    if query.stride(2) != 1 or query.stride(1) != qk or query.stride(0) != heads * qk:
+        query = query.contiguous()
+    tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
+    sink = getattr(op, "attn_sink", None)
+    sink = None if sink is None else sink.detach().to(torch.float32).contiguous()
+    scale = 1.0 / math.sqrt(op.qk_nope_head_dim + op.qk_rope_head_dim) if softmax_scale is None else float(softmax_scale)
+    proj = op.kv_b_proj.detach()
+    proj = proj if proj.is_contiguous() else proj.contiguous()
+    return query, tables, sink, scale, proj
+
+
 def _mla_forward(op, query, ckv_cache, kpe_cache, block_tables, softmax_scale, *, total_seq_lens=None, cu_q_lens=None,
                  cu_total_seq_lens=None):
     L.require_cuda(query, ckv_cache, kpe_cache, block_tables, total_seq_lens, cu_q_lens, cu_total_seq_lens, op.kv_b_proj)
     tq, heads, qk = query.shape
     nope, rope, vdim, r = op.qk_nope_head_dim, op.qk_rope_head_dim, op.v_head_dim, op.kv_lora_rank
     assert heads == op.num_heads and qk == nope + rope
-    proj = op.kv_b_proj.detach()
-    if proj.dtype != query.dtype or ckv_cache.dtype != query.dtype or kpe_cache.dtype != query.dtype:
+    if op.kv_b_proj.dtype != query.dtype or ckv_cache.dtype != query.dtype or kpe_cache.dtype != query.dtype:
         # the golden's `c_kv @ kv_b_proj.T` raises the same way when the module was not cast to the cache dtype
         raise RuntimeError("expected m1 and m2 to have the same dtype: cast the module (kv_b_proj) to the cache dtype")
     assert ckv_cache.dim() == 4 and ckv_cache.shape[1] == 1 and ckv_cache.shape[3] == r
@@ -82,17 +97,13 @@ def _mla_forward(op, query, ckv_cache, kpe_cache, block_tables, softmax_scale, *
     assert ckv_cache.shape[:3] == kpe_cache.shape[:3]
     if ckv_cache.stride(3) != 1 or kpe_cache.stride(3) != 1:
         raise NotImplementedError("hip mla: caches must be dense in their last dimension")
-    if not proj.is_contiguous():           # (a strided parameter is copied per call; the repack cache is keyed on the original)
-        proj = proj.contiguous()
     page = ckv_cache.shape[2]
-    scale = 1.0 / math.sqrt(nope + rope) if softmax_scale is None else float(softmax_scale)
     dev = query.device
     if tq == 0:
         return torch.zeros(0, heads, vdim, dtype=query.dtype, device=dev)
+    query, tables, sink, scale, proj = _prepared(op, query, block_tables, softmax_scale)
 
     # 1) absorb W_kn into the query:  q_abs[t, h] = q_nope[t, h] @ W_kn[h]   (W_kn[h]: [nope, r], k rows)
-    if query.stride(2) != 1 or query.stride(1) != qk or query.stride(0) != heads * qk:
-        query = query.contiguous()
     q_abs = torch.empty(tq, heads, r, dtype=query.dtype, device=dev)
     if tq <= 128 and nope % 128 == 0 and r % 64 == 0:
         # decode-sized: the weight-streaming grouped GEMM wants K-major weights; W_kn is stored [nope, r] per head, so a
@@ -106,14 +117,11 @@ def _mla_forward(op, query, ckv_cache, kpe_cache, block_tables, softmax_scale, *
         q_rope, q_rope_ld = q_rope.contiguous(), rope
 
     # 2) attention over the compressed cache
-    tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
     o_lat = torch.empty(tq, heads, r, dtype=query.dtype, device=dev)
     lib = L.load()
     batch = tables.shape[0]
     max_len = page * tables.shape[1]
     ws = torch.empty(max(lib.mojo_hip_mla_latent_attn_workspace_bytes(tq, heads, r, max_len), 64), dtype=torch.uint8, device=dev)
-    sink = getattr(op, "attn_sink", None)
-    sink = None if sink is None else sink.detach().to(torch.float32).contiguous()
     L.check(lib.mojo_hip_mla_latent_attn(
         L.ptr(q_abs), r, L.ptr(q_rope), q_rope_ld, L.ptr(ckv_cache), L.ptr(kpe_cache),
         L.ptr(None if total_seq_lens is None else total_seq_lens.contiguous()),
@@ -168,18 +176,11 @@ def _prefill_decompressed(op, query, ckv_cache, kpe_cache, cu_q_lens, block_tabl
     seqs_per_slice = max(1, min(batch, budget // (per_seq * kv_cols * es)))
     if cu_total_seq_lens is None and tq * kv_cols * es <= budget:
         seqs_per_slice = batch                              # kv = q lengths: the whole batch has exactly tq keys
-    proj = op.kv_b_proj.detach()
-    proj = proj if proj.is_contiguous() else proj.contiguous()
-    if query.stride(2) != 1 or query.stride(1) != qk or query.stride(0) != heads * qk:
-        query = query.contiguous()
-    tables = block_tables if block_tables.stride(1) == 1 else block_tables.contiguous()
+    query, tables, sink, scale, proj = _prepared(op, query, block_tables, softmax_scale)
     cu_q = cu_q_lens.contiguous()
     cu_kv = None if cu_total_seq_lens is None else cu_total_seq_lens.contiguous()
     stream = L.stream_of(query)
     out = torch.empty(tq, heads, vdim, dtype=dt, device=dev)
-    sink = getattr(op, "attn_sink", None)
-    sink = None if sink is None else sink.detach().to(torch.float32).contiguous()
-    scale = 1.0 / math.sqrt(nope + rope) if softmax_scale is None else float(softmax_scale)
     # (no clamp to the cache's own token count: sequences that share prefix pages sum to more than the cache holds)
     cap = seqs_per_slice * per_seq
     if cu_total_seq_lens is None:

@@ -57,49 +57,15 @@ __global__ __launch_bounds__(512, 1) void mla512_oct_kernel(MlaArgs a) {
   const int hq = wave & 3, half = wave >> 2;          // 16-head group, key / latent half
   const int grp = lane >> 4, l15 = lane & 15;
 
-  int b, n_vis;
-  if (a.cu_q == nullptr) {
-    b = tile;
-    n_vis = a.seq_lens[b];
-  } else {
-    if (tile < a.cu_q[0] || tile >= a.cu_q[a.batch]) return;
-    int lo = 0, hi = a.batch;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.cu_q[mid] <= tile) lo = mid; else hi = mid;
-    }
-    b = lo;
-    const int q_len = a.cu_q[b + 1] - a.cu_q[b];
-    const int kv_len = a.cu_kv ? a.cu_kv[b + 1] - a.cu_kv[b] : q_len;
-    n_vis = min(kv_len, kv_len - q_len + (tile - a.cu_q[b]) + 1);
-  }
-  const int32_t* table = a.tables + static_cast<int64_t>(b) * a.table_stride;
-  if (n_vis > 0) {                                    // the golden stops at the first negative page id
-    int p1 = (n_vis + a.page - 1) / a.page;
-    int fn = -1;
-    if (p1 > a.max_pages) { fn = a.max_pages; p1 = a.max_pages; }
-    for (int base = 0; base < p1; base += 64) {
-      const int idx = base + lane;
-      const int v = idx < p1 ? table[idx] : 0;
-      const unsigned long long neg = __ballot(v < 0);
-      if (neg) { fn = base + __builtin_ctzll(neg); break; }
-    }
-    if (fn >= 0) n_vis = min(n_vis, fn * a.page);
-  }
+  const MlaRow row = mla_row(a, tile, lane);
+  if (row.padding) return;
   const int k_begin = split * a.split_keys;
-  const int k_end = min(n_vis, k_begin + a.split_keys);
+  const int k_end = min(row.n_vis, k_begin + a.split_keys);
   const int n_kt = k_end > k_begin ? (k_end - k_begin + MLA_KEYS - 1) / MLA_KEYS : 0;
 
-  int* s_table = reinterpret_cast<int*>(smem_generic + TABLE_OFF);
-  const unsigned table_u32 = smem_u32 + TABLE_OFF;
-  int win_base = 0;
-  auto fill_window = [&](int p0) {
-    for (int i = threadIdx.x; i < TABLE_ENTRIES; i += 512) s_table[i] = (p0 + i < a.max_pages) ? table[p0 + i] : -1;
-    win_base = p0;
-    __syncthreads();
-  };
   auto page_of = [&](int key) { return key >> a.page_shift; };
-  fill_window(page_of(k_begin));
+  MlaWindow<TABLE_ENTRIES, 512> win(smem_generic + TABLE_OFF, a, row.table);
+  win.fill(page_of(k_begin));
 
   const int head0 = hb * HPB + hq * 16;                 // first head of this wave
   const bool active = head0 < a.heads;                  // identical for the two waves of a pair
@@ -125,13 +91,7 @@ __global__ __launch_bounds__(512, 1) void mla512_oct_kernel(MlaArgs a) {
     StagePlan sp;
     sp.buf = buf;
     const int k_first = k_begin + kt * MLA_KEYS;
-    {
-      const int p_last = page_of(min(k_first + MLA_KEYS - 1, k_end - 1));
-      if (p_last >= win_base + TABLE_ENTRIES) {
-        __syncthreads();
-        fill_window(page_of(k_first));
-      }
-    }
+    win.ahead(k_first, min(k_first + MLA_KEYS - 1, k_end - 1), page_of);
     const int mask = a.page - 1;
     int my_phys, phys_b;
     const int key_l = min(k_first + wave + 8 * (lane & 7), k_end - 1);      // lane i < 8 owns c_kv row wave + 8i
@@ -139,7 +99,7 @@ __global__ __launch_bounds__(512, 1) void mla512_oct_kernel(MlaArgs a) {
     const int key_b = min(k_first + row_b, k_end - 1);
     asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)"
                  : "=&v"(my_phys), "=&v"(phys_b)
-                 : "v"(table_u32 + 4 * ((key_l >> a.page_shift) - win_base)), "v"(table_u32 + 4 * ((key_b >> a.page_shift) - win_base))
+                 : "v"(win.addr(page_of(key_l))), "v"(win.addr(page_of(key_b)))
                  : "memory");
     my_phys = max(my_phys, 0);
     phys_b = max(phys_b, 0);
@@ -392,16 +352,7 @@ __global__ __launch_bounds__(512, 1) void mla512_oct_kernel(MlaArgs a) {
   typedef typename vec_of<T, 4>::type V4;
   const int d0 = half * 256 + grp * 4;
   if (a.n_splits == 1) {
-    float den = lt;
-    float w = 1.f;
-    const float ml2 = m * a.scale_log2;
-    if (a.sink) {
-      const float sk = a.sink[head] * 1.4426950408889634f;
-      const float M = fmaxf(ml2, sk);
-      w = (m == -INFINITY) ? 0.f : fast_exp2(ml2 - M);
-      den = lt * w + fast_exp2(sk - M);
-    }
-    const float inv = den > 0.f ? w / den : 0.f;
+    const float inv = mla_finish<MlaFastExp2>(m * a.scale_log2, m == -INFINITY, lt, a.sink, head);
     T* dst = static_cast<T*>(a.o_lat) + (static_cast<int64_t>(tile) * a.heads + head) * R + d0;
 #pragma unroll
     for (int dt = 0; dt < 16; ++dt) {
@@ -411,7 +362,7 @@ __global__ __launch_bounds__(512, 1) void mla512_oct_kernel(MlaArgs a) {
       *reinterpret_cast<V4*>(dst + dt * 16) = ov;
     }
   } else {
-    const int64_t slot = (static_cast<int64_t>(tile) * a.n_splits + split) * a.heads + head;
+    const int64_t slot = mla_slot(a, tile, split, head);
     float* po = a.part_o + slot * R + d0;
 #pragma unroll
     for (int dt = 0; dt < 16; ++dt) *reinterpret_cast<f32x4*>(po + dt * 16) = o[dt];

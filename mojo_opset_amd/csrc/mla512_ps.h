@@ -80,36 +80,10 @@ __global__ __launch_bounds__(512, 2) void mla512_ps_kernel(MlaArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r31 = lane & 31, h = lane >> 5;
 
-  int b, n_vis;
-  if (a.cu_q == nullptr) {
-    b = tile;
-    n_vis = a.seq_lens[b];
-  } else {
-    if (tile < a.cu_q[0] || tile >= a.cu_q[a.batch]) return;
-    int lo = 0, hi = a.batch;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.cu_q[mid] <= tile) lo = mid; else hi = mid;
-    }
-    b = lo;
-    const int q_len = a.cu_q[b + 1] - a.cu_q[b];
-    const int kv_len = a.cu_kv ? a.cu_kv[b + 1] - a.cu_kv[b] : q_len;
-    n_vis = min(kv_len, kv_len - q_len + (tile - a.cu_q[b]) + 1);
-  }
-  const int32_t* table = a.tables + static_cast<int64_t>(b) * a.table_stride;
-  if (n_vis > 0) {                                    // the golden stops at the first negative page id
-    int p1 = (n_vis + a.page - 1) / a.page;
-    int fn = -1;
-    if (p1 > a.max_pages) { fn = a.max_pages; p1 = a.max_pages; }
-    for (int base = 0; base < p1; base += 64) {
-      const int idx = base + lane;
-      const int v = idx < p1 ? table[idx] : 0;
-      const unsigned long long neg = __ballot(v < 0);
-      if (neg) { fn = base + __builtin_ctzll(neg); break; }
-    }
-    if (fn >= 0) n_vis = min(n_vis, fn * a.page);
-  }
-  n_vis = __builtin_amdgcn_readfirstlane(n_vis);
+  const MlaRow row = mla_row(a, tile, lane);
+  if (row.padding) return;
+  const int32_t* table = row.table;                     // (page ids by scalar loads: no LDS window)
+  const int n_vis = __builtin_amdgcn_readfirstlane(row.n_vis);
   const int k_begin = split * a.split_keys;
   const int k_end = min(n_vis, k_begin + a.split_keys);
   const int n_kt = k_end > k_begin ? (k_end - k_begin + KEYS - 1) / KEYS : 0;      // 32-key slots of this split
@@ -373,19 +347,11 @@ __global__ __launch_bounds__(512, 2) void mla512_ps_kernel(MlaArgs a) {
       lt = p + q;
     }
     if (a.n_splits == 1) {
-      float den = lt, w = 1.f;
-      const float ml2 = m * a.scale_log2;
-      if (a.sink) {
-        const float sk = a.sink[head] * 1.4426950408889634f;
-        const float M = fmaxf(ml2, sk);
-        w = (m == -INFINITY) ? 0.f : fast_exp2(ml2 - M);
-        den = lt * w + fast_exp2(sk - M);
-      }
-      const float inv = den > 0.f ? w / den : 0.f;
+      const float inv = mla_finish<MlaFastExp2>(m * a.scale_log2, m == -INFINITY, lt, a.sink, head);
       asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(al_base), "v"(inv) : "memory");
       __builtin_amdgcn_s_barrier();
     } else if (active && h == 0 && head0 + r31 < a.heads) {
-      const int64_t slot = (static_cast<int64_t>(tile) * a.n_splits + split) * a.heads + head;
+      const int64_t slot = mla_slot(a, tile, split, head);
       a.part_ml[slot * 2] = m * a.scale_log2;
       a.part_ml[slot * 2 + 1] = lt;
     }
@@ -500,7 +466,7 @@ __global__ __launch_bounds__(512, 2) void mla512_ps_kernel(MlaArgs a) {
       }
   } else {
     if (!store || (a.ps_debug & 32)) return;
-    const int64_t slot = (static_cast<int64_t>(tile) * a.n_splits + split) * a.heads + head;
+    const int64_t slot = mla_slot(a, tile, split, head);
     float* po = a.part_o + slot * R + dhalf * 256 + 4 * h;
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt)

@@ -48,6 +48,10 @@ struct MlaArgs {
   int ps_prefetch;          // mla512_ps: L2 prefetch ahead of the LDS-DMA (MOJO_HIP_MLA_PS_PREFETCH=1: by the loaders, 2: by a consumer wave per group; default off)
 };
 
+}  // namespace mojo
+#include "mla_common.h"
+namespace mojo {
+
 template <typename T> struct mla_mfma;
 template <> struct mla_mfma<bf16_t> {
   typedef bf16x8 frag;
@@ -59,7 +63,7 @@ template <> struct mla_mfma<f16_t> {
 };
 
 constexpr int MLA_KEYS = 64;
-constexpr int MLA512_DEFAULT_KERNEL = 3;       // 0 oct, 1 pair, 2 ping-pong, 3 specialised waves (dispatch_mla)
+constexpr int MLA512_DEFAULT_KERNEL = 3;       // 0 oct, 1 pair, 2 ping-pong, 3 specialised waves (MLA_K_*, mla512_choice)
 
 template <int R, int ROPE> struct mla_geom {
   static constexpr int CH = (R + ROPE) / 8;                               // 16-byte chunks per latent row
@@ -88,48 +92,15 @@ __global__ __launch_bounds__(512 / NQ, NQ == 1 ? 2 : 1) void mla_latent_kernel(M
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int grp = lane >> 4, l15 = lane & 15;
 
-  // ---- which sequence / how many visible keys -----------------------------------------------------------
-  int b, n_vis;
-  if (a.cu_q == nullptr) {                                  // decode: tile == sequence
-    b = tile;
-    n_vis = a.seq_lens[b];
-  } else {                                                  // prefill: tile == query token
-    if (tile < a.cu_q[0] || tile >= a.cu_q[a.batch]) return;   // padding token: stays zero
-    int lo = 0, hi = a.batch;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.cu_q[mid] <= tile) lo = mid; else hi = mid;
-    }
-    b = lo;
-    const int q_len = a.cu_q[b + 1] - a.cu_q[b];
-    const int kv_len = a.cu_kv ? a.cu_kv[b + 1] - a.cu_kv[b] : q_len;
-    n_vis = min(kv_len, kv_len - q_len + (tile - a.cu_q[b]) + 1);
-  }
-  const int32_t* table = a.tables + static_cast<int64_t>(b) * a.table_stride;
-  if (n_vis > 0) {                                          // golden: pages behind the first negative id are dropped
-    int p1 = (n_vis + a.page - 1) / a.page;
-    int fn = -1;
-    if (p1 > a.max_pages) { fn = a.max_pages; p1 = a.max_pages; }
-    for (int base = 0; base < p1; base += 64) {
-      const int idx = base + lane;
-      const int v = idx < p1 ? table[idx] : 0;
-      const unsigned long long neg = __ballot(v < 0);
-      if (neg) { fn = base + __builtin_ctzll(neg); break; }
-    }
-    if (fn >= 0) n_vis = min(n_vis, fn * a.page);
-  }
+  // ---- which sequence / how many visible keys (mla_common.h) ------------------------------------------------
+  const MlaRow row = mla_row(a, tile, lane);
+  if (row.padding) return;                                  // padding token: stays zero
+  const int n_vis = row.n_vis;
   const int k_begin = split * a.split_keys;
   const int k_end = min(n_vis, k_begin + a.split_keys);
-  // A window of TABLE_ENTRIES page ids lives in LDS (refilled when the key loop walks past it): no dependent
-  // global load — and no FLAT load, which hipcc guards with vmcnt(0)/lgkmcnt(0) — sits in front of the LDS-DMA.
-  int* s_table = reinterpret_cast<int*>(smem_generic + 2 * GE::TILE_BYTES);
-  int win_base = 0;
-  auto fill_window = [&](int p0) {
-    for (int i = threadIdx.x; i < GE::TABLE_ENTRIES; i += NTHREADS) s_table[i] = (p0 + i < a.max_pages) ? table[p0 + i] : -1;
-    win_base = p0;
-    __syncthreads();
-  };
-  fill_window(a.page_shift >= 0 ? (k_begin >> a.page_shift) : k_begin / a.page);
+  auto page_of = [&](int key) { return a.page_shift >= 0 ? (key >> a.page_shift) : key / a.page; };
+  MlaWindow<GE::TABLE_ENTRIES, NTHREADS> win(smem_generic + 2 * GE::TILE_BYTES, a, row.table);
+  win.fill(page_of(k_begin));
   const bool active = wave * 16 * NQ < a.heads;            // waves beyond the head count only help staging
   int head[NQ];
 #pragma unroll
@@ -152,15 +123,8 @@ __global__ __launch_bounds__(512 / NQ, NQ == 1 ? 2 : 1) void mla_latent_kernel(M
 
   // ---- staging: the tile is GE::CHS * 64 chunks, laid out linearly; 512 lanes take 512 chunks per round ------
   auto stage = [&](int kt, int buf) {
-    {  // wave-uniform for the whole workgroup
-      const int k_first = k_begin + kt * MLA_KEYS;
-      const int k_last = min(k_first + MLA_KEYS - 1, k_end - 1);
-      const int p_last = a.page_shift >= 0 ? (k_last >> a.page_shift) : k_last / a.page;
-      if (p_last >= win_base + GE::TABLE_ENTRIES) {
-        __syncthreads();
-        fill_window(a.page_shift >= 0 ? (k_first >> a.page_shift) : k_first / a.page);
-      }
-    }
+    const int k_first = k_begin + kt * MLA_KEYS;           // (uniform for the whole workgroup)
+    win.ahead(k_first, min(k_first + MLA_KEYS - 1, k_end - 1), page_of);
     constexpr int TOTAL = MLA_KEYS * GE::CHS;
     constexpr int ROUNDS = (TOTAL + NTHREADS - 1) / NTHREADS;
 #pragma unroll
@@ -173,8 +137,8 @@ __global__ __launch_bounds__(512 / NQ, NQ == 1 ? 2 : 1) void mla_latent_kernel(M
       if (cs >= GE::CH) cs = GE::CH - 1;                   // pad chunks: never read
       int key = k_begin + kt * MLA_KEYS + kl;
       if (key >= k_end) key = k_end - 1;
-      const int lp = a.page_shift >= 0 ? (key >> a.page_shift) : key / a.page;
-      int phys = s_table[lp - win_base];
+      const int lp = page_of(key);
+      int phys = win.id(lp);
       if (phys < 0) phys = 0;
       const int slot = key - lp * a.page;
       const T* src = cs < R / 8
@@ -317,15 +281,7 @@ __global__ __launch_bounds__(512 / NQ, NQ == 1 ? 2 : 1) void mla_latent_kernel(M
     const int hd = head[c];
     if (a.n_splits == 1) {
       // finish here: apply the optional sink logit, normalise; rows without keys become zeros (nan_to_num)
-      float den = ls;
-      float w = 1.f;
-      if (a.sink) {
-        const float sk = a.sink[hd] * 1.4426950408889634f;
-        const float M = fmaxf(m[c], sk);
-        w = (m[c] == -INFINITY) ? 0.f : exp2f(m[c] - M);
-        den = ls * w + exp2f(sk - M);
-      }
-      const float inv = den > 0.f ? w / den : 0.f;
+      const float inv = mla_finish<MlaExp2>(m[c], m[c] == -INFINITY, ls, a.sink, hd);
       T* dst = static_cast<T*>(a.o_lat) + (static_cast<int64_t>(tile) * a.heads + hd) * R;
       typedef typename vec_of<T, 4>::type V4;
 #pragma unroll
@@ -336,7 +292,7 @@ __global__ __launch_bounds__(512 / NQ, NQ == 1 ? 2 : 1) void mla_latent_kernel(M
         *reinterpret_cast<V4*>(dst + dt * 16 + grp * 4) = ov;
       }
     } else {
-      const int64_t slot = (static_cast<int64_t>(tile) * a.n_splits + split) * a.heads + hd;
+      const int64_t slot = mla_slot(a, tile, split, hd);
       float* po = a.part_o + slot * R;
 #pragma unroll
       for (int dt = 0; dt < GE::ND; ++dt) *reinterpret_cast<f32x4*>(po + dt * 16 + grp * 4) = o[c][dt];
@@ -381,7 +337,7 @@ __global__ __launch_bounds__(512) void mla_merge_kernel(MlaArgs a, int R) {
     f32x4 po[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int64_t slot = (static_cast<int64_t>(tile) * a.n_splits + min(i, a.n_splits - 1)) * a.heads + head;
+      const int64_t slot = mla_slot(a, tile, min(i, a.n_splits - 1), head);
       ms[i] = a.part_ml[slot * 2];
       ls[i] = a.part_ml[slot * 2 + 1];
       po[i] = live ? *reinterpret_cast<const f32x4*>(a.part_o + slot * R + d0) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -390,11 +346,7 @@ __global__ __launch_bounds__(512) void mla_merge_kernel(MlaArgs a, int R) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (i < a.n_splits) M1 = fmaxf(M1, ms[i]);
-    float sk1 = 0.f;
-    if (a.sink) {
-      sk1 = a.sink[head] * 1.4426950408889634f;
-      M1 = fmaxf(M1, sk1);
-    }
+    const float sk1 = mla_merge_sink(a.sink, head, M1);
     f32x4 num1 = {0.f, 0.f, 0.f, 0.f};
     float den1 = 0.f;
 #pragma unroll
@@ -405,8 +357,8 @@ __global__ __launch_bounds__(512) void mla_merge_kernel(MlaArgs a, int R) {
       if (live) num1 += po[i] * w;
     }
     if (!live) return;
-    den1 = (a.sink ? exp2f(sk1 - M1) : 0.f) + den1;
-    const float inv1 = den1 > 0.f ? 1.0f / den1 : 0.f;
+    den1 = mla_sink_share(a.sink, sk1, M1) + den1;
+    const float inv1 = mla_merge_inv(den1);
     typedef typename vec_of<T, 4>::type V4;
     V4 ov;
 #pragma unroll
@@ -415,20 +367,16 @@ __global__ __launch_bounds__(512) void mla_merge_kernel(MlaArgs a, int R) {
     return;
   }
   float M = -INFINITY;
-  for (int sp = sl; sp < a.n_splits; sp += nl) M = fmaxf(M, a.part_ml[((static_cast<int64_t>(tile) * a.n_splits + sp) * a.heads + head) * 2]);
+  for (int sp = sl; sp < a.n_splits; sp += nl) M = fmaxf(M, a.part_ml[mla_slot(a, tile, sp, head) * 2]);
   if (dt == 0) s_m[sl] = M;
   __syncthreads();
   M = s_m[0];
   for (int j = 1; j < nl; ++j) M = fmaxf(M, s_m[j]);
-  float sk = 0.f;
-  if (a.sink) {
-    sk = a.sink[head] * 1.4426950408889634f;
-    M = fmaxf(M, sk);
-  }
+  const float sk = mla_merge_sink(a.sink, head, M);
   f32x4 num = {0.f, 0.f, 0.f, 0.f};
   float den = 0.f;
   for (int sp = sl; sp < a.n_splits; sp += nl) {
-    const int64_t slot = (static_cast<int64_t>(tile) * a.n_splits + sp) * a.heads + head;
+    const int64_t slot = mla_slot(a, tile, sp, head);
     const float ms = a.part_ml[slot * 2];
     if (ms == -INFINITY) continue;
     const float w = exp2f(ms - M);
@@ -439,14 +387,118 @@ __global__ __launch_bounds__(512) void mla_merge_kernel(MlaArgs a, int R) {
   if (dt == 0) s_den[sl] = den;
   __syncthreads();
   if (sl != 0 || !live) return;
-  den = a.sink ? exp2f(sk - M) : 0.f;
+  den = mla_sink_share(a.sink, sk, M);
   for (int j = 0; j < nl; ++j) { den += s_den[j]; if (j) num += s_num[j][dt]; }
-  const float inv = den > 0.f ? 1.0f / den : 0.f;
+  const float inv = mla_merge_inv(den);
   typedef typename vec_of<T, 4>::type V4;
   V4 ov;
 #pragma unroll
   for (int e = 0; e < 4; ++e) ov[e] = static_cast<T>(num[e] * inv);
   *reinterpret_cast<V4*>(static_cast<T*>(a.o_lat) + (static_cast<int64_t>(tile) * a.heads + head) * R + d0) = ov;
+}
+
+// ---- the launch plan --------------------------------------------------------------------------------------------------------
+// Everything the host decides about a launch, in one place: the workspace query and the entry point both fill an MlaGeom and
+// read the MlaPlan; neither sizes anything itself.
+//
+// For the two calls to agree a C caller passes both the same q_tokens, heads and kv_lora_rank, runs them under the same
+// MOJO_HIP_MLA_SPLITS, and gives the query — which has no page arguments — as max_kv_len the length the launch walks:
+// block_size * max_blocks_per_seq, or the launch's own max_kv_len where that is positive and smaller.
+struct MlaGeom {                              // shapes only
+  int64_t q_tokens, heads, r, rope;
+  int64_t page, max_pages;                    // page == 0: no table shape (the query); max_kv_len then IS the capacity
+  int64_t max_kv_len;
+};
+
+enum { MLA_K_NONE = -2, MLA_K_LATENT = -1, MLA_K_OCT = 0, MLA_K_PAIR = 1, MLA_K_PP = 2, MLA_K_PS = 3 };
+
+// the r = 512 / rope = 64 kernels, indexed by MLA_K_*: one workgroup per (token, 64 heads, split)
+struct Mla512Kernel { void (*bf16)(MlaArgs); void (*f16)(MlaArgs); int lds_bytes, threads; const char* tag; };
+static const Mla512Kernel MLA512_KERNELS[4] = {
+    {mla512_oct_kernel<bf16_t>, mla512_oct_kernel<f16_t>, MLA512_OCT_LDS, 512, "oct"},
+#ifdef MOJO_HIP_BUILD_EXPERIMENTS
+    {mla512_pair_kernel<bf16_t>, mla512_pair_kernel<f16_t>, MLA512_PAIR_LDS, 256, "pair"},
+    {mla512_pp_kernel<bf16_t>, mla512_pp_kernel<f16_t>, MLA512_PP_LDS, 512, "pp"},
+#else
+    {nullptr, nullptr, 0, 0, "pair"},
+    {nullptr, nullptr, 0, 0, "pp"},
+#endif
+    {mla512_ps_kernel<bf16_t>, mla512_ps_kernel<f16_t>, MLA512_PS_LDS, 512, "ps"},
+};
+
+struct MlaPlan {
+  int64_t head_blocks;                        // workgroups per (token, split): the r = 512 kernels take 64 heads each
+  int64_t walk_len;                           // the longest key range the launch walks
+  int n_splits, split_keys;                   // splits of that range; keys per split (whole 64-key tiles)
+  int64_t slots;                              // (token, split, head) partials
+  int64_t need_bytes;                         // what the launch needs of the workspace (0: a single split)
+  int64_t query_bytes;                        // what the query answers: need_bytes + 64 of slack
+  int64_t part_o_off, part_ml_off;            // byte offsets of part_o [slots, r] and part_ml [slots, 2] (fp32) in the workspace
+  int kernel;                                 // MLA_K_*; MLA_K_NONE: no instance for (r, rope, page) — the launch refuses
+  const char* tag;                            // of an r = 512 kernel: the <which> of "mla512:<which>:splits<n>"
+};
+
+static int mla_splits(int64_t tiles, int64_t max_len) {
+  if (const int v = static_cast<int>(MOJO_SWITCH("MOJO_HIP_MLA_SPLITS", 0)); v >= 1) return v;
+  int64_t sp = 256 / (tiles > 0 ? tiles : 1);
+  const int64_t cap = ceil_div(max_len > 0 ? max_len : 1, 256);
+  if (sp > cap) sp = cap;
+  if (sp < 1) sp = 1;
+  if (sp > 64) sp = 64;
+  return static_cast<int>(sp);
+}
+
+// MOJO_HIP_MLA_KERNEL: "ps" specialised waves (default), "oct" two waves per SIMD in lock-step on 64-key tiles (the kernel
+// for pages below 16 tokens); an experiments build adds "pp" (ping-pong) and "pair" (one wave per SIMD)
+static int mla512_choice(int page_shift) {
+  int which = [] {
+    const long long e = MOJO_SWITCH("MOJO_HIP_MLA_KERNEL", -1);
+    if (e < 0) return MLA512_DEFAULT_KERNEL;
+    if (e == switch_word("ps")) return static_cast<int>(MLA_K_PS);
+#ifdef MOJO_HIP_BUILD_EXPERIMENTS
+    if (e == switch_word("pair")) return static_cast<int>(MLA_K_PAIR);
+    if (e == switch_word("pp")) return static_cast<int>(MLA_K_PP);
+#endif
+    return static_cast<int>(MLA_K_OCT);
+  }();
+  if (which == MLA_K_PS && page_shift < 4) which = MLA_K_OCT;   // a loader's 16 rows must share one page id: pages of >= 16 tokens
+  return which;
+}
+
+static int mla_page_shift(int64_t page) { return (page & (page - 1)) == 0 ? __builtin_ctzll(page) : -1; }
+
+static MlaPlan mla_plan(const MlaGeom& g) {
+  MlaPlan p{};
+  p.head_blocks = g.r == 512 ? (g.heads + 63) / 64 : 1;
+  const int64_t cap = g.page * g.max_pages;
+  p.walk_len = g.page == 0 ? g.max_kv_len : (g.max_kv_len > 0 && g.max_kv_len < cap) ? g.max_kv_len : cap;
+  p.n_splits = mla_splits(g.q_tokens * p.head_blocks, p.walk_len);
+  p.split_keys = static_cast<int>(ceil_div(ceil_div(p.walk_len > 0 ? p.walk_len : 1, p.n_splits), MLA_KEYS) * MLA_KEYS);
+  p.slots = g.q_tokens * p.n_splits * g.heads;
+  p.part_o_off = 0;
+  p.part_ml_off = p.slots * g.r * static_cast<int64_t>(sizeof(float));
+  p.need_bytes = p.n_splits > 1 ? p.slots * (g.r + 2) * static_cast<int64_t>(sizeof(float)) : 0;
+  p.query_bytes = p.need_bytes + 64;
+  p.kernel = MLA_K_NONE;
+  p.tag = "";
+  const bool general = (g.r == 64 && g.rope == 32) || (g.r == 32 && g.rope == 32) || (g.r == 256 && g.rope == 64) || (g.r == 128 && g.rope == 64);
+  if (g.r == 512 && g.rope == 64 && g.page > 0 && mla_page_shift(g.page) >= 0) {
+    p.kernel = mla512_choice(mla_page_shift(g.page));
+    p.tag = MLA512_KERNELS[p.kernel].tag;
+  } else if (general) {
+    p.kernel = MLA_K_LATENT;
+  }
+  return p;
+}
+
+// ---- the launches -----------------------------------------------------------------------------------------------------------
+template <typename T>
+static int launch_mla_merge(const MlaArgs& a, int r, hipStream_t s) {
+  if (a.n_splits > 1) {
+    hipLaunchKernelGGL(mla_merge_kernel<T>, dim3(a.n_tiles, a.heads), dim3(a.n_splits <= 4 ? 128 : 512), 0, s, a, r);
+    MOJO_CHECK_LAUNCH("mla_merge");
+  }
+  return MOJO_OK;
 }
 
 template <typename T, int R, int ROPE>
@@ -459,72 +511,31 @@ static int launch_mla(const MlaArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(fn, dim3(a.n_tiles, a.n_splits), dim3(512 / NQ), GE::LDS_BYTES, s, a);
   MOJO_CHECK_LAUNCH("mla_latent");
   note_launch("mla_latent:r%d:splits%d", R, a.n_splits);
-  if (a.n_splits > 1) {
-    hipLaunchKernelGGL(mla_merge_kernel<T>, dim3(a.n_tiles, a.heads), dim3(a.n_splits <= 4 ? 128 : 512), 0, s, a, R);
-    MOJO_CHECK_LAUNCH("mla_merge");
-  }
-  return MOJO_OK;
+  return launch_mla_merge<T>(a, R, s);
 }
 
 template <typename T>
-static int dispatch_mla(const MlaArgs& a, int r, int rope, hipStream_t s) {
-  if (r == 512 && rope == 64 && a.page_shift >= 0) {
-    const int head_blocks = (a.heads + 63) / 64;
-    // MOJO_HIP_MLA_KERNEL: "ps" specialised waves (default), "oct" two waves per SIMD in lock-step on 64-key tiles (the
-    // kernel for pages below 16 tokens); an experiments build adds "pp" (ping-pong) and "pair" (one wave per SIMD)
-    int which = [] {
-      const long long e = MOJO_SWITCH("MOJO_HIP_MLA_KERNEL", -1);
-      if (e < 0) return MLA512_DEFAULT_KERNEL;
-      if (e == switch_word("ps")) return 3;
-#ifdef MOJO_HIP_BUILD_EXPERIMENTS
-      if (e == switch_word("pair")) return 1;
-      if (e == switch_word("pp")) return 2;
-#endif
-      return 0;                                          // "oct"
-    }();
-    if (which == 3 && a.page_shift < 4) which = 0;       // a loader's 16 rows must share one page id: pages of >= 16 tokens
-    if (which == 3) {
-      void (*fn)(MlaArgs) = mla512_ps_kernel<T>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, MLA512_PS_LDS);
-      hipLaunchKernelGGL(fn, dim3(a.n_tiles * head_blocks, a.n_splits), dim3(512), MLA512_PS_LDS, s, a);
-#ifdef MOJO_HIP_BUILD_EXPERIMENTS
-    } else if (which == 1) {
-      void (*fn)(MlaArgs) = mla512_pair_kernel<T>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, MLA512_PAIR_LDS);
-      hipLaunchKernelGGL(fn, dim3(a.n_tiles * head_blocks, a.n_splits), dim3(256), MLA512_PAIR_LDS, s, a);
-    } else if (which == 2) {
-      void (*fn)(MlaArgs) = mla512_pp_kernel<T>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, MLA512_PP_LDS);
-      hipLaunchKernelGGL(fn, dim3(a.n_tiles * head_blocks, a.n_splits), dim3(512), MLA512_PP_LDS, s, a);
-#endif
-    } else {
-      void (*fn)(MlaArgs) = mla512_oct_kernel<T>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, MLA512_OCT_LDS);
-      hipLaunchKernelGGL(fn, dim3(a.n_tiles * head_blocks, a.n_splits), dim3(512), MLA512_OCT_LDS, s, a);
-    }
-    MOJO_CHECK_LAUNCH("mla512");
-    note_launch("mla512:%s:splits%d", which == 3 ? "ps" : which == 1 ? "pair" : which == 2 ? "pp" : "oct", a.n_splits);
-    if (a.n_splits > 1) {
-      hipLaunchKernelGGL(mla_merge_kernel<T>, dim3(a.n_tiles, a.heads), dim3(a.n_splits <= 4 ? 128 : 512), 0, s, a, 512);
-      MOJO_CHECK_LAUNCH("mla_merge");
-    }
-    return MOJO_OK;
-  }
-  if (r == 64 && rope == 32) return launch_mla<T, 64, 32>(a, s);
-  if (r == 32 && rope == 32) return launch_mla<T, 32, 32>(a, s);
-  if (r == 256 && rope == 64) return launch_mla<T, 256, 64>(a, s);
-  if (r == 128 && rope == 64) return launch_mla<T, 128, 64>(a, s);
-  MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "mla: (kv_lora_rank, rope) = (%d, %d) not instantiated", r, rope);
+static int launch_mla512(const MlaArgs& a, const MlaPlan& p, hipStream_t s) {
+  const Mla512Kernel& k = MLA512_KERNELS[p.kernel];
+  void (*fn)(MlaArgs) = std::is_same<T, bf16_t>::value ? k.bf16 : k.f16;
+  static std::atomic<uint64_t> attr_set[4];                // per (kernel, device); this function is per dtype
+  if (first_call_on_device(attr_set[p.kernel])) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes);
+  hipLaunchKernelGGL(fn, dim3(a.n_tiles * static_cast<int>(p.head_blocks), a.n_splits), dim3(k.threads), k.lds_bytes, s, a);
+  MOJO_CHECK_LAUNCH("mla512");
+  note_launch("mla512:%s:splits%d", p.tag, a.n_splits);
+  return launch_mla_merge<T>(a, 512, s);
 }
 
-static int mla_splits(int64_t tiles, int64_t max_len) {
-  if (const int v = static_cast<int>(MOJO_SWITCH("MOJO_HIP_MLA_SPLITS", 0)); v >= 1) return v;
-  int64_t sp = 256 / (tiles > 0 ? tiles : 1);
-  const int64_t cap = ceil_div(max_len > 0 ? max_len : 1, 256);
-  if (sp > cap) sp = cap;
-  if (sp < 1) sp = 1;
-  if (sp > 64) sp = 64;
-  return static_cast<int>(sp);
+template <typename T>
+static int dispatch_mla(const MlaArgs& a, const MlaPlan& p, int r, int rope, hipStream_t s) {
+  if (p.kernel >= 0) return launch_mla512<T>(a, p, s);
+  if (p.kernel == MLA_K_LATENT) {
+    if (r == 64) return launch_mla<T, 64, 32>(a, s);
+    if (r == 32) return launch_mla<T, 32, 32>(a, s);
+    if (r == 256) return launch_mla<T, 256, 64>(a, s);
+    return launch_mla<T, 128, 64>(a, s);
+  }
+  MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "mla: (kv_lora_rank, rope) = (%d, %d) not instantiated", r, rope);
 }
 
 }  // namespace mojo
@@ -533,9 +544,7 @@ using namespace mojo;
 
 extern "C" int64_t mojo_hip_mla_latent_attn_workspace_bytes(int64_t q_tokens, int64_t heads, int64_t kv_lora_rank,
                                                             int64_t max_kv_len) {
-  const int sp = mla_splits(q_tokens * (kv_lora_rank == 512 ? (heads + 63) / 64 : 1), max_kv_len);
-  if (sp == 1) return 64;
-  return q_tokens * sp * heads * (kv_lora_rank + 2) * static_cast<int64_t>(sizeof(float)) + 64;
+  return mla_plan(MlaGeom{q_tokens, heads, kv_lora_rank, 0, 0, 0, max_kv_len}).query_bytes;
 }
 
 extern "C" int mojo_hip_mla_latent_attn(const void* q_lat, int64_t q_lat_stride, const void* q_rope,
@@ -566,6 +575,7 @@ extern "C" int mojo_hip_mla_latent_attn(const void* q_lat, int64_t q_lat_stride,
     set_error("mla_latent_attn: memset failed");
     return MOJO_ELAUNCH;
   }
+  const MlaPlan plan = mla_plan(MlaGeom{q_tokens, heads, kv_lora_rank, rope_dim, block_size, max_blocks_per_seq, max_kv_len});
   MlaArgs a;
   a.q_lat = q_lat; a.q_stride = q_lat_stride;
   if (q_rope) { a.q_rope = q_rope; a.q_rope_stride = q_rope_stride; }
@@ -575,14 +585,11 @@ extern "C" int mojo_hip_mla_latent_attn(const void* q_lat, int64_t q_lat_stride,
   a.table_stride = block_table_stride; a.ckv_blk = ckv_block_stride; a.ckv_tok = ckv_token_stride;
   a.kpe_blk = kpe_block_stride; a.kpe_tok = kpe_token_stride;
   a.heads = static_cast<int>(heads); a.page = static_cast<int>(block_size);
-  a.page_shift = (block_size & (block_size - 1)) == 0 ? __builtin_ctzll(block_size) : -1;
+  a.page_shift = mla_page_shift(block_size);
   a.max_pages = static_cast<int>(max_blocks_per_seq); a.batch = static_cast<int>(batch);
   a.n_tiles = static_cast<int>(q_tokens);
-  const int64_t cap = block_size * max_blocks_per_seq;
-  const int64_t max_len = (max_kv_len > 0 && max_kv_len < cap) ? max_kv_len : cap;
-  // the r = 512 kernel runs one workgroup per 64 heads: count those when sizing the split
-  a.n_splits = mla_splits(q_tokens * ((kv_lora_rank == 512 && rope_dim == 64) ? (heads + 63) / 64 : 1), max_len);
-  a.split_keys = static_cast<int>(ceil_div(ceil_div(max_len > 0 ? max_len : 1, a.n_splits), MLA_KEYS) * MLA_KEYS);
+  a.n_splits = plan.n_splits;
+  a.split_keys = plan.split_keys;
   a.scale_log2 = softmax_scale * 1.4426950408889634f;
   a.ps_debug = 0; a.ps_issuers = 2; a.ps_prefetch = 0;
 #ifdef MOJO_HIP_BUILD_EXPERIMENTS           // ablation switches of the `ps` kernel
@@ -591,16 +598,14 @@ extern "C" int mojo_hip_mla_latent_attn(const void* q_lat, int64_t q_lat_stride,
   { const long long e = MOJO_SWITCH("MOJO_HIP_MLA_PS_PREFETCH", 0); a.ps_prefetch = e == 1 ? 1 : e == 2 ? 2 : 0; }
 #endif
   a.part_o = nullptr; a.part_ml = nullptr;
-  if (a.n_splits > 1) {
-    const int64_t slots = q_tokens * a.n_splits * heads;
-    const int64_t need = slots * (kv_lora_rank + 2) * static_cast<int64_t>(sizeof(float));
-    MOJO_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16), MOJO_EWORKSPACE,
-                 "mla_latent_attn: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-    a.part_o = static_cast<float*>(workspace);
-    a.part_ml = a.part_o + slots * kv_lora_rank;
+  if (plan.n_splits > 1) {
+    MOJO_REQUIRE(workspace && workspace_bytes >= plan.need_bytes && aligned_to(workspace, 16), MOJO_EWORKSPACE,
+                 "mla_latent_attn: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)plan.need_bytes);
+    a.part_o = reinterpret_cast<float*>(static_cast<char*>(workspace) + plan.part_o_off);
+    a.part_ml = reinterpret_cast<float*>(static_cast<char*>(workspace) + plan.part_ml_off);
   }
   const int r = static_cast<int>(kv_lora_rank), rope = static_cast<int>(rope_dim);
-  return dtype == MOJO_BF16 ? dispatch_mla<bf16_t>(a, r, rope, s) : dispatch_mla<f16_t>(a, r, rope, s);
+  return dtype == MOJO_BF16 ? dispatch_mla<bf16_t>(a, plan, r, rope, s) : dispatch_mla<f16_t>(a, plan, r, rope, s);
 }
 
 

@@ -34,7 +34,7 @@ import torch
 
 import visibility_mla as M
 from hip_utils import DEV, hip_cls, switch_env
-from visibility_mla import Case
+from visibility_mla import Case, default_splits, split_keys      # (sizes, as the host code computes them)
 
 pytestmark = pytest.mark.gpu
 BF16, F16 = torch.bfloat16, torch.float16
@@ -93,17 +93,6 @@ def ident(v):
     if isinstance(v, dict):
         return ",".join(f"{k[9:] if k.startswith('MOJO_HIP_') else k}={x}" for k, x in v.items()) or "default"
     return v if isinstance(v, str) else None
-
-
-# ---- sizes, as the host code computes them ------------------------------------------------------------------------------
-def default_splits(tokens, heads, r, rope, capacity):
-    """`mla_splits` without the switch: 256 workgroups' worth of splits, at most one per 256 keys of the capacity, 1 .. 64."""
-    tiles = tokens * ((heads + 63) // 64 if (r, rope) == (512, 64) else 1)
-    return max(1, min(256 // max(tiles, 1), -(-capacity // 256), 64))
-
-
-def split_keys(capacity, splits):
-    return -(-(-(-capacity // splits)) // 64) * 64
 
 
 def decode_lens(split, capacity=CAPACITY):

@@ -41,6 +41,17 @@ FAILURES_LISTED = 64
 SINK_ON, SINK_OFF = 0.0, -30000.0    # even / odd heads
 
 
+# ---- sizes, as the host code computes them (csrc/mla_attn.hip: mla_plan) ------------------------------------------------
+def default_splits(tokens, heads, r, rope, capacity):
+    """`mla_splits` without the switch: 256 workgroups' worth of splits, at most one per 256 keys of the capacity, 1 .. 64."""
+    tiles = tokens * ((heads + 63) // 64 if (r, rope) == (512, 64) else 1)
+    return max(1, min(256 // max(tiles, 1), -(-capacity // 256), 64))
+
+
+def split_keys(capacity, splits):
+    return -(-(-(-capacity // splits)) // 64) * 64
+
+
 @dataclass(frozen=True)
 class Case:
     """One geometry.  ``kind``: "decode" (one row per sequence, ``[B, H, nope + rope]``) or "prefill" (``q_lens[b]`` rows, packed,
