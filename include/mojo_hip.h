@@ -797,6 +797,37 @@ int mojo_hip_reject_sampling(const void* target_probs, const int64_t* draft_toke
                              const float* uniforms, int64_t* next_tokens, void* accepted_len, int64_t batch,
                              int64_t steps, int64_t vocab, int joint, int dtype, mojo_stream_t stream);
 
+/* ---- The DiT block ops (DIT_BLOCK_OPS: MojoLayerNorm, MojoResidualAddLayerNorm, MojoGelu, MojoSilu, MojoGridRoPE).
+ *      layernorm (core/operators/normalization.py:19-68, :365-432): s = hidden [+ residual, rounded to the input dtype;
+ *      residual nullable]; mean = sum(s) / dim in fp32 over the row held in registers; var = mean((s - mean)^2), never
+ *      E[s^2] - mean^2; rstd = rsqrt(var + eps); normed = round_T(fma((s - mean) * rstd, weight, bias)), or
+ *      round_T((s - mean) * rstd) when weight and bias are NULL (both given or both NULL, in the activation dtype).
+ *      sum_out (nullable, norm_pos = "pre") receives s.  hidden / residual rows are row_stride elements apart (>= dim, the
+ *      last dimension dense); normed_out and sum_out are dense [rows, dim].  dtype in {f32, f16, bf16}.  Launch tags are
+ *      `layernorm:vec<V>:tpr<64|128|256>:<cached|reread>:<nt|plain>`.  V is the widest of {16 bytes, 2 elements, 1 element}
+ *      that dim, the row strides and every pointer allow; threads per row follow the RMSNorm kernels (64 up to 256
+ *      vectors, 128 up to 512, else 256; with rows <= 128 the 16-byte form takes 256 from 256 vectors on).  A thread keeps
+ *      layernorm_cache_vectors() vectors of its row in registers: rows of more than tpr x that many vectors (only tpr256
+ *      has such) re-read their tail in the second and third pass (`reread`).
+ *      activation: out[i] = round_T(f(float(in[i]))), one rounding; kind 0 = GELU in the erf form
+ *      x * 0.5 * (1 + erff(x * sqrt(1/2))), kind 1 = SiLU x / (1 + expf(-x)).  in and out dense, out may be in.  16-byte
+ *      vectors when both pointers allow (tag `activation:<gelu_erf|silu>:vec<V>:<nt|plain>`, V = 1 otherwise), a scalar tail.
+ *      grid_rope (experimental/operators/position_embedding.py:80-118): x [batch, tokens, heads, head_dim] read through
+ *      x_strides (batch, token, head; elements; the last dimension dense), out dense.  Token t of sample i is rotated iff
+ *      t < F_i * H_i * W_i (grid_sizes [batch, 3], int32 or int64, ON THE DEVICE) and t < that sample's frequency rows;
+ *      every other token is copied.  freqs is fp32 [rows, head_dim / 2, 2] = (cos, sin) interleaved (a complex64 tensor
+ *      seen through view_as_real).  freq_table NULL: every sample reads rows [0, shared_freq_rows); else an int64
+ *      [batch, 2] device table of (first row, row count) per sample.  Adjacent pairs (a, b) = (x[2j], x[2j + 1]):
+ *      re = a * c - b * s, im = a * s + b * c, each product and sum rounded on its own in fp32, one rounding to T.      */
+int64_t mojo_hip_layernorm_cache_vectors(void);
+int mojo_hip_layernorm(const void* hidden, const void* residual, const void* weight, const void* bias,
+                       void* normed_out, void* sum_out, int64_t rows, int64_t dim, int64_t hidden_row_stride,
+                       int64_t residual_row_stride, int dtype, float eps, mojo_stream_t stream);
+int mojo_hip_activation(const void* in, void* out, int64_t n, int kind, int dtype, mojo_stream_t stream);
+int mojo_hip_grid_rope(const void* x, void* out, const float* freqs, const void* grid_sizes, int grid_sizes_is_i64,
+                       const int64_t* freq_table, int64_t shared_freq_rows, int64_t batch, int64_t tokens,
+                       int64_t heads, int64_t head_dim, const int64_t x_strides[3], int dtype, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,10 @@ SIGNATURES = {
     "mojo_hip_sample_with_uniforms": (c_int, [_P, _P, _P, _P, _I, _I, _I, c_int, c_float, _I, c_float, _I, c_int, _P, _I, _P]),
     "mojo_hip_apply_penalties": (c_int, [_P, _P, _P, _I, _I, c_int, c_int, _P]),
     "mojo_hip_reject_sampling": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, c_int, c_int, _P]),
+    "mojo_hip_layernorm_cache_vectors": (c_int64, []),
+    "mojo_hip_layernorm": (c_int, [_P] * 6 + [_I] * 4 + [c_int, c_float, _P]),
+    "mojo_hip_activation": (c_int, [_P, _P, _I, c_int, c_int, _P]),
+    "mojo_hip_grid_rope": (c_int, [_P, _P, _P, _P, c_int, _P, _I, _I, _I, _I, _I, _I64x3, c_int, _P]),
 }
 
 _lock = threading.Lock()

@@ -1,15 +1,16 @@
 """HIP<Op> classes of the HBM-streaming operators: SwiGLU, (ResidualAdd)RMSNorm, RoPE,
-RotaryEmbedding, StorePagedKVCache.  Each `forward` validates the reference's contract, hands raw
+RotaryEmbedding, StorePagedKVCache, and the DiT block's (ResidualAdd)LayerNorm, Gelu, Silu and GridRoPE.  Each `forward` validates the reference's contract, hands raw
 device pointers to the C ABI and returns torch tensors; there is no torch compute in here."""
 from typing import Optional
 
 import torch
 
-from ....core.operators.activation import MojoSwiGLU
+from ....core.operators.activation import MojoGelu, MojoSilu, MojoSwiGLU
 from ....core.operators.kv_cache import (MojoStorePagedKVCache, MojoStorePagedMLAKVCache,
                                            assert_paged_kv_layout_contract)
-from ....core.operators.normalization import MojoResidualAddRMSNorm, MojoRMSNorm, MojoRMSNormInplace
-from ....core.operators.position_embedding import MojoApplyRoPE, MojoRotaryEmbedding
+from ....core.operators.normalization import (MojoLayerNorm, MojoResidualAddLayerNorm, MojoResidualAddRMSNorm, MojoRMSNorm,
+                                                MojoRMSNormInplace)
+from ....core.operators.position_embedding import MojoApplyRoPE, MojoGridRoPE, MojoRotaryEmbedding
 from .. import lib as L
 
 _ROCM = ["rocm"]
@@ -112,6 +113,165 @@ class HIPResidualAddRMSNorm(MojoResidualAddRMSNorm):
         pre = self.norm_pos == "pre"
         normed, summed = _rmsnorm(hidden_state, residual, self.weight, self.variance_epsilon, pre)
         return (normed, summed) if pre else (normed, normed)
+
+
+_FLOATS = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _require_float(what: str, t: torch.Tensor) -> None:
+    """fp32 / fp16 / bf16 or a refusal that names the dtype: an integer tensor (or fp64) is never cast behind the caller's back."""
+    if not t.is_floating_point():
+        raise NotImplementedError(f"{what}: integer input of dtype {t.dtype}; the op is defined on floating-point tensors")
+    if t.dtype not in _FLOATS:
+        raise NotImplementedError(f"{what}: dtype {t.dtype} is not supported (fp32, fp16, bf16)")
+
+
+def _layernorm(what, hidden, residual, weight, bias, eps, want_sum):
+    """(normed, sum or None).  ``hidden`` / ``residual`` whose last dimension is dense and whose leading dimensions collapse to
+    one row stride (a column slice of a wider tensor) are read in place; anything else is made dense first."""
+    _require_float(what, hidden)
+    dim = hidden.shape[-1] if hidden.dim() else 0
+    if hidden.dim() == 0:
+        raise ValueError(f"{what}: hidden_state needs a last dimension to normalise over")
+    if residual is not None and (residual.dtype != hidden.dtype or residual.shape != hidden.shape):
+        raise NotImplementedError(f"{what}: hidden_state and residual must share one shape and dtype")
+    if (weight is None) != (bias is None):
+        raise NotImplementedError(f"{what}: weight and bias come together or not at all")
+    if weight is not None:
+        if weight.dtype != hidden.dtype or bias.dtype != hidden.dtype:
+            raise NotImplementedError(f"{what}: weight and bias ({weight.dtype}, {bias.dtype}) must have the activation dtype {hidden.dtype}")
+        if tuple(weight.shape) != (dim,) or tuple(bias.shape) != (dim,):
+            raise ValueError(f"{what}: weight length {tuple(weight.shape)} / bias length {tuple(bias.shape)} do not match the hidden size {dim}")
+    L.require_cuda(hidden, residual, weight, bias)
+    normed = torch.empty(hidden.shape, dtype=hidden.dtype, device=hidden.device)
+    summed = torch.empty_like(normed) if want_sum else None
+    if hidden.numel() == 0:                                   # rows == 0 (or dim == 0): nothing to launch
+        return normed, summed
+    rows_h = _row_view(hidden)
+    if rows_h is None or rows_h[1] < dim:                     # (a row stride below dim: an expanded tensor)
+        hidden = hidden.contiguous()
+        rows_h = _row_view(hidden)
+    rows_r = None
+    if residual is not None:
+        rows_r = _row_view(residual)
+        if rows_r is None or rows_r[1] < dim:
+            residual = residual.contiguous()
+            rows_r = _row_view(residual)
+    w = None if weight is None else _dense(weight.detach())
+    b = None if bias is None else _dense(bias.detach())
+    L.check(L.load().mojo_hip_layernorm(L.ptr(hidden), L.ptr(residual), L.ptr(w), L.ptr(b), L.ptr(normed), L.ptr(summed), rows_h[0], dim,
+                                        rows_h[1], rows_r[1] if rows_r else 0, L.dtype_code(hidden.dtype), float(eps),
+                                        L.stream_of(hidden)), what)
+    return normed, summed
+
+
+class HIPLayerNorm(MojoLayerNorm):
+    supported_platforms_list = _ROCM
+
+    def forward(self, hidden_state: torch.Tensor) -> torch.Tensor:
+        return _layernorm("HIPLayerNorm", hidden_state, None, self.weight, self.bias, self.variance_epsilon, False)[0]
+
+
+class HIPResidualAddLayerNorm(MojoResidualAddLayerNorm):
+    supported_platforms_list = _ROCM
+
+    def forward(self, hidden_state: torch.Tensor, residual: torch.Tensor):
+        pre = self.norm_pos == "pre"
+        normed, summed = _layernorm("HIPResidualAddLayerNorm", hidden_state, residual, self.weight, self.bias, self.variance_epsilon, pre)
+        return (normed, summed) if pre else (normed, normed)
+
+
+ACT_GELU_ERF, ACT_SILU = 0, 1                 # `kind` of mojo_hip_activation
+
+
+def _activation(what, x, kind, out=None):
+    """``out`` (dense, the shape and dtype of ``x``) may be ``x`` itself.  A non-contiguous ``x`` is copied once, to a dense
+    tensor, before the kernel reads it: an elementwise pass has no stride pattern worth a kernel form of its own."""
+    _require_float(what, x)
+    L.require_cuda(x, out)
+    if out is None:
+        x = _dense(x)
+        out = torch.empty_like(x)
+    elif not (x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype):
+        raise NotImplementedError(f"{what}: an explicit output needs dense x and out of one shape and dtype")
+    if x.numel():
+        L.check(L.load().mojo_hip_activation(L.ptr(x), L.ptr(out), x.numel(), kind, L.dtype_code(x.dtype), L.stream_of(x)), what)
+    return out
+
+
+class HIPGelu(MojoGelu):
+    """The erf form.  A non-contiguous input is copied once in Python (`_activation`)."""
+
+    supported_platforms_list = _ROCM
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return _activation("HIPGelu", x, ACT_GELU_ERF)
+
+
+class HIPSilu(MojoSilu):
+    """A non-contiguous input is copied once in Python (`_activation`)."""
+
+    supported_platforms_list = _ROCM
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return _activation("HIPSilu", x, ACT_SILU)
+
+
+class HIPGridRoPE(MojoGridRoPE):
+    """``x`` is read in place through its strides (the last dimension dense, the others even: a slice of a fused QKV buffer
+    is), the complex64 frequencies through ``view_as_real`` without a copy.  ``freqs_list`` entries that are all one tensor
+    are passed as one pointer; distinct entries are packed into one buffer per call.
+
+    ``grid_sizes`` on the CPU is checked here (a grid with more cells than ``L`` or than its frequency entry has rows raises,
+    as the golden's reshape and broadcast do) and copied to the device; ``grid_sizes`` on the device is read by the kernel,
+    with no host synchronisation, and then a grid larger than its entry is the caller's error: the kernel rotates the tokens
+    the entry has rows for, copies the rest, and never reads past an entry."""
+
+    supported_platforms_list = _ROCM
+
+    def forward(self, x: torch.Tensor, grid_sizes: torch.Tensor, freqs_list):
+        self.check_shape_contract(x, grid_sizes, freqs_list)
+        _require_float("HIPGridRoPE", x)
+        if grid_sizes.is_floating_point() or grid_sizes.dtype == torch.bool:
+            raise NotImplementedError(f"HIPGridRoPE: grid_sizes must be an integer tensor, got {grid_sizes.dtype}")
+        batch, tokens, heads, dim = x.shape
+        half = dim // 2
+        freqs = list(freqs_list[:batch])
+        rows = []
+        for i, f in enumerate(freqs):
+            if f.dtype != torch.complex64:
+                raise NotImplementedError(f"HIPGridRoPE: freqs_list[{i}] is {f.dtype}; the frequencies must be complex64")
+            if half and (f.dim() == 0 or f.shape[-1] != half or f.numel() % half or f.numel() // half != f.shape[0]):
+                raise ValueError(f"HIPGridRoPE: freqs_list[{i}] of shape {tuple(f.shape)} is not [seq_len, 1, {half}]")
+            rows.append(f.shape[0] if f.dim() else 0)
+        if not grid_sizes.is_cuda:
+            for i, (gf, gh, gw) in enumerate(grid_sizes.tolist()):
+                cells = gf * gh * gw
+                if cells > tokens or cells > rows[i]:
+                    raise ValueError(f"HIPGridRoPE: grid {(gf, gh, gw)} of sample {i} has {cells} cells, more than the {tokens} tokens "
+                                     f"of x or the {rows[i]} rows of freqs_list[{i}]")
+        L.require_cuda(x, *freqs)
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        if x.numel() == 0:
+            return out
+        elt_pair = 2 * x.element_size()
+        if x.stride(-1) != 1 or any(st % 2 for st in x.stride()[:3]) or x.data_ptr() % elt_pair:
+            x = x.contiguous()
+        grid = grid_sizes if grid_sizes.dtype in (torch.int32, torch.int64) else grid_sizes.to(torch.int64)
+        grid = _dense(grid.to(x.device))
+        first = freqs[0]
+        if all(f is first or (f.data_ptr() == first.data_ptr() and f.shape == first.shape and f.stride() == first.stride()) for f in freqs):
+            table, shared_rows = None, rows[0]
+            packed = torch.view_as_real(_dense(first))
+        else:
+            starts = [sum(rows[:i]) for i in range(batch)]
+            table = torch.tensor([[s0, r] for s0, r in zip(starts, rows)], dtype=torch.int64).to(x.device)
+            shared_rows = 0
+            packed = torch.cat([torch.view_as_real(_dense(f)).reshape(r, dim) for f, r in zip(freqs, rows)])
+        L.check(L.load().mojo_hip_grid_rope(L.ptr(x), L.ptr(out), L.ptr(packed), L.ptr(grid), int(grid.dtype == torch.int64), L.ptr(table),
+                                            shared_rows, batch, tokens, heads, dim, L.strides3(*x.stride()[:3]), L.dtype_code(x.dtype),
+                                            L.stream_of(x)), "HIPGridRoPE")
+        return out
 
 
 class HIPApplyRoPE(MojoApplyRoPE):

@@ -1,4 +1,4 @@
-from .activation import MojoSwiGLU
+from .activation import MojoGelu, MojoSilu, MojoSwiGLU
 from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
                         MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
                         MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
@@ -10,8 +10,9 @@ from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStore
 from .mla import MojoPagedDecodeMLA, MojoPagedPrefillMLA
 from .mlp import MojoSwiGLUMLP
 from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts, MojoQuantMoE
-from .normalization import MojoResidualAddRMSNorm, MojoRMSNorm, MojoRMSNormInplace
-from .position_embedding import MojoApplyRoPE, MojoRotaryEmbedding
+from .normalization import (MojoLayerNorm, MojoResidualAddLayerNorm, MojoResidualAddRMSNorm, MojoRMSNorm,
+                            MojoRMSNormInplace)
+from .position_embedding import MojoApplyRoPE, MojoGridRoPE, MojoRotaryEmbedding
 from .quantize import (MojoDequant, MojoDequantSwiGLUQuant, MojoDynamicQuant, MojoLayerNormQuant, MojoMoEDynamicQuant,
                        MojoResidualAddLayerNormQuant, MojoResidualAddRMSNormQuant, MojoRMSNormQuant, MojoStaticQuant)
 from .sampling import (MojoApplyPenaltiesTempurate, MojoJoinProbRejectSampling, MojoRejectSampling, MojoTopKSampling,
@@ -55,3 +56,6 @@ FULL_ATTN_OPS = ("MojoSdpa",)
 # stage.  A set of its own likewise (golden: tests/quant_dense_golden.py)
 QUANT_DENSE_OPS = ("MojoRMSNormQuant", "MojoLayerNormQuant", "MojoResidualAddLayerNormQuant", "MojoStaticQuant", "MojoDequant",
                    "MojoDequantSwiGLUQuant")
+# the ops around every `MojoSdpa` of a DiT block (Wan2.2): LayerNorm with and without affine, the FFN's GELU, the time
+# embedding's SiLU and the 3-D grid RoPE of q and k.  A set of its own likewise (golden: tests/dit_block_golden.py)
+DIT_BLOCK_OPS = ("MojoLayerNorm", "MojoResidualAddLayerNorm", "MojoGelu", "MojoSilu", "MojoGridRoPE")

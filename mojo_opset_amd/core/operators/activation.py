@@ -1,4 +1,5 @@
-"""API class `MojoSwiGLU` (`mojo_opset/core/operators/activation.py:38-66`)."""
+"""API class `MojoSwiGLU` (`mojo_opset/core/operators/activation.py:38-66`) and the elementwise `MojoGelu` /
+`MojoSilu` (``DIT_BLOCK_OPS``; :6-35)."""
 from ..operator import MojoOperator
 
 
@@ -14,3 +15,11 @@ class MojoSwiGLU(MojoOperator):
 
     def extra_repr(self) -> str:
         return f"swiglu_limit={self.swiglu_limit!r}"
+
+
+class MojoGelu(MojoOperator):
+    """forward(x) -> gelu(x) in the erf form (torch's default, not the tanh approximation); any shape, same dtype."""
+
+
+class MojoSilu(MojoOperator):
+    """forward(x) -> x * sigmoid(x); any shape, same dtype."""

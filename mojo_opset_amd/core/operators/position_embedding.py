@@ -3,7 +3,8 @@
 Follows `mojo_opset/core/operators/position_embedding.py:9-175`.  ``inv_freq`` and the optional
 ``cos``/``sin`` cache are non-persistent buffers with the reference's names, computed in fp32.
 The tables are computed once on the host and then moved to the factory device, so the cached
-gather path is bit-identical to the CPU golden regardless of the device's libm.
+gather path is bit-identical to the CPU golden regardless of the device's libm.  `MojoGridRoPE` (``DIT_BLOCK_OPS``) follows
+`mojo_opset/experimental/operators/position_embedding.py:80-118`.
 """
 from typing import Optional
 
@@ -95,3 +96,19 @@ class MojoApplyRoPE(MojoOperator):
 
     def extra_repr(self) -> str:
         return f"interleaved={self.interleaved!r}"
+
+
+class MojoGridRoPE(MojoOperator):
+    """forward(x [B, L, N, D], grid_sizes [B, 3], freqs_list) -> x with the first ``F_i * H_i * W_i`` tokens of sample ``i``
+    rotated pair by pair, ``(x[2j] + i x[2j+1]) * freqs_list[i][t, 0, j]``, and the padding tokens behind them unchanged.
+    ``freqs_list[i]`` is a complex64 ``[F_i * H_i * W_i, 1, D / 2]`` of unit phases; D is even."""
+
+    def __init__(self):
+        super().__init__()
+
+    @staticmethod
+    def check_shape_contract(x, grid_sizes, freqs_list) -> None:
+        assert x.dim() == 4, "x must be 4D: [B, L, N, D]"
+        assert x.size(-1) % 2 == 0, "D must be even for complex pairing"
+        assert grid_sizes.dim() == 2 and grid_sizes.size(1) == 3, "grid_sizes must be [B, 3]"
+        assert grid_sizes.size(0) == x.size(0) and len(freqs_list) >= x.size(0), "one grid and one frequency tensor per sample"
