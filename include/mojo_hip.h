@@ -828,6 +828,52 @@ int mojo_hip_grid_rope(const void* x, void* out, const float* freqs, const void*
                        const int64_t* freq_table, int64_t shared_freq_rows, int64_t batch, int64_t tokens,
                        int64_t heads, int64_t head_dim, const int64_t x_strides[3], int dtype, mojo_stream_t stream);
 
+/* ---- The vision-tower ops (VISION_TOWER_OPS: MojoPackedSdpa, MojoVisionRotaryEmbedding2D, MojoApplyVisionRoPE2D, MojoMRoPE,
+ *      MojoMRoPEInplace).
+ *      packed_sdpa: the semantics of MojoSWA(is_causal=False) (core/operators/attention.py:747-835): the arguments of
+ *      mojo_hip_swa_packed without the windows, and no causal edge — every query row of sequence b sees every key of
+ *      [cu_total_seq_lens[b], cu_total_seq_lens[b + 1]).  q_len and kv_len of a sequence are independent (kv_len < q_len is
+ *      legal).  The kernel is the prefill's with the walk of mojo_hip_sdpa: the same bits as mojo_hip_sdpa on the same tokens
+ *      at the same key split.  Hints, workspace and key split as mojo_hip_swa_packed; a sequence longer than max_q_len_hint
+ *      has its rows past the hint written as zeros, and keys at or past max_kv_len_hint are not seen.  Rows of sequences
+ *      without keys and rows at or past cu_q_lens[batch] are zeros.  Every cu_total_seq_lens entry is clamped to
+ *      [0, total_kv_tokens] by the kernel: no read leaves the tensors.  Launch tags `packed_sdpa:default:<fast_stage|
+ *      general_stage>:ksplit<n>`.
+ *      (MojoApplyVisionRoPE2D, core/operators/position_embedding.py:366-407, is mojo_hip_apply_rope with rope_dim = head_dim
+ *      on token-first tensors: the same fp32 products and sum, bit for bit.)
+ *      vision_rotary_2d (core/operators/position_embedding.py:281-363): cos_out / sin_out fp32 [tokens][rope_dim] dense.
+ *      samples: int64 [batch][3] ON THE DEVICE, (first row, H, W) per image, first rows ascending from 0 and
+ *      first + H * W <= tokens; H and W multiples of adapooling_factor.  Token i of a sample sits at
+ *      (h, w) = (bh * f + ih, bw * f + iw) with (bh, bw) the f x f window i / f^2 in row-major window order and (ih, iw)
+ *      the patch i % f^2 inside it.  Row = [h * inv_freq | w * inv_freq] twice (inv_freq: fp32 [rope_dim / 4]); each angle is
+ *      one fp32 product, then cosf / sinf.  Tag `vision_rotary_2d:pool<f>`.
+ *      mrope (core/operators/position_embedding.py:178-278, experimental/operators/position_embedding.py:121-236): query
+ *      [tokens][q_heads * head_dim] and key [tokens][k_heads * head_dim] by a row stride in elements; half = sum of
+ *      mrope_section (host array of 3), 2 * half <= head_dim.  out[i] = h1 * c - h2 * s, out[half + i] = h2 * c + h1 * s,
+ *      each product and the sum rounded on their own in fp32, one rounding to dtype.  In place when query_out == query and
+ *      key_out == key (elements at or past 2 * half are not touched); otherwise both outputs are distinct tensors and those
+ *      elements are copied.  Tables (table_dtype f32 / f16 / bf16, converted on read) are [3][tokens][half] addressed by
+ *      table_section_stride / table_token_stride, or one merged [tokens][half] table with table_section_stride = 0; the
+ *      kernel picks the table per element: chunked (is_interleaved = 0): 0 / 1 / 2 by the section i falls in; interleaved:
+ *      1 where i % 3 == 1 and i < 3 * section[1], 2 where i % 3 == 2 and i < 3 * section[2], else 0.  Tags
+ *      `mrope:vec<V>:<inplace|copy>:<merged|chunked|interleaved>`.  No host sync.                                        */
+int64_t mojo_hip_packed_sdpa_workspace_bytes(int64_t total_q_tokens, int64_t total_kv_tokens, int64_t batch,
+                                             int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                                             int64_t max_q_len_hint, int64_t max_kv_len_hint);
+int mojo_hip_packed_sdpa(const void* query, const void* key, const void* value, const int32_t* cu_q_lens,
+                         const int32_t* cu_total_seq_lens, void* out, int64_t total_q_tokens,
+                         int64_t total_kv_tokens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                         int64_t kv_token_stride, int64_t kv_head_stride, int64_t max_q_len_hint,
+                         int64_t max_kv_len_hint, float softmax_scale, int layout_abab, int dtype, void* workspace,
+                         int64_t workspace_bytes, mojo_stream_t stream);
+int mojo_hip_vision_rotary_2d(float* cos_out, float* sin_out, const int64_t* samples, int64_t batch, int64_t tokens,
+                              int64_t rope_dim, int64_t adapooling_factor, const float* inv_freq, mojo_stream_t stream);
+int mojo_hip_mrope(const void* query, const void* key, void* query_out, void* key_out, const void* cos_table,
+                   const void* sin_table, int64_t tokens, int64_t q_heads, int64_t k_heads, int64_t head_dim,
+                   int64_t q_row_stride, int64_t k_row_stride, int64_t qo_row_stride, int64_t ko_row_stride,
+                   int64_t table_section_stride, int64_t table_token_stride, const int64_t mrope_section[3],
+                   int is_interleaved, int table_dtype, int dtype, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

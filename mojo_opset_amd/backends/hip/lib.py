@@ -141,6 +141,10 @@ SIGNATURES = {
     "mojo_hip_layernorm": (c_int, [_P] * 6 + [_I] * 4 + [c_int, c_float, _P]),
     "mojo_hip_activation": (c_int, [_P, _P, _I, c_int, c_int, _P]),
     "mojo_hip_grid_rope": (c_int, [_P, _P, _P, _P, c_int, _P, _I, _I, _I, _I, _I, _I64x3, c_int, _P]),
+    "mojo_hip_packed_sdpa_workspace_bytes": (c_int64, [_I] * 8),
+    "mojo_hip_packed_sdpa": (c_int, [_P] * 6 + [_I] * 10 + [c_float, c_int, c_int, _P, _I, _P]),
+    "mojo_hip_vision_rotary_2d": (c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "mojo_hip_mrope": (c_int, [_P] * 6 + [_I] * 10 + [_I64x3, c_int, c_int, c_int, _P]),
 }
 
 _lock = threading.Lock()

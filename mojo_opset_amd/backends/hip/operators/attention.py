@@ -5,7 +5,8 @@ from typing import Optional
 import torch
 
 from ....core.operators.attention import (MojoPagedDecodeGQA, MojoPagedDecodeNstepSWA, MojoPagedDecodeSWA,
-                                          MojoPagedPrefillGQA, MojoPagedPrefillSWA, MojoSdpa, MojoSWA, assert_nstep_query,
+                                          MojoPackedSdpa, MojoPagedPrefillGQA, MojoPagedPrefillSWA, MojoSdpa, MojoSWA,
+                                          assert_nstep_query,
                                           assert_paged_decode_contract, assert_paged_prefill_contract,
                                           assert_swa_packed_contract)
 from .... import switches
@@ -127,6 +128,7 @@ _PREFILL_GQA = ("mojo_hip_paged_prefill_gqa_workspace_bytes", "mojo_hip_paged_pr
 _PREFILL_SWA = ("mojo_hip_paged_prefill_swa_workspace_bytes", "mojo_hip_paged_prefill_swa")
 _SWA_PACKED = ("mojo_hip_swa_packed_workspace_bytes", "mojo_hip_swa_packed")
 _SDPA = ("mojo_hip_sdpa_workspace_bytes", "mojo_hip_sdpa")
+_PACKED_SDPA = ("mojo_hip_packed_sdpa_workspace_bytes", "mojo_hip_packed_sdpa")
 
 
 class HIPPagedDecodeGQA(MojoPagedDecodeGQA):
@@ -439,3 +441,63 @@ class HIPSdpa(MojoSdpa):
             k.stride(0), k.stride(1), k.stride(2), kind, *m_strides, scale, L.dtype_code(q.dtype),
             L.ptr(ws), ws_bytes, L.stream_of(q)), what)
         return out[0] if squeeze else out
+
+
+class HIPPackedSdpa(MojoPackedSdpa):
+    """Packed var-len bidirectional attention: the linear prefill kernel of `HIPSWA` with the walk of `HIPSdpa`
+    — no offset, every whole key tile on the unmasked fast-staged loop, only a sequence's tail tile masked.  One packed
+    sequence of ``Sq x Sk`` gives the bits of `HIPSdpa` on the same tokens at the same key split.
+
+    K and V are read in place under the rule of `_kv_in_place` (views into a fused QKV buffer qualify); otherwise both are
+    made contiguous.  Both GQA layouts.  Envelope: bf16 / fp16, ``head_dim`` 64 / 96 / 128, ``Hq / Hkv`` 1 / 2 / 4 / 8; anything
+    else raises ``NotImplementedError`` (``head_dim`` 72 / 80 is the caller's padding to 96).  No host sync, capture-safe.
+
+    Contract: ``cu_q_lens[0] == 0``; ``cu_total_seq_lens[0]`` may be positive; ``q_len`` and ``kv_len`` of a sequence are
+    independent.  Beyond the reference: rows of a sequence with ``kv_len <= 0`` and rows at or past ``cu_q_lens[-1]`` are
+    zeros.  ``max_q_len`` / ``max_total_seq_len`` are upper-bound hints: a sequence longer than ``max_q_len`` has its rows past
+    the hint written as zeros, and keys at or past ``max_total_seq_len`` of a sequence are not seen.  ``MOJO_HIP_VALIDATE=1``
+    (a host sync) raises ``ValueError`` for arrays that decrease, ends past ``Tq`` / ``Tk`` and a length above its hint.
+    Without it every ``cu_total_seq_lens`` entry is clamped to ``[0, Tk]`` by the kernel, so no read leaves the tensors."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key, value, cu_q_lens, cu_total_seq_lens, softmax_scale: Optional[float] = None, *,
+                max_q_len: Optional[int] = None, max_total_seq_len: Optional[int] = None):
+        what = "HIPPackedSdpa"
+        assert_swa_packed_contract(query, key, value, cu_q_lens, cu_total_seq_lens)
+        tokens, hq, dim = query.shape
+        kv_tokens, hkv = key.shape[:2]
+        if query.dtype not in (torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"{what}: dtype {query.dtype} (bf16 / fp16)")
+        if dim not in _SDPA_DIMS:
+            raise NotImplementedError(f"{what}: head_dim {dim} {_SDPA_DIMS}")
+        if hq // hkv not in _SDPA_GROUPS:
+            raise NotImplementedError(f"{what}: {hq // hkv} query heads per kv head {_SDPA_GROUPS}")
+        L.require_cuda(query, key, value, cu_q_lens, cu_total_seq_lens)
+        batch = cu_q_lens.shape[0] - 1
+        hint_q = int(max_q_len) if max_q_len else 0
+        hint_kv = int(max_total_seq_len) if max_total_seq_len else 0
+        if _validate_tables() and batch > 0:
+            q_lens, kv_lens = cu_q_lens[1:] - cu_q_lens[:-1], cu_total_seq_lens[1:] - cu_total_seq_lens[:-1]
+            if int(cu_q_lens[0]) != 0 or int(cu_total_seq_lens[0]) < 0 or bool((q_lens < 0).any()) or bool((kv_lens < 0).any()):
+                raise ValueError(f"{what}: cu_q_lens must start at 0 and both cumulative arrays must be non-decreasing")
+            if int(cu_q_lens[-1]) > tokens or int(cu_total_seq_lens[-1]) > kv_tokens:
+                raise ValueError(f"{what}: the cumulative lengths end past the query ({tokens}) or key ({kv_tokens}) tokens")
+            if (hint_q and int(q_lens.max()) > hint_q) or (hint_kv and int(kv_lens.max()) > hint_kv):
+                raise ValueError(f"{what}: a sequence's length exceeds its max_q_len / max_total_seq_len hint")
+        q = query if query.is_contiguous() else query.contiguous()
+        if tokens == 0:
+            return torch.empty_like(q)
+        if kv_tokens == 0:                                 # no key anywhere: every row reads as zeros
+            return torch.zeros_like(q)
+        k, v = (key, value) if _kv_in_place(key, value) else (key.contiguous(), value.contiguous())
+        cu_q, cu_kv = cu_q_lens.contiguous(), cu_total_seq_lens.contiguous()
+        scale = 1.0 / math.sqrt(dim) if softmax_scale is None else float(softmax_scale)
+        out = torch.empty_like(q)
+        lib = L.load()
+        ws_bytes = getattr(lib, _PACKED_SDPA[0])(tokens, kv_tokens, batch, hq, hkv, dim, hint_q, hint_kv)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes > 0 else None
+        L.check(getattr(lib, _PACKED_SDPA[1])(
+            L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(cu_q), L.ptr(cu_kv), L.ptr(out), tokens, kv_tokens, batch, hq, hkv, dim,
+            k.stride(0), k.stride(1), hint_q, hint_kv, scale, 1 if self.gqa_layout == "ABAB" else 0,
+            L.dtype_code(q.dtype), L.ptr(ws), ws_bytes, L.stream_of(q)), what)
+        return out

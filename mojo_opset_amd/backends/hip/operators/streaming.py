@@ -1,5 +1,6 @@
 """HIP<Op> classes of the HBM-streaming operators: SwiGLU, (ResidualAdd)RMSNorm, RoPE,
-RotaryEmbedding, StorePagedKVCache, and the DiT block's (ResidualAdd)LayerNorm, Gelu, Silu and GridRoPE.  Each `forward` validates the reference's contract, hands raw
+RotaryEmbedding, StorePagedKVCache, the DiT block's (ResidualAdd)LayerNorm, Gelu, Silu and GridRoPE, and the vision tower's
+VisionRotaryEmbedding2D, ApplyVisionRoPE2D and MRoPE(Inplace).  Each `forward` validates the reference's contract, hands raw
 device pointers to the C ABI and returns torch tensors; there is no torch compute in here."""
 from typing import Optional
 
@@ -10,7 +11,9 @@ from ....core.operators.kv_cache import (MojoStorePagedKVCache, MojoStorePagedML
                                            assert_paged_kv_layout_contract)
 from ....core.operators.normalization import (MojoLayerNorm, MojoResidualAddLayerNorm, MojoResidualAddRMSNorm, MojoRMSNorm,
                                                 MojoRMSNormInplace)
-from ....core.operators.position_embedding import MojoApplyRoPE, MojoGridRoPE, MojoRotaryEmbedding
+from ....core.operators.position_embedding import (MojoApplyRoPE, MojoApplyVisionRoPE2D, MojoGridRoPE, MojoMRoPE,
+                                                     MojoMRoPEInplace, MojoRotaryEmbedding, MojoVisionRotaryEmbedding2D,
+                                                     check_mrope_contract)
 from .. import lib as L
 
 _ROCM = ["rocm"]
@@ -429,3 +432,129 @@ class HIPStorePagedMLAKVCache(MojoStorePagedMLAKVCache):
             compressed_kv_cache.stride(0), compressed_kv_cache.stride(2), k_pe_cache.stride(0), k_pe_cache.stride(2),
             L.stream_of(compressed_kv_cache)), "HIPStorePagedMLAKVCache")
         return compressed_kv_cache, k_pe_cache
+
+
+class HIPVisionRotaryEmbedding2D(MojoVisionRotaryEmbedding2D):
+    """One launch computes every token's ``(h, w)`` position under the adapooling regrouping from its index and writes its
+    ``(cos, sin)`` row, where the reference loops over the samples on the host and gathers from a
+    ``max_grid x rope_dim / 4`` table.  The angle is the fp32 product ``pos * inv_freq[i]``, rounded once as the golden's
+    ``outer`` rounds it; cos and sin are the device's ``cosf`` / ``sinf``.
+
+    Not capture-safe: the output size ``sum(h * w)`` is a host quantity, so ``grid_hw`` is read on the host once (the
+    reference's contract contains the same read).  The outputs live on the device of ``inv_freq``."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, grid_hw: torch.Tensor):
+        grids = self.check_grid_contract(grid_hw, self.adapooling_factor)
+        L.require_cuda(self.inv_freq)
+        dev = self.inv_freq.device
+        firsts, total = [], 0
+        for gh, gw in grids:
+            firsts.append(total)
+            total += gh * gw
+        cos = torch.empty(total, self.rope_dim, dtype=torch.float32, device=dev)
+        sin = torch.empty_like(cos)
+        if total == 0:
+            return cos, sin
+        samples = torch.tensor([[f, gh, gw] for f, (gh, gw) in zip(firsts, grids)], dtype=torch.int64).to(dev)
+        inv_freq = _dense(self.inv_freq.float())
+        L.check(L.load().mojo_hip_vision_rotary_2d(L.ptr(cos), L.ptr(sin), L.ptr(samples), len(grids), total, self.rope_dim,
+                                                   self.adapooling_factor, L.ptr(inv_freq), L.stream_of(cos)),
+                "HIPVisionRotaryEmbedding2D")
+        return cos, sin
+
+
+class HIPApplyVisionRoPE2D(MojoApplyVisionRoPE2D):
+    """`mojo_hip_apply_rope` with ``rope_dim = head_dim`` on token-first tensors: its two rounded fp32 products and rounded sum
+    are the golden's ``x * cos + rotate_half(x) * sin`` bit for bit, so this op is a host path over that
+    kernel.  q and k are read in place through their token and head strides (the last dimension dense: slices of a fused
+    ``[T, 3, N, D]`` projection qualify); the vector width follows ``D / 2``, the strides and the base alignment (16-, 8-,
+    4-byte or element loads).  fp32 tables are read in place; a 16-bit table is widened to fp32 first — the golden's own
+    promotion, exact — as one pass over ``[T, D]``."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, q, k, cos, sin):
+        self.check_shape_contract(q, k, cos, sin)
+        L.require_cuda(q, k, cos, sin)
+        if q.dtype != k.dtype:
+            raise NotImplementedError("HIPApplyVisionRoPE2D: q and k must share one dtype")
+        _require_float("HIPApplyVisionRoPE2D", q)
+        if q.shape[-1] % 2:
+            raise ValueError(f"HIPApplyVisionRoPE2D: head_dim {q.shape[-1]} must be even")
+        if q.stride(-1) != 1:
+            q = q.contiguous()
+        if k.stride(-1) != 1:
+            k = k.contiguous()
+        cos, sin = _dense(cos.float()), _dense(sin.float())
+        tokens, dim = q.shape[0], q.shape[-1]
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        k_out = torch.empty(k.shape, dtype=k.dtype, device=k.device)
+        L.check(L.load().mojo_hip_apply_rope(
+            L.ptr(q), L.ptr(k), L.ptr(q_out), L.ptr(k_out), L.ptr(cos), L.ptr(sin), 1, tokens, q.shape[1], k.shape[1], dim, dim,
+            L.strides3(0, q.stride(0), q.stride(1)), L.strides3(0, k.stride(0), k.stride(1)),
+            L.strides3(0, q_out.stride(0), q_out.stride(1)), L.strides3(0, k_out.stride(0), k_out.stride(1)),
+            0, cos.stride(0), L.dtype_code(q.dtype), L.stream_of(q)), "HIPApplyVisionRoPE2D")
+        return q_out, k_out
+
+
+def _mrope(what, query, key, cos_table, sin_table, mrope_section, is_interleaved, head_dim, inplace):
+    """The host path of both MRoPE classes: validation, then one launch over q and k.  Rows are addressed by their stride
+    (the last dimension dense), so slices of a fused QKV row are read — and, in place, written — where they are."""
+    head_dim, half, hq, hk = check_mrope_contract(query, key, cos_table, sin_table, mrope_section, head_dim)
+    L.require_cuda(query, key, cos_table, sin_table)
+    if query.dtype != key.dtype:
+        raise NotImplementedError(f"{what}: query and key must share one dtype")
+    _require_float(what, query)
+    _require_float(what, cos_table)
+    tokens = query.shape[0]
+    q_in, k_in = query, key
+    if inplace:
+        for name, t in (("query", query), ("key", key)):
+            if t.numel() and t.stride(-1) != 1:
+                raise NotImplementedError(f"{what}: the in-place form needs a dense last dimension of {name}")
+        q_out, k_out = query, key
+    else:
+        q_in = query if query.stride(-1) == 1 else query.contiguous()
+        k_in = key if key.stride(-1) == 1 else key.contiguous()
+        q_out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+        k_out = torch.empty(key.shape, dtype=key.dtype, device=key.device)
+    if tokens == 0:
+        return q_out, k_out
+    cos, sin = cos_table, sin_table
+    if cos.stride(-1) != 1 or cos.stride() != sin.stride():
+        cos, sin = cos.contiguous(), sin.contiguous()
+    sec_stride, tok_stride = (cos.stride(0), cos.stride(1)) if cos.dim() == 3 else (0, cos.stride(0))
+    L.check(L.load().mojo_hip_mrope(
+        L.ptr(q_in), L.ptr(k_in), L.ptr(q_out), L.ptr(k_out), L.ptr(cos), L.ptr(sin), tokens, hq, hk, head_dim,
+        q_in.stride(0), k_in.stride(0), q_out.stride(0), k_out.stride(0), sec_stride, tok_stride,
+        L.strides3(*[int(s) for s in mrope_section]), 1 if is_interleaved else 0, L.dtype_code(cos.dtype),
+        L.dtype_code(query.dtype), L.stream_of(query)), what)
+    return q_out, k_out
+
+
+class HIPMRoPE(MojoMRoPE):
+    """Multimodal RoPE, out of place: one launch over q and k; for ``[3, T, half]`` tables the kernel picks the
+    table per element and never materialises a merged one.  Math in fp32 — each product rounded, no contraction — and one
+    rounding to the storage type.
+
+    The result has the QUERY's dtype.  The reference's out-of-place golden returns fp32 when the tables are fp32 (torch's
+    promotion inside ``cat``); this op returns that fp32 result rounded once to the query's dtype, which is bit for bit what
+    `MojoMRoPEInplace(inplace=True)` stores.  16-bit tables are converted on read and computed in fp32 (the golden computes in
+    the 16-bit type there and rounds three times).  No host sync, capture-safe."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key, cos_table, sin_table, mrope_section, is_interleaved: bool = False,
+                head_dim: Optional[int] = None):
+        return _mrope("HIPMRoPE", query, key, cos_table, sin_table, mrope_section, is_interleaved, head_dim, False)
+
+
+class HIPMRoPEInplace(MojoMRoPEInplace):
+    """Multimodal RoPE in its serving form: with ``inplace=True`` the rotated elements are written back into
+    ``query`` and ``key`` (slices of a fused QKV row are written where they are; elements at or past ``2 * sum(mrope_section)``
+    are not touched) and the inputs are returned; bit for bit the golden with fp32 tables.  ``inplace=False`` is `HIPMRoPE`."""
+    supported_platforms_list = _ROCM
+
+    def forward(self, query, key, cos_table, sin_table, mrope_section, is_interleaved: bool = False,
+                head_dim: Optional[int] = None):
+        return _mrope("HIPMRoPEInplace", query, key, cos_table, sin_table, mrope_section, is_interleaved, head_dim,
+                      bool(self.inplace))

@@ -2,7 +2,8 @@ from .activation import MojoGelu, MojoSilu, MojoSwiGLU
 from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
                         MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
                         MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
-                        MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoSdpa, MojoSWA)
+                        MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoPackedSdpa, MojoSdpa,
+                        MojoSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
 from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
@@ -12,7 +13,8 @@ from .mlp import MojoSwiGLUMLP
 from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts, MojoQuantMoE
 from .normalization import (MojoLayerNorm, MojoResidualAddLayerNorm, MojoResidualAddRMSNorm, MojoRMSNorm,
                             MojoRMSNormInplace)
-from .position_embedding import MojoApplyRoPE, MojoGridRoPE, MojoRotaryEmbedding
+from .position_embedding import (MojoApplyRoPE, MojoApplyVisionRoPE2D, MojoGridRoPE, MojoMRoPE, MojoMRoPEInplace,
+                                 MojoRotaryEmbedding, MojoVisionRotaryEmbedding2D)
 from .quantize import (MojoDequant, MojoDequantSwiGLUQuant, MojoDynamicQuant, MojoLayerNormQuant, MojoMoEDynamicQuant,
                        MojoResidualAddLayerNormQuant, MojoResidualAddRMSNormQuant, MojoRMSNormQuant, MojoStaticQuant)
 from .sampling import (MojoApplyPenaltiesTempurate, MojoJoinProbRejectSampling, MojoRejectSampling, MojoTopKSampling,
@@ -59,3 +61,7 @@ QUANT_DENSE_OPS = ("MojoRMSNormQuant", "MojoLayerNormQuant", "MojoResidualAddLay
 # the ops around every `MojoSdpa` of a DiT block (Wan2.2): LayerNorm with and without affine, the FFN's GELU, the time
 # embedding's SiLU and the 3-D grid RoPE of q and k.  A set of its own likewise (golden: tests/dit_block_golden.py)
 DIT_BLOCK_OPS = ("MojoLayerNorm", "MojoResidualAddLayerNorm", "MojoGelu", "MojoSilu", "MojoGridRoPE")
+# the ops a Qwen-VL model adds to the text decoder: packed var-len bidirectional attention (the vision tower's, with the
+# semantics of the reference's `MojoSWA(is_causal=False)`), the tower's 2-D rotary pair and the decoder's multimodal RoPE.  A set
+# of its own likewise (golden: tests/vision_tower_golden.py)
+VISION_TOWER_OPS = ("MojoPackedSdpa", "MojoVisionRotaryEmbedding2D", "MojoApplyVisionRoPE2D", "MojoMRoPE", "MojoMRoPEInplace")

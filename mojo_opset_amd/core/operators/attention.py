@@ -323,3 +323,25 @@ class MojoPagedPrefillSWAWithKVDequant(_PagedSWAKVDequantBase, MojoOperator):
         super().__init__()
         self._init_swa_kv_dequant(is_causal, gqa_layout, global_window_size, local_window_size, query_dtype,
                                   context_dtype, compute_dtype)
+
+
+class MojoPackedSdpa(MojoOperator):
+    """Packed var-len BIDIRECTIONAL attention over contiguous K/V: the attention of a vision tower, where every sequence is
+    one image or one window.  The semantics of the reference's ``MojoSWA(is_causal=False, gqa_layout=...)`` (:747-835), under
+    a name of its own: sequence ``b`` owns query rows ``[cu_q_lens[b], cu_q_lens[b+1])`` and K/V rows
+    ``[cu_total_seq_lens[b], cu_total_seq_lens[b+1])``, and every query row of the sequence sees every key of it.  ``q_len``
+    and ``kv_len`` are independent; ``kv_len < q_len`` is legal (there is no offset).
+
+    forward(query [Tq,Hq,D], key [Tk,Hkv,D], value [Tk,Hkv,D], cu_q_lens [B+1] i32, cu_total_seq_lens [B+1] i32,
+            softmax_scale=None, *, max_q_len=None, max_total_seq_len=None) -> [Tq,Hq,D]
+    """
+
+    def __init__(self, gqa_layout: str = "AABB"):
+        super().__init__()
+        if gqa_layout not in _GQA_LAYOUTS:
+            raise ValueError(f"gqa_layout must be one of ['ABAB', 'AABB'], got {gqa_layout}")
+        self.gqa_layout = gqa_layout
+        self.gqa_interleave = gqa_layout == "ABAB"
+
+    def extra_repr(self) -> str:
+        return f"gqa_layout={self.gqa_layout}"

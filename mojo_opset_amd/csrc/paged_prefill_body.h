@@ -32,8 +32,13 @@
 // FULL instances (MojoSdpa, sdpa.hip): linear, bidirectional — every row sees [0, kv_len) — with uniform lengths, strided
 // addressing and an optional mask; see SdpaArgs.
 //
+// NODIAG instances (MojoPackedSdpa, packed_sdpa.hip): linear, bidirectional, packed var-len — the walk of the FULL instances
+// (no offset, every whole key tile unmasked, only the tail tile masked) over the arguments of the LINEAR ones (PrefillArgs: cu_*
+// arrays, zero fill of the padding rows, key split and merge).
+//
 // This header is the whole prefill: kernels, launch chain and plan.  paged_prefill_gqa.hip instantiates the paged forms,
-// swa_packed.hip the linear ones and sdpa.hip the bidirectional ones (three translation units: they compile side by side).
+// swa_packed.hip the linear ones, sdpa.hip the strided bidirectional ones and packed_sdpa.hip the packed bidirectional ones
+// (four translation units: they compile side by side).
 #pragma once
 #include <math.h>
 
@@ -73,6 +78,9 @@ struct PrefillArgs {
   // sliding window (the SWA instances only): key j is visible to the row at position p iff j <= p and (j >= p - local_win or
   // j < global_win).  No local window: local_win = -2^30 (no key qualifies); no global window: global_win = 0.
   int local_win = -(1 << 30), global_win = 0;
+  // NODIAG instances only: the caller's hints as exact bounds.  Keys at or past kv_cap of a sequence are unseen; query rows at
+  // or past q_cap (= the longest run the launch covers) are written as zeros.
+  int kv_cap = 0x7fffffff, q_cap = 0x7fffffff;
 };
 
 // FULL instances (MojoSdpa, sdpa.hip): bidirectional attention of uniform [Sq] x [Sk] per batch entry, every tensor addressed by
@@ -140,10 +148,15 @@ constexpr int PF_LDS = 4 * PF_TILE_BYTES + PF_TABLE * 4 + 16;    // K0 V0 K1 V1 
 
 template <typename T, int G /* q heads per kv head */, int DK /* head_dim / 32 */, bool SPLIT = false /* key split, see PrefillArgs */,
           bool SWA = false /* sliding window, see below */, bool LINEAR = false /* packed K/V, no pages (see the top) */,
-          bool FULL = false /* no causal edge: every row sees [0, kv_len); strided addressing (SdpaArgs) */,
-          bool MASK = false /* FULL only: a bias / boolean mask per score */>
+          bool FULL = false /* the arguments are SdpaArgs: uniform lengths, strided addressing, no cu_* arrays; implies no causal edge */,
+          bool MASK = false /* FULL only: a bias / boolean mask per score */,
+          bool NODIAG = false /* no causal edge over PrefillArgs: every row of a packed sequence sees [0, kv_len) */>
 __global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL, SdpaArgs, PrefillArgs> a) {
-  static_assert(!FULL || (LINEAR && !SWA), "the bidirectional instances are linear and take no window");
+  // The two meanings FULL used to carry: BIDIR = "no causal edge" (no offset, kv_hi = kv_len, whole tiles up to kv_len / PF_KEYS,
+  // only the tail tile masked, a row without a key stores zeros); FULL = "the arguments are SdpaArgs" (strides, sq / sk, mask).
+  constexpr bool BIDIR = FULL || NODIAG;
+  static_assert(!BIDIR || (LINEAR && !SWA), "the bidirectional instances are linear and take no window");
+  static_assert(!(FULL && NODIAG), "NODIAG names the bidirectional instances over PrefillArgs");
   static_assert(!MASK || FULL, "a mask is read by the bidirectional instances only");
   typedef typename pf_mfma<T>::frag frag;
   constexpr int QPB = 128 / G;               // query positions per workgroup
@@ -220,8 +233,10 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL
     kv_end = min(max(kv_end, 0), a.max_pages);
     kv_lo = min(max(kv_lo, 0), kv_end);
   }
-  const int q_len = q_end - q_start;
-  const int kv_len = (FULL || a.cu_kv) ? kv_end - kv_lo : q_len;
+  const int q_len_all = q_end - q_start;
+  const int q_len = NODIAG ? min(q_len_all, a.q_cap) : q_len_all;
+  const int kv_len_all = (FULL || a.cu_kv) ? kv_end - kv_lo : q_len;
+  const int kv_len = NODIAG ? min(kv_len_all, a.kv_cap) : kv_len_all;
   // row `pos` of this sequence, head `head`, in the query and in the output (FULL: by strides, the two may differ)
   auto q_row = [&](int pos, int head) -> const T* {
     if constexpr (FULL) return static_cast<const T*>(a.q) + (b * a.q_bs + head * a.q_hs + pos * a.q_ts);
@@ -246,13 +261,18 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL
   };
   // A sequence longer than the caller's max_q_len hint has rows no query block of this launch covers: they are written
   // as zeros (never left uninitialised) by the workgroup of the sequence's last covered block.
-  if (qb == a.n_qb - 1 && q_len > a.n_qb * QPB && ks == 0) zero_rows(a.n_qb * QPB, q_len);
+  // (NODIAG: q_len is already cut at q_cap <= n_qb * QPB, and the rows behind the cut are the ones to zero)
+  if constexpr (NODIAG) {
+    if (qb == a.n_qb - 1 && q_len_all > q_len && ks == 0) zero_rows(q_len, q_len_all);
+  } else {
+    if (qb == a.n_qb - 1 && q_len > a.n_qb * QPB && ks == 0) zero_rows(a.n_qb * QPB, q_len);
+  }
   if (qb * QPB >= q_len) return;
   if (kv_len <= 0) {                                     // a sequence without keys: its rows read as zeros
     if (ks == 0) zero_rows(qb * QPB, min(q_len, (qb + 1) * QPB));
     return;
   }
-  const int offset = FULL ? 0 : kv_len - q_len;          // query i sees keys 0 .. offset + i (FULL: enters no bound)
+  const int offset = BIDIR ? 0 : kv_len - q_len;         // query i sees keys 0 .. offset + i (BIDIR: enters no bound)
 #ifdef PF_WG_STAMPS
   const unsigned long long wg_t0 = __builtin_readcyclecounter();
   if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) {
@@ -267,7 +287,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL
   const int grp = lane >> 4, l15 = lane & 15;
 
   const int pos_hi = min(q_len, (qb + 1) * QPB) - 1;    // last query position of this block
-  int kv_hi = FULL ? kv_len : min(kv_len, offset + pos_hi + 1);   // keys [0, kv_hi) are visible to some row
+  int kv_hi = BIDIR ? kv_len : min(kv_len, offset + pos_hi + 1);   // keys [0, kv_hi) are visible to some row
   if (kv_hi < 1) kv_hi = 1;
   const int n_kb_all = (kv_hi + PF_KEYS - 1) / PF_KEYS;
   // Sliding window (MojoPagedPrefillSWA).  The rows of the block sit at positions [p_lo, p_hi]; together they see keys
@@ -544,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL
     u0 = min(max(r0 - gap_t, 0), n_vkb);
     n_whole = min(max(full_end / PF_KEYS - gap_t, u0), n_vkb) - u0;
   }
-  const int n_full = FULL ? min(kv_len / PF_KEYS, n_kb)
+  const int n_full = BIDIR ? min(kv_len / PF_KEYS, n_kb)
                           : SWA ? min(n_whole, n_kb) : min(min(min(kv_len, offset + qb * QPB + 1), first_neg_key) / PF_KEYS, n_kb);
   const int n_fast = a.fast_stage ? n_full : 0;          // tiles [0, n_fast) may be staged the fast way
 
@@ -815,7 +835,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL
           for (int r = 0; r < 4; ++r) {
             const int key = key0 + 16 * t + r;
             if (has_hole && key >= first_neg_key) sc[t][r] = seed[qt];   // zero K rows: score 0 (relative to the reference)
-            if constexpr (FULL) {
+            if constexpr (BIDIR) {
               if (key >= kv_len) sc[t][r] = -INFINITY;   // the tail tile: no causal edge
             } else {
               if (key > offset + row_pos[qt] || key >= kv_len) sc[t][r] = -INFINITY;
@@ -987,7 +1007,7 @@ __global__ __launch_bounds__(256, 2) void prefill_kernel(std::conditional_t<FULL
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const float lsum = osum[qt][0] + xor_sum_16_32(lhole[qt]);
-    const float inv = (FULL && !(lsum > 0.f)) ? 0.f : 1.0f / lsum;   // (FULL: a row whose mask hides every key stores zeros)
+    const float inv = (BIDIR && !(lsum > 0.f)) ? 0.f : 1.0f / lsum;  // (BIDIR: a row whose mask hides every key stores zeros)
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       V4 ov;
@@ -1031,7 +1051,7 @@ static __device__ __forceinline__ int sdpa_len(const A& a) {    // Sq (0) / Sk (
   if constexpr (FULL) return WHICH ? a.sk : a.sq;
   else return 0;
 }
-template <typename T, int G, bool FULL = false>
+template <typename T, int G, bool FULL = false, bool NODIAG = false /* cut q_len at PrefillArgs::q_cap, as the attention launch did */>
 __global__ __launch_bounds__(256) void prefill_merge_kernel(std::conditional_t<FULL, SdpaArgs, PrefillArgs> a) {
   constexpr int QPB = 128 / G;
   constexpr int ROWS = 128 / PF_MERGE_SPLIT;
@@ -1041,7 +1061,8 @@ __global__ __launch_bounds__(256) void prefill_merge_kernel(std::conditional_t<F
   const int rem = wg % inner;
   const int kvh = rem % a.hkv, b = (rem / a.hkv + a.skew * (wg / inner)) % a.batch;
   const int q_start = FULL ? 0 : a.cu_q[b];
-  const int q_len = FULL ? sdpa_len<FULL, 0>(a) : a.cu_q[b + 1] - q_start;
+  const int q_len_all = FULL ? sdpa_len<FULL, 0>(a) : a.cu_q[b + 1] - q_start;
+  const int q_len = NODIAG ? min(q_len_all, a.q_cap) : q_len_all;
   const int kv_len = FULL ? sdpa_len<FULL, 1>(a) : (a.cu_kv ? a.cu_kv[b + 1] - a.cu_kv[b] : q_len);
   if (qb * QPB >= q_len || kv_len <= 0) return;          // (rows the attention launch zeroed or never owned)
   const int per_row = a.dim / 4;
@@ -1100,19 +1121,19 @@ namespace mojo { constexpr int W64_TABLE = 0; }
 #endif
 namespace mojo {
 
-template <typename T, int G, int DK, bool SWA, bool LINEAR = false>
+template <typename T, int G, int DK, bool SWA, bool LINEAR = false, bool NODIAG = false>
 static void launch_pf(const PrefillArgs& a, dim3 grid, hipStream_t s) {
   static std::atomic<uint64_t> attr_set{0};
   if (first_call_on_device(attr_set)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, false, SWA, LINEAR>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, true, SWA, LINEAR>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, false, SWA, LINEAR, false, false, NODIAG>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_kernel<T, G, DK, true, SWA, LINEAR, false, false, NODIAG>), hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS);
   }
   if constexpr (SWA || LINEAR) {                         // (the experiments-build kernels take no window and have no linear form)
     if (a.ksplit > 1) {
-      hipLaunchKernelGGL((prefill_kernel<T, G, DK, true, SWA, LINEAR>), grid, dim3(256), PF_LDS, s, a);
-      hipLaunchKernelGGL((prefill_merge_kernel<T, G>), dim3(static_cast<unsigned>(a.n_qb * a.hkv * a.batch * PF_MERGE_SPLIT)), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((prefill_kernel<T, G, DK, true, SWA, LINEAR, false, false, NODIAG>), grid, dim3(256), PF_LDS, s, a);
+      hipLaunchKernelGGL((prefill_merge_kernel<T, G, false, NODIAG>), dim3(static_cast<unsigned>(a.n_qb * a.hkv * a.batch * PF_MERGE_SPLIT)), dim3(256), 0, s, a);
     } else {
-      hipLaunchKernelGGL((prefill_kernel<T, G, DK, false, SWA, LINEAR>), grid, dim3(256), PF_LDS, s, a);
+      hipLaunchKernelGGL((prefill_kernel<T, G, DK, false, SWA, LINEAR, false, false, NODIAG>), grid, dim3(256), PF_LDS, s, a);
     }
     return;
   }
@@ -1156,23 +1177,25 @@ static void launch_pf(const PrefillArgs& a, dim3 grid, hipStream_t s) {
 #endif
   // (reached by the plain paged launch only; the instance is named in full so that no other launch instantiates it)
   if (a.ksplit > 1) {
-    hipLaunchKernelGGL((prefill_kernel<T, G, DK, true, SWA, LINEAR>), grid, dim3(256), PF_LDS, s, a);
+    hipLaunchKernelGGL((prefill_kernel<T, G, DK, true, SWA, LINEAR, false, false, NODIAG>), grid, dim3(256), PF_LDS, s, a);
     hipLaunchKernelGGL((prefill_merge_kernel<T, G>), dim3(static_cast<unsigned>(a.n_qb * a.hkv * a.batch * PF_MERGE_SPLIT)), dim3(256), 0, s, a);
   } else {
-    hipLaunchKernelGGL((prefill_kernel<T, G, DK, false, SWA, LINEAR>), grid, dim3(256), PF_LDS, s, a);
+    hipLaunchKernelGGL((prefill_kernel<T, G, DK, false, SWA, LINEAR, false, false, NODIAG>), grid, dim3(256), PF_LDS, s, a);
   }
 }
 
-template <typename T, int G, bool SWA, bool LINEAR = false>
+template <typename T, int G, bool SWA, bool LINEAR = false, bool NODIAG = false>
 static int dispatch_dk(const PrefillArgs& a, dim3 grid, hipStream_t s) {
   switch (a.dim) {
-    case 64: launch_pf<T, G, 2, SWA, LINEAR>(a, grid, s); break;
-    case 96: launch_pf<T, G, 3, SWA, LINEAR>(a, grid, s); break;
-    case 128: launch_pf<T, G, 4, SWA, LINEAR>(a, grid, s); break;
+    case 64: launch_pf<T, G, 2, SWA, LINEAR, NODIAG>(a, grid, s); break;
+    case 96: launch_pf<T, G, 3, SWA, LINEAR, NODIAG>(a, grid, s); break;
+    case 128: launch_pf<T, G, 4, SWA, LINEAR, NODIAG>(a, grid, s); break;
     default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_prefill_gqa: head_dim %d (64, 96, 128)", a.dim);
   }
   MOJO_CHECK_LAUNCH("paged_prefill_gqa");
-  if constexpr (LINEAR)
+  if constexpr (NODIAG)
+    note_launch("packed_sdpa:default:%s:ksplit%d", a.fast_stage ? "fast_stage" : "general_stage", a.ksplit);
+  else if constexpr (LINEAR)
     note_launch(SWA ? "prefill_linear:default:%s:ksplit%d:swa" : "prefill_linear:default:%s:ksplit%d",
                 a.fast_stage ? "fast_stage" : "general_stage", a.ksplit);
   else
@@ -1206,7 +1229,7 @@ static bool prefill_use_pp(int64_t max_q) {
   return false;
 }
 
-template <typename T, bool SWA, bool LINEAR = false>
+template <typename T, bool SWA, bool LINEAR = false, bool NODIAG = false>
 static int dispatch_g(PrefillArgs a, int G, int64_t batch, int64_t max_q, hipStream_t s) {
   // Experiments build only: the phase-alternating kernel takes unsplit launches over pages it can stage with scalar page
   // ids when MOJO_HIP_PREFILL_PP=1.
@@ -1226,10 +1249,10 @@ static int dispatch_g(PrefillArgs a, int G, int64_t batch, int64_t max_q, hipStr
 #endif
   dim3 grid(static_cast<unsigned>((n_qb * a.hkv * batch + n_zero) * a.ksplit));
   switch (G) {
-    case 1: return dispatch_dk<T, 1, SWA, LINEAR>(a, grid, s);
-    case 2: return dispatch_dk<T, 2, SWA, LINEAR>(a, grid, s);
-    case 4: return dispatch_dk<T, 4, SWA, LINEAR>(a, grid, s);
-    case 8: return dispatch_dk<T, 8, SWA, LINEAR>(a, grid, s);
+    case 1: return dispatch_dk<T, 1, SWA, LINEAR, NODIAG>(a, grid, s);
+    case 2: return dispatch_dk<T, 2, SWA, LINEAR, NODIAG>(a, grid, s);
+    case 4: return dispatch_dk<T, 4, SWA, LINEAR, NODIAG>(a, grid, s);
+    case 8: return dispatch_dk<T, 8, SWA, LINEAR, NODIAG>(a, grid, s);
     default: MOJO_REQUIRE(false, MOJO_EUNSUPPORTED, "paged_prefill_gqa: group size %d (1, 2, 4, 8)", G);
   }
 }
@@ -1302,7 +1325,8 @@ struct PrefillCall {
 // The GQA and SWA entry points share one body (SWA: the windowed kernel instances, key split sized on the visible keys).
 // LINEAR (mojo_hip_swa_packed): key_cache / value_cache are the packed [Tk, Hkv, D] tensors, cache_token_stride and
 // cache_head_stride their strides, cu_total_seq_lens is required and there is no table; g.total_kv_tokens = Tk.
-template <bool SWA, bool LINEAR = false>
+// NODIAG (mojo_hip_packed_sdpa): the LINEAR arguments, no window; g.max_kv_hint also caps every sequence's keys.
+template <bool SWA, bool LINEAR = false, bool NODIAG = false>
 static int paged_prefill_planned(const PrefillCall& c, const PrefillPlan& p) {
   const PrefillGeom& g = c.g;
   hipStream_t s = static_cast<hipStream_t>(c.stream);
@@ -1344,6 +1368,10 @@ static int paged_prefill_planned(const PrefillCall& c, const PrefillPlan& p) {
     a.local_win = g.local_window >= 0 ? static_cast<int>(g.local_window) : -(1 << 30);
     a.global_win = g.global_window > 0 ? static_cast<int>(g.global_window) : 0;
   }
+  if constexpr (NODIAG) {
+    if (g.max_kv_hint > 0 && g.max_kv_hint < a.kv_cap) a.kv_cap = static_cast<int>(g.max_kv_hint);
+    if (p.max_q < a.q_cap) a.q_cap = static_cast<int>(p.max_q);
+  }
   const bool no_fs = MOJO_SWITCH("MOJO_HIP_PREFILL_FAST_STAGE", 1) == 0;        // 0: general staging everywhere (tests)
   // (LINEAR: no page terms — what remains is the 32-bit bound on a lane's offset inside its wave's 16 keys, and the switch)
   a.fast_stage = ((LINEAR || a.page_shift >= 4) && c.cache_token_stride * 16 * 2 + 256 < (int64_t{1} << 31) && !no_fs) ? 1 : 0;
@@ -1353,8 +1381,8 @@ static int paged_prefill_planned(const PrefillCall& c, const PrefillPlan& p) {
   a.ws_o = split ? static_cast<float*>(c.workspace) : nullptr;
   a.ws_ml = split ? a.ws_o + p.rows * g.head_dim : nullptr;
   const int G = static_cast<int>(g.q_heads / g.kv_heads);
-  return c.dtype == MOJO_BF16 ? dispatch_g<bf16_t, SWA, LINEAR>(a, G, g.batch, p.max_q, s)
-                              : dispatch_g<f16_t, SWA, LINEAR>(a, G, g.batch, p.max_q, s);
+  return c.dtype == MOJO_BF16 ? dispatch_g<bf16_t, SWA, LINEAR, NODIAG>(a, G, g.batch, p.max_q, s)
+                              : dispatch_g<f16_t, SWA, LINEAR, NODIAG>(a, G, g.batch, p.max_q, s);
 }
 
 }  // namespace mojo
