@@ -19,6 +19,7 @@ import torch
 import mojo_opset_amd as mo
 import oracle.sampling as G
 from conftest import bit_equal, clone_tree, load_golden, to_device
+from sampling_judge import Judged, _cdf_targets, _check_draw, _ulps, final64  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -43,66 +44,6 @@ def _hip(name, **kwargs):
 
 def _ids(cases):
     return [pytest.param(c, id=f"{c['op'][4:]}-{i}") for i, c in enumerate(cases)]
-
-
-def _ulps(a, b):
-    """Distance in units of the last place between two tensors of one 16-bit dtype (same sign or zero)."""
-    return (a.view(torch.int16).int() - b.view(torch.int16).int()).abs()
-
-
-def final64(values, kept, filter_value):
-    """``final_probs_dist`` in fp64 with the first ``kept[row]`` positions kept."""
-    k = values.shape[-1]
-    removed = torch.arange(k).expand(values.shape) >= kept.unsqueeze(-1)
-    return torch.softmax(values.double().masked_fill(removed, filter_value), dim=-1)
-
-
-class Judged:
-    """The golden's view of one filter call on 2-D fp32 values: cut, tolerance, undecidable rows (module docstring)."""
-
-    def __init__(self, logits, top_p, keep, k, filter_value):
-        x = logits.reshape(-1, logits.shape[-1])
-        self.k = min(k, x.shape[-1])
-        self.filter_value = filter_value
-        self.probs32, self.indices, self.values = G.top_p_filter(x, top_p, keep, k, filter_value)
-        cum32 = self.values.softmax(-1).cumsum(-1)
-        cum64 = torch.softmax(self.values.double(), -1).cumsum(-1)
-        self.delta = 8 * float((cum32.double() - cum64).abs().max())
-        threshold = float(torch.tensor(top_p, dtype=torch.float32))               # what the fp32 comparison sees
-        self.nearest = float((cum64 - threshold).abs().min())
-        self.undecidable = ((cum64 - threshold).abs() < self.delta).any(-1)
-        self.kept = (~G.removed_mask(cum32, top_p, keep)).sum(-1)
-        self.ref64 = final64(self.values, self.kept, filter_value)
-        big = self.ref64 > 1e-30
-        self.golden_err = float(((self.probs32.double() - self.ref64).abs() / self.ref64.clamp(min=1e-300))[big].max())
-        self.tol = 8 * self.golden_err
-
-    def check(self, probs, indices, dtype, what):
-        rows = self.values.shape[0]
-        probs, indices = probs.reshape(rows, self.k).cpu(), indices.reshape(rows, self.k).cpu()
-        assert indices.dtype == torch.int64 and probs.dtype == dtype
-        assert torch.equal(indices, self.indices), f"{what}: indices differ from the golden's"
-        frac = float(self.undecidable.float().mean())
-        print(f"{what}: delta {self.delta:.3e} nearest approach {self.nearest:.3e} undecidable rows {int(self.undecidable.sum())} "
-              f"of {rows}; golden fp32 error {self.golden_err:.3e} -> tolerance {self.tol:.3e}")
-        assert frac <= 0.05
-        worst = torch.full((rows,), float("inf"), dtype=torch.float64)
-        for shift in (0, -1, 1):
-            kept = (self.kept + shift).clamp(1, self.k)
-            ref = final64(self.values, kept, self.filter_value)
-            allowed = self.undecidable if shift else torch.ones(rows, dtype=torch.bool)
-            if dtype == torch.float32:
-                big = ref > 1e-30
-                err = ((probs.double() - ref).abs() / ref.clamp(min=1e-300)).masked_fill(~big, 0.0).amax(-1)
-                err = torch.where(((probs != 0) & (ref == 0)).any(-1), torch.full_like(err, float("inf")), err)
-                ok_zero = ((probs == 0) | (ref > 0)).all(-1)                   # removed positions exactly 0 under -inf
-                err = torch.where(ok_zero, err, torch.full_like(err, float("inf")))
-            else:
-                err = _ulps(probs, ref.to(dtype)).amax(-1).double()
-            worst = torch.where(allowed, torch.minimum(worst, err), worst)
-        bound = self.tol if dtype == torch.float32 else 1.0
-        print(f"{what}: worst {'relative error' if dtype == torch.float32 else 'ulp distance'} {float(worst.max()):.3e} (bound {bound:.3e})")
-        assert float(worst.max()) <= bound
 
 
 def _run_filter(logits, top_p, keep, k, filter_value=NEG_INF, slices=0):
@@ -172,27 +113,15 @@ def test_every_slice_count_gives_the_same_bits(rows, vocab, k, dtype):
     logits = _logits(rows, vocab, 1.0, dtype, 0)
     base = _run_filter(logits, 0.75, 1, k)
     forms = {L.last_launch()}
-    for slices in (1, 2, 8):
+    for slices in (1, 2, 3, 5, 8, 4096):
         assert bit_equal(_run_filter(logits, 0.75, 1, k, slices=slices), base), f"slices={slices}"
         forms.add(L.last_launch())
     print(sorted(forms))
     assert all(f.startswith("sampling:filter:top_p:slices") for f in forms) and len(forms) >= 2
     u = torch.rand(rows, device=DEV)
-    picks = [_S().sample_with_uniforms(logits.to(DEV), u, k, top_p=0.75, slices=s) for s in (0, 1, 2, 8)]
+    picks = [_S().sample_with_uniforms(logits.to(DEV), u, k, top_p=0.75, slices=s) for s in (0, 1, 2, 3, 5, 8, 4096)]
     assert all(bit_equal(p, picks[0]) for p in picks[1:])
     assert L.last_launch().startswith("sampling:sample:top_p:slices")
-
-
-def _cdf_targets(judged, rows, g):
-    """For the first, the last kept and a random kept position of every row: the fp32 midpoint of its interval of the fp64 CDF."""
-    cdf = judged.ref64.cumsum(-1)
-    cdf = cdf / cdf[:, -1:]
-    lower = torch.cat([torch.zeros(rows, 1, dtype=torch.float64), cdf[:, :-1]], dim=-1)
-    last = judged.kept - 1
-    rand = (torch.rand(rows, generator=g) * judged.kept).long().clamp(max=judged.k - 1)
-    for name, target in (("first", torch.zeros(rows, dtype=torch.long)), ("last kept", last), ("random kept", rand)):
-        lo, hi = lower.gather(-1, target[:, None])[:, 0], cdf.gather(-1, target[:, None])[:, 0]
-        yield name, target, ((lo + hi) / 2).float(), hi - lo
 
 
 @pytest.mark.parametrize("rows,vocab,k,top_p,dtype,seed", [(20, 151936, 1000, 0.75, torch.float32, 0),
@@ -258,19 +187,6 @@ def _judged_sampler(name, kwargs, logits):
         return Judged(logits, 2.0, 1, k, NEG_INF)
     return Judged(logits, kwargs.get("top_p", 0.75), kwargs.get("min_tokens_to_keep", 1), kwargs.get("rand_top_k", 1000),
                   kwargs.get("filter_value", NEG_INF))
-
-
-def _check_draw(judged, probs, tokens, what):
-    rows = judged.values.shape[0]
-    probs, tokens = probs.reshape(rows, 1).cpu(), tokens.reshape(rows, 1).cpu()
-    where = judged.indices == tokens
-    assert bool((where.sum(-1) == 1).all())                                     # a token of the candidate set ...
-    want = judged.ref64[where]
-    ok = ~judged.undecidable
-    assert bool((want[ok] > 0).all()) and bool((probs > 0).all())               # ... that the golden keeps ...
-    err = float(((probs[:, 0].double() - want).abs() / want)[ok].max())
-    print(f"{what}: relative error of the returned probability {err:.3e} (bound {judged.tol:.3e})")
-    assert err <= judged.tol                                                    # ... with its probability
 
 
 @pytest.mark.parametrize("case", _ids(SAMPLERS))
