@@ -874,6 +874,55 @@ int mojo_hip_mrope(const void* query, const void* key, void* query_out, void* ke
                    int64_t table_section_stride, int64_t table_token_stride, const int64_t mrope_section[3],
                    int is_interleaved, int table_dtype, int dtype, mojo_stream_t stream);
 
+/* ---- The input-embedding ops (EMBEDDING_OPS: MojoEmbedding, MojoParallelEmbedding, MojoOverEncodingNGram, MojoOverEncoding,
+ *      MojoNF4DequantEmbedding; core/operators/embedding.py, core/operators/over_encoding.py).  Ids, q_lens and the layer's
+ *      three vocabulary arrays are read ON THE DEVICE: no host synchronisation, graph-capturable.  An index outside its table
+ *      never reads out of bounds and never traps: it selects a row of zeros.
+ *      embedding: out[t] = table[ids[t] - vocab_start] when that index is in [0, rows), else zeros.  ids int32 / int64
+ *      (ids_i64) dense [tokens]; table and out by a row stride in elements, dtype f32 / f16 / bf16 (a byte copy).  16-byte
+ *      vectors when the row bytes, both strides and both base pointers are multiples of 16, single elements otherwise.  Tags
+ *      `embedding:<vec16|scalar>:lanes<L>`.
+ *      nf4_embedding: the same indexing into a packed-NF4 table: qweight [rows][dim / 2] bytes dense (int8 or uint8: the bits),
+ *      element 2j the low and 2j + 1 the high nibble of byte j; scale / mean [rows][dim / group_size] dense in scale_dtype
+ *      (f32 / f16 / bf16); codebook: the 16 levels as fp16 on the device (the reference holds them ROUNDED to fp16).  The value
+ *      is fp32(codebook[nibble]) * fp32(scale) + fp32(mean), the product and the sum each rounded in fp32 (no fused
+ *      multiply-add), rounded once to out_dtype.  group_size: any positive divisor of dim, taken per element (odd sizes
+ *      split a byte between two groups).  Tags `nf4_embedding:<vec8|scalar>:lanes<L>`.
+ *      oe_ngram: out[t][g] = id + oe_vocab_offsets[g] with id = x[t], carry = ori_vocab_size, and for i in 1 .. oe_grams[g] - 1:
+ *      id = (id + p(i) * carry) mod V, carry = carry * ori_vocab_size mod V (V = oe_vocab_sizes[g]; torch's floor modulus; sums
+ *      and products wrap in 64 bits; the first carry is not reduced; a gram of 1 applies no modulus).  p(i) = x[t - i] inside
+ *      the sequence, history[seq][hist_len + pos - i] before its start (the history is read from its END; hist_len >=
+ *      max_gram - 1 or MOJO_EINVAL).  seq_len == 0: packed, input_ids [tokens] with q_lens [batch] (negative: 0; a token at or
+ *      past sum(q_lens) gets id 0, in the concatenation a row of zeros); seq_len > 0: batched, input_ids [batch][seq_len]
+ *      dense, tokens == batch * seq_len.  history [batch][hist_len] by hist_stride.  A gram above max_gram is clamped to it.
+ *      index_flags: bit 0 input_ids, 1 history, 2 q_lens, 3 oe_vocab_sizes, 4 oe_grams, 5 oe_vocab_offsets is int64 (else
+ *      int32).  out has the dtype of input_ids, [tokens][num_grams] dense.  num_grams <= 255.  Tags `oe_ngram:<packed|batched>`.
+ *      over_encoding_concat: one launch writes out[t] = [ori_table row of x[t] | mega row of id(t, 0) | ... | mega row of
+ *      id(t, G - 1)], ori_dim + G * mega_dim elements by out_row_stride; the ids are those of oe_ngram and are not written
+ *      anywhere.  ori_table [ori_rows][ori_dim] by ori_row_stride; the mega table dense [mega_rows][mega_dim] by
+ *      mega_row_stride in dtype (mega_nf4 = 0; scale / mean / codebook unused) or packed NF4 as in nf4_embedding (mega_nf4 = 1;
+ *      mega_row_stride unused), indexed by id - mega_vocab_start.  The 16-byte path needs every segment start (ori_dim + g *
+ *      mega_dim elements) and every row on a 16-byte boundary; else single elements.  Tags
+ *      `oe_concat:<dense|nf4>:<vec|scalar>:<packed|batched>`.                                                              */
+int mojo_hip_embedding(const void* ids, int ids_i64, const void* table, void* out, int64_t tokens, int64_t rows, int64_t dim,
+                       int64_t vocab_start, int64_t table_row_stride, int64_t out_row_stride, int dtype,
+                       mojo_stream_t stream);
+int mojo_hip_nf4_embedding(const void* ids, int ids_i64, const void* qweight, const void* scale, const void* mean,
+                           const void* codebook, void* out, int64_t tokens, int64_t rows, int64_t dim, int64_t group_size,
+                           int64_t vocab_start, int64_t out_row_stride, int scale_dtype, int out_dtype, mojo_stream_t stream);
+int mojo_hip_oe_ngram(const void* input_ids, const void* history, const void* q_lens, const void* oe_vocab_sizes,
+                      const void* oe_grams, const void* oe_vocab_offsets, void* out, int64_t tokens, int64_t batch,
+                      int64_t seq_len, int64_t hist_len, int64_t hist_stride, int64_t num_grams, int64_t max_gram,
+                      int64_t ori_vocab_size, int index_flags, mojo_stream_t stream);
+int mojo_hip_over_encoding_concat(const void* input_ids, const void* history, const void* q_lens, const void* oe_vocab_sizes,
+                                  const void* oe_grams, const void* oe_vocab_offsets, int64_t tokens, int64_t batch,
+                                  int64_t seq_len, int64_t hist_len, int64_t hist_stride, int64_t num_grams, int64_t max_gram,
+                                  int64_t ori_vocab_size, int index_flags, const void* ori_table, int64_t ori_rows,
+                                  int64_t ori_dim, int64_t ori_row_stride, const void* mega_table, const void* mega_scale,
+                                  const void* mega_mean, const void* codebook, int64_t mega_rows, int64_t mega_dim,
+                                  int64_t mega_row_stride, int64_t group_size, int64_t mega_vocab_start, int mega_nf4,
+                                  int scale_dtype, void* out, int64_t out_row_stride, int dtype, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

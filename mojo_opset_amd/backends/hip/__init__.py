@@ -6,6 +6,8 @@ the registry ignores them; on a ROCm host they are the first-priority backend.
 from .operators.attention import *  # noqa: F401,F403
 from .operators.kv_int8 import *  # noqa: F401,F403
 from .operators.streaming import *  # noqa: F401,F403
+from .operators.embedding import (HIPEmbedding, HIPNF4DequantEmbedding, HIPOverEncoding, HIPOverEncodingNGram,  # noqa: F401
+                                  HIPParallelEmbedding)
 from .operators.gemm import HIPGemm, HIPGroupGemm, HIPQuantGemm, HIPSwiGLUMLP  # noqa: F401
 from .operators.mla import HIPPagedDecodeMLA, HIPPagedPrefillMLA  # noqa: F401
 from .operators.compute_with_comm import (HIPAllGatherGemm, HIPGemmAll2All, HIPGemmAllReduce,  # noqa: F401

@@ -145,6 +145,11 @@ SIGNATURES = {
     "mojo_hip_packed_sdpa": (c_int, [_P] * 6 + [_I] * 10 + [c_float, c_int, c_int, _P, _I, _P]),
     "mojo_hip_vision_rotary_2d": (c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "mojo_hip_mrope": (c_int, [_P] * 6 + [_I] * 10 + [_I64x3, c_int, c_int, c_int, _P]),
+    "mojo_hip_embedding": (c_int, [_P, c_int, _P, _P] + [_I] * 6 + [c_int, _P]),
+    "mojo_hip_nf4_embedding": (c_int, [_P, c_int] + [_P] * 5 + [_I] * 6 + [c_int, c_int, _P]),
+    "mojo_hip_oe_ngram": (c_int, [_P] * 7 + [_I] * 8 + [c_int, _P]),
+    "mojo_hip_over_encoding_concat": (c_int, [_P] * 6 + [_I] * 8 + [c_int, _P] + [_I] * 3 + [_P] * 4 + [_I] * 5 +
+                                      [c_int, c_int, _P, _I, c_int, _P]),
 }
 
 _lock = threading.Lock()

@@ -5,12 +5,14 @@ from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, Moj
                         MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoPackedSdpa, MojoSdpa,
                         MojoSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
+from .embedding import MojoEmbedding, MojoParallelEmbedding
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
 from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
                        build_paged_kv_chunk_metadata)
 from .mla import MojoPagedDecodeMLA, MojoPagedPrefillMLA
 from .mlp import MojoSwiGLUMLP
 from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts, MojoQuantMoE
+from .over_encoding import MojoNF4DequantEmbedding, MojoOverEncoding, MojoOverEncodingNGram
 from .normalization import (MojoLayerNorm, MojoResidualAddLayerNorm, MojoResidualAddRMSNorm, MojoRMSNorm,
                             MojoRMSNormInplace)
 from .position_embedding import (MojoApplyRoPE, MojoApplyVisionRoPE2D, MojoGridRoPE, MojoMRoPE, MojoMRoPEInplace,
@@ -65,3 +67,7 @@ DIT_BLOCK_OPS = ("MojoLayerNorm", "MojoResidualAddLayerNorm", "MojoGelu", "MojoS
 # semantics of the reference's `MojoSWA(is_causal=False)`), the tower's 2-D rotary pair and the decoder's multimodal RoPE.  A set
 # of its own likewise (golden: tests/vision_tower_golden.py)
 VISION_TOWER_OPS = ("MojoPackedSdpa", "MojoVisionRotaryEmbedding2D", "MojoApplyVisionRoPE2D", "MojoMRoPE", "MojoMRoPEInplace")
+# the first operation of a decode step: token ids to hidden states.  The plain and the vocabulary-parallel embedding lookup, the
+# over-encoding layer (n-gram ids, the fused gather of the original and the mega table's rows, the up projection) and the
+# packed-NF4 lookup its mega table may be stored as.  A set of its own likewise (golden: tests/embedding_golden.py)
+EMBEDDING_OPS = ("MojoEmbedding", "MojoParallelEmbedding", "MojoOverEncodingNGram", "MojoOverEncoding", "MojoNF4DequantEmbedding")
