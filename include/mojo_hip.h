@@ -923,6 +923,43 @@ int mojo_hip_over_encoding_concat(const void* input_ids, const void* history, co
                                   int64_t mega_row_stride, int64_t group_size, int64_t mega_vocab_start, int mega_nf4,
                                   int scale_dtype, void* out, int64_t out_row_stride, int dtype, mojo_stream_t stream);
 
+/* ---- The short-convolution ops (SHORT_CONV_OPS: MojoCausalConv1dUpdateState, MojoCausalConv1d; core/operators/convolution.py):
+ *      the depthwise causal convolution of width 2..4 in front of a linear-attention or state-space mixer, forward only.
+ *      For every sequence s and channel d, with cat = [state_in[s][d][0 .. S) | x[s][0 .. T)] (state_in == NULL: S zeros):
+ *        out[s][t][d]      = act(bias[d] + sum_k weight[d][k] * cat[S + t - (W - 1) + k])        k = 0 .. W - 1
+ *        state_out[s][d][j] = cat[T + j]                                                          j = 0 .. S - 1
+ *      fp32 arithmetic in ONE order: acc = bias (or +0.0), then acc = acc + weight[k] * cat[..] for k = 0 .. W - 1, the product and
+ *      the sum each rounded on their own (no fused multiply-add); silu != 0 applies SiLU to the fp32 accumulator
+ *      (mojo_hip_activation's function); one rounding to dtype; then, with residual, storage(out) + residual in fp32 rounded again.
+ *      x, weight [dim][width] dense, bias [dim], states, residual and out share dtype (f32 / f16 / bf16).  width 2, 3 or 4;
+ *      width - 1 <= state_len <= 8; anything else MOJO_EUNSUPPORTED.
+ *      Batched (cu_seqlens == NULL): batch sequences of seq_len tokens.  Packed: cu_seqlens int32 / int64 (cu_i64) [batch + 1] ON
+ *      THE DEVICE (no host synchronisation, graph-capturable), seq_len = the packed token count, the batch strides unused; a bound
+ *      is clamped into [0, seq_len], a token outside every sequence gets zeros, and no tap crosses a sequence start.
+ *      x, out and residual are addressed by (batch, time, dim) strides in elements; the states [batch][dim][state_len] by
+ *      (batch, dim) strides with the columns dense.  The kernel follows x: x_time_stride == 1 (batched) takes the
+ *      time-contiguous forms and needs out / residual time strides of 1; else x_dim_stride == 1 takes the channel-contiguous
+ *      form and needs out / residual dim strides of 1; anything else MOJO_EINVAL (the caller makes x dense).
+ *      Channel-contiguous: a thread owns one vector of channels (16 bytes, else 8, else 4, else one element, by what dim, bases
+ *      and strides allow) and walks a run of run_tokens() consecutive tokens with the last W - 1 inputs in registers.  Tags
+ *      `causal_conv1d:channel:vec<V>:<batched|packed>`.
+ *      Time-contiguous: seq_len <= row_thread_max_t() one thread per (sequence, channel) row (`causal_conv1d:time:row`); longer
+ *      rows in 16-byte vectors with the head and tail of every row peeled when x, out and residual rows are misaligned alike
+ *      (`causal_conv1d:time:vec<V>`), single elements otherwise (`causal_conv1d:time:vec1`).
+ *      state_out may be state_in in the BATCHED forms (the in-place update of MojoCausalConv1dUpdateState): the one thread
+ *      that reads a row's old state is the one that writes its new state, after its reads, and no other thread touches that
+ *      row.  Packed: MOJO_EINVAL when they are the same pointer (the caller must reject any overlap).  seq_len == 0 writes
+ *      nothing in the batched forms (the state stays); packed, every sequence is empty and state_out = state_in or zeros. */
+int64_t mojo_hip_causal_conv1d_run_tokens(void);
+int64_t mojo_hip_causal_conv1d_row_thread_max_t(void);
+int mojo_hip_causal_conv1d(const void* x, const void* weight, const void* bias, const void* residual, const void* state_in,
+                           void* state_out, void* out, const void* cu_seqlens, int cu_i64, int64_t batch, int64_t seq_len,
+                           int64_t dim, int64_t width, int64_t state_len, int64_t x_batch_stride, int64_t x_time_stride,
+                           int64_t x_dim_stride, int64_t out_batch_stride, int64_t out_time_stride, int64_t out_dim_stride,
+                           int64_t res_batch_stride, int64_t res_time_stride, int64_t res_dim_stride,
+                           int64_t state_in_batch_stride, int64_t state_in_dim_stride, int64_t state_out_batch_stride,
+                           int64_t state_out_dim_stride, int silu, int dtype, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,17 +19,18 @@ one more; its golden is ``tests/dit_block_golden.py``.  ``VISION_TOWER_OPS`` (wh
 attention, the vision tower's 2-D rotary pair, the decoder's multimodal RoPE) is one more; its golden is
 ``tests/vision_tower_golden.py``.  ``EMBEDDING_OPS`` (token ids to hidden states: the plain and the vocabulary-parallel
 embedding, the over-encoding layer with its n-gram ids and the packed-NF4 lookup) is one more; its golden is
-``tests/embedding_golden.py``.
+``tests/embedding_golden.py``.  ``SHORT_CONV_OPS`` (the depthwise causal short convolution in front of a linear-attention or
+state-space mixer: the prefill forward and the state update) is one more; its golden is ``tests/short_conv_golden.py``.
 """
 from .core import *  # noqa: F401,F403
 from .core import __all__ as _core_all
 from .core import (BEYOND_SURVEY_OPS, EXTENDED_OPS, KV_INT8_OPS, KV_INT8_SWA_OPS, NSTEP_KV_INT8_OPS, NSTEP_OPS,  # noqa: F401
                    DIT_BLOCK_OPS, FULL_ATTN_OPS, PACKED_ATTN_OPS, QUANT_DENSE_OPS, QUANT_MOE_OPS, SAMPLING_OPS, VISION_TOWER_OPS,
-                   EMBEDDING_OPS)
+                   EMBEDDING_OPS, SHORT_CONV_OPS)
 from . import core as _core
 from . import backends  # noqa: F401  (registers HIP<Op> classes)
 from .paged_cache import PagedDummyCache  # noqa: E402  device-side block allocator (SURVEY §8 f4)
 
 __all__ = list(_core_all) + ["PagedDummyCache"]
-globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS + NSTEP_OPS + NSTEP_KV_INT8_OPS + PACKED_ATTN_OPS + FULL_ATTN_OPS + QUANT_DENSE_OPS + DIT_BLOCK_OPS + VISION_TOWER_OPS + EMBEDDING_OPS})   # beyond §8: not in __all__
+globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS + NSTEP_OPS + NSTEP_KV_INT8_OPS + PACKED_ATTN_OPS + FULL_ATTN_OPS + QUANT_DENSE_OPS + DIT_BLOCK_OPS + VISION_TOWER_OPS + EMBEDDING_OPS + SHORT_CONV_OPS})   # beyond §8: not in __all__
 __version__ = "0.1.0"

@@ -6,6 +6,7 @@ the registry ignores them; on a ROCm host they are the first-priority backend.
 from .operators.attention import *  # noqa: F401,F403
 from .operators.kv_int8 import *  # noqa: F401,F403
 from .operators.streaming import *  # noqa: F401,F403
+from .operators.convolution import HIPCausalConv1d, HIPCausalConv1dUpdateState  # noqa: F401
 from .operators.embedding import (HIPEmbedding, HIPNF4DequantEmbedding, HIPOverEncoding, HIPOverEncodingNGram,  # noqa: F401
                                   HIPParallelEmbedding)
 from .operators.gemm import HIPGemm, HIPGroupGemm, HIPQuantGemm, HIPSwiGLUMLP  # noqa: F401

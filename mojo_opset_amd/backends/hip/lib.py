@@ -150,6 +150,9 @@ SIGNATURES = {
     "mojo_hip_oe_ngram": (c_int, [_P] * 7 + [_I] * 8 + [c_int, _P]),
     "mojo_hip_over_encoding_concat": (c_int, [_P] * 6 + [_I] * 8 + [c_int, _P] + [_I] * 3 + [_P] * 4 + [_I] * 5 +
                                       [c_int, c_int, _P, _I, c_int, _P]),
+    "mojo_hip_causal_conv1d_run_tokens": (c_int64, []),
+    "mojo_hip_causal_conv1d_row_thread_max_t": (c_int64, []),
+    "mojo_hip_causal_conv1d": (c_int, [_P] * 8 + [c_int] + [_I] * 18 + [c_int, c_int, _P]),
 }
 
 _lock = threading.Lock()

@@ -1,5 +1,6 @@
 from .attention import *  # noqa: F401,F403
 from .kv_int8 import *  # noqa: F401,F403
+from .convolution import HIPCausalConv1d, HIPCausalConv1dUpdateState  # noqa: F401
 from .embedding import (HIPEmbedding, HIPNF4DequantEmbedding, HIPOverEncoding, HIPOverEncodingNGram,  # noqa: F401
                         HIPParallelEmbedding)
 from .gemm import HIPGemm, HIPGroupGemm, HIPQuantGemm, HIPSwiGLUMLP  # noqa: F401

@@ -5,6 +5,7 @@ from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, Moj
                         MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoPackedSdpa, MojoSdpa,
                         MojoSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
+from .convolution import MojoCausalConv1d, MojoCausalConv1dUpdateState
 from .embedding import MojoEmbedding, MojoParallelEmbedding
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
 from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
@@ -71,3 +72,7 @@ VISION_TOWER_OPS = ("MojoPackedSdpa", "MojoVisionRotaryEmbedding2D", "MojoApplyV
 # over-encoding layer (n-gram ids, the fused gather of the original and the mega table's rows, the up projection) and the
 # packed-NF4 lookup its mega table may be stored as.  A set of its own likewise (golden: tests/embedding_golden.py)
 EMBEDDING_OPS = ("MojoEmbedding", "MojoParallelEmbedding", "MojoOverEncodingNGram", "MojoOverEncoding", "MojoNF4DequantEmbedding")
+# the depthwise causal "short convolution" (width 2..4, optional SiLU) in front of every linear-attention or state-space mixer:
+# the reference's update-state op and the forward of its `MojoCausalConv1dFunction` as an inference operator (the reference has no
+# operator class of that name).  A set of its own likewise (golden: tests/short_conv_golden.py)
+SHORT_CONV_OPS = ("MojoCausalConv1dUpdateState", "MojoCausalConv1d")

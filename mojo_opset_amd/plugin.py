@@ -55,7 +55,7 @@ def rebase_hip_backend(reference, platforms: Optional[Sequence[str]] = None) -> 
     # the §8 set and the ops beyond it (a name the reference has no class for, as NSTEP_KV_INT8_OPS' today, is skipped below)
     for name in (list(mine.__all__) + list(mine.BEYOND_SURVEY_OPS) + list(mine.NSTEP_OPS) + list(mine.NSTEP_KV_INT8_OPS) +
                  list(mine.PACKED_ATTN_OPS) + list(mine.FULL_ATTN_OPS) + list(mine.QUANT_DENSE_OPS) + list(mine.DIT_BLOCK_OPS) +
-                 list(mine.VISION_TOWER_OPS) + list(mine.EMBEDDING_OPS)):
+                 list(mine.VISION_TOWER_OPS) + list(mine.EMBEDDING_OPS) + list(mine.SHORT_CONV_OPS)):
         if not name.startswith("Mojo") or name in ("MojoOperator", "MojoBackendRegistry"):
             continue
         hip_cls = getattr(hip_pkg, "HIP" + name[4:], None)
