@@ -960,6 +960,30 @@ int mojo_hip_causal_conv1d(const void* x, const void* weight, const void* bias, 
                            int64_t state_in_batch_stride, int64_t state_in_dim_stride, int64_t state_out_batch_stride,
                            int64_t state_out_dim_stride, int silu, int dtype, mojo_stream_t stream);
 
+/* ---- The int8-compute prefill (SAGE_ATTN_OPS: MojoPagedPrefillSageGQA; core/operators/attention.py): causal paged
+ *      prefill whose two contractions are int8 products with int32 accumulators (v_mfma_i32_16x16x64_i8).
+ *      query [tokens, hq, dim] int8 dense, query_scale [hq, tokens] fp32 dense; key_cache / value_cache [n_blocks, hkv, page, dim]
+ *      int8, dense in dim, one set of strides (in bytes = elements, multiples of 16); key_scale [n_blocks, hkv, page] fp32 dense;
+ *      value_scale [hkv, dim] fp32 dense; cu_q_lens / cu_total_seq_lens int32 [batch + 1] (the latter NULL: kv_len = q_len);
+ *      block_tables int32, row stride table_stride; out [tokens, hq, dim] bf16 dense.  For score row (t, h), kv head kh:
+ *        s[j] = ((float(q8 . k8[j]) * softmax_scale) * query_scale[h][t]) * key_scale[j][kh]      (fp32, in this order)
+ *        p[j] = rint(exp(s[j] - max_visible s) * 127), 0 for a hidden key
+ *        out  = bf16(float(sum_j p[j] v8[j][d]) * value_scale[kh][d] / float(sum_j p[j]))
+ *      Two passes over the keys (maxima, then probabilities), no workspace, no atomics on memory: two calls give the same bits.
+ *      Envelope: dim 64 / 128, page a multiple of 16 up to 256, hq / hkv in {1, 2, 4, 8}; MOJO_EUNSUPPORTED otherwise, and when
+ *      min(max_total_seq_len if > 0, page * max_pages) exceeds 132104 keys (127 * 128 * kv_len must stay below 2^31).
+ *      max_q_len / max_total_seq_len <= 0: no hint.  A length above its hint is cut to the hint (rows past max_q_len are zeros,
+ *      keys past max_total_seq_len or past the table's width are not seen).  Every key from the first page id that is negative
+ *      or >= n_blocks on is a zero K / V row (score 0, counted in the row sum).  Rows of a sequence without keys, rows that see
+ *      no key (kv_len < q_len) and rows at or past cu_q_lens[batch] are zeros.  Tag `sage_prefill:d<dim>:g<group>`. */
+int mojo_hip_paged_prefill_sage_gqa(const void* query, const void* query_scale, const void* key_cache, const void* key_scale,
+                                    const void* value_cache, const void* value_scale, const void* cu_q_lens,
+                                    const void* cu_total_seq_lens, const void* block_tables, void* out, int64_t tokens,
+                                    int64_t batch, int64_t hq, int64_t hkv, int64_t dim, int64_t n_blocks, int64_t page,
+                                    int64_t max_pages, int64_t table_stride, int64_t cache_block_stride,
+                                    int64_t cache_head_stride, int64_t cache_token_stride, int64_t max_q_len,
+                                    int64_t max_total_seq_len, float softmax_scale, int abab, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

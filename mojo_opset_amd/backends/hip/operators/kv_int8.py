@@ -1,6 +1,7 @@
 """HIP<Op> classes of the int8 paged KV cache with per-channel scales: the quantising store, the decode / prefill
-GQA that read it, their sliding-window forms and the n-step decode.  Everything that is not built raises ``NotImplementedError`` on the host, before any
-device work."""
+GQA that read it, their sliding-window forms and the n-step decode.  These ops contract in 16 bits: ``compute_dtype=torch.int8`` and quantised queries raise ``NotImplementedError`` here, on the host,
+before any device work, like everything else that is not built.  int8 COMPUTE (int8 query, per-token K scales, quantised
+probabilities, both contractions on the int8 matrix cores) is `HIPPagedPrefillSageGQA` in ``sage.py``."""
 from typing import Optional
 
 import torch

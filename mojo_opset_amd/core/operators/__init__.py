@@ -1,7 +1,7 @@
 from .activation import MojoGelu, MojoSilu, MojoSwiGLU
 from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
                         MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
-                        MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant,
+                        MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillSageGQA,
                         MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoPackedSdpa, MojoSdpa,
                         MojoSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
@@ -76,3 +76,7 @@ EMBEDDING_OPS = ("MojoEmbedding", "MojoParallelEmbedding", "MojoOverEncodingNGra
 # the reference's update-state op and the forward of its `MojoCausalConv1dFunction` as an inference operator (the reference has no
 # operator class of that name).  A set of its own likewise (golden: tests/short_conv_golden.py)
 SHORT_CONV_OPS = ("MojoCausalConv1dUpdateState", "MojoCausalConv1d")
+# int8-COMPUTE paged prefill (SageAttention style): int8 query with per-token scales, int8 K cache with per-token scales, int8 V
+# cache with per-channel scales, probabilities quantised to [0, 127]; both contractions are int8 products.  A set of its own
+# likewise (golden: the core class's own `forward`, checked against tests/sage_golden.py)
+SAGE_ATTN_OPS = ("MojoPagedPrefillSageGQA",)

@@ -253,6 +253,78 @@ class MojoPagedPrefillGQAWithKVDequant(_PagedGQAKVDequantBase, MojoOperator):
         self._init_kv_dequant(is_causal, gqa_layout, query_dtype, context_dtype, compute_dtype)
 
 
+class MojoPagedPrefillSageGQA(_PagedGQABase, MojoOperator):
+    """Causal paged prefill with int8 COMPUTE (SageAttention style; `SAGE_ATTN_OPS`): an int8 query with per-token scales, an
+    int8 K cache with per-token scales, an int8 V cache with per-channel scales, and probabilities quantised to ``[0, 127]``, so
+    that Q.K^T and P.V are both int8 products with exact integer sums.
+
+    forward(query [T,Hq,D] int8, query_scale [Hq,T] fp32, key_cache [N,Hkv,page,D] int8, key_scale [N,Hkv,page] fp32,
+            value_cache [N,Hkv,page,D] int8, value_scale [Hkv,D] fp32, cu_q_lens [B+1] i32, block_tables [B,nb] i32,
+            softmax_scale=None, cu_total_seq_lens=None, mask=None, max_q_len=None, max_total_seq_len=None) -> [T,Hq,D] bf16
+
+    For query row ``(t, h)`` of a sequence of ``kv_len`` keys, ``kh`` the kv head of ``h``:
+
+    1. ``dot[j] = sum_d q8[t,h,d] * k8[j,kh,d]`` (an exact integer);
+    2. ``s[j] = ((float(dot[j]) * softmax_scale) * query_scale[h,t]) * key_scale[j,kh]``, every product fp32, in this order;
+    3. key ``j`` is visible iff ``j <= kv_len - q_len + (t - seq_start)``; ``m = max s[j]`` over the visible keys;
+    4. ``p[j] = round_half_even(exp(s[j] - m) * 127)`` for a visible key, 0 for a hidden one: quantised against the FINAL maximum;
+    5. ``out[t,h,d] = bf16(value_scale[kh,d] * (sum_j p[j] * v8[j,kh,d]) / (sum_j p[j]))`` - the divisor is the sum of the
+       QUANTISED probabilities (the ``1/127`` of both sums cancels).
+
+    Rows of a sequence with ``q_len == 0`` or ``kv_len <= 0``, and rows that see no key (``kv_len < q_len``), are zeros.
+
+    ``forward`` below is the golden.  The scores are fp32 as stated; ``exp``, the rounding and the final quotient are evaluated
+    in fp64 so that the integers ``p`` do not depend on the host's vectorised fp32 ``exp``."""
+
+    def __init__(self, is_causal: bool = True, gqa_layout: str = "AABB", query_dtype: torch.dtype = torch.int8,
+                 context_dtype: torch.dtype = torch.int8, compute_dtype: torch.dtype = torch.int8):
+        super().__init__()
+        self._init_gqa(is_causal, gqa_layout)
+        assert query_dtype == torch.int8, f"MojoPagedPrefillSageGQA: int8 query only, got {query_dtype}"
+        assert context_dtype == torch.int8, f"MojoPagedPrefillSageGQA: int8 context only, got {context_dtype}"
+        assert compute_dtype == torch.int8, f"MojoPagedPrefillSageGQA: int8 compute only, got {compute_dtype}"
+        self.query_dtype, self.context_dtype, self.compute_dtype = query_dtype, context_dtype, compute_dtype
+
+    def forward(self, query, query_scale, key_cache, key_scale, value_cache, value_scale, cu_q_lens, block_tables,
+                softmax_scale: Optional[float] = None, cu_total_seq_lens: Optional[torch.Tensor] = None,
+                mask: Optional[torch.Tensor] = None, max_q_len: Optional[int] = None,
+                max_total_seq_len: Optional[int] = None):
+        assert_paged_prefill_contract(cu_q_lens, block_tables, cu_total_seq_lens)
+        assert mask is None and self.is_causal, "MojoPagedPrefillSageGQA: causal attention without an explicit mask only"
+        tokens, hq, dim = query.shape
+        hkv, page = key_cache.shape[1], key_cache.shape[2]
+        group = hq // hkv
+        scale = torch.tensor(dim ** -0.5 if softmax_scale is None else softmax_scale, dtype=torch.float32)
+        heads = torch.arange(hq)
+        kv_of = heads % hkv if self.gqa_layout == "ABAB" else heads // group
+        out = torch.zeros(tokens, hq, dim, dtype=torch.bfloat16, device=query.device)
+        cu_q = cu_q_lens.tolist()
+        cu_kv = cu_q if cu_total_seq_lens is None else cu_total_seq_lens.tolist()
+        for b in range(len(cu_q) - 1):
+            q0, q_len, kv_len = cu_q[b], cu_q[b + 1] - cu_q[b], cu_kv[b + 1] - cu_kv[b]
+            if q_len <= 0 or kv_len <= 0:
+                continue
+            pages = block_tables[b, :(kv_len + page - 1) // page].long()
+            k8 = key_cache[pages].transpose(1, 2).reshape(-1, hkv, dim)[:kv_len]          # [kv, Hkv, D]
+            v8 = value_cache[pages].transpose(1, 2).reshape(-1, hkv, dim)[:kv_len]
+            ks = key_scale[pages].transpose(1, 2).reshape(-1, hkv)[:kv_len].float()       # [kv, Hkv]
+            q8 = query[q0:q0 + q_len]                                                     # [q, Hq, D]
+            dot = torch.einsum("qhd,khd->hqk", q8.double(), k8[:, kv_of].double())        # exact: |dot| < 2^53
+            s = ((dot.float() * scale) * query_scale[:, q0:q0 + q_len].float()[:, :, None]) * ks[:, kv_of].T[:, None, :]
+            visible = torch.arange(kv_len)[None, :] <= (kv_len - q_len + torch.arange(q_len))[:, None]
+            m = s.masked_fill(~visible, float("-inf")).amax(dim=-1, keepdim=True)
+            p = torch.where(visible, torch.round(torch.exp((s - m).double()) * 127), 0.0)  # [Hq, q, kv] integers
+            num = torch.einsum("hqk,khd->qhd", p, v8[:, kv_of].double())                  # exact integer sums
+            den = p.sum(dim=-1).T[:, :, None]                                             # [q, Hq, 1]
+            o = value_scale.double()[kv_of][None] * num / den
+            out[q0:q0 + q_len] = torch.where(den > 0, o, 0.0).to(torch.bfloat16)
+        return out
+
+    def extra_repr(self) -> str:
+        return (f"is_causal={self.is_causal!r}, gqa_layout={self.gqa_layout!r}, query_dtype={self.query_dtype!r}, "
+                f"context_dtype={self.context_dtype!r}, compute_dtype={self.compute_dtype!r}")
+
+
 class _PagedSWAKVDequantBase:
     """Constructor of the windowed int8-cache pair (`mojo_opset/experimental/operators/attention.py:806-848`, :988-1030):
     the attributes of `_PagedSWABase` and of `_PagedGQAKVDequantBase` together — ``is_causal``, ``gqa_layout``,

@@ -21,6 +21,9 @@ OBJ_DIR = os.path.join(HERE, "build")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmojo_hip.so")
 ARCH = "gfx950"
+# flags of single units, behind the common ones: no packed fp32 VALU forms (v_pk_mul_f32 and kin) in the score / exp chains of the
+# int8 prefill, whose integers must be the golden's
+UNIT_FLAGS = {"sage_prefill.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -82,7 +85,8 @@ def build(force: bool = False, jobs: int = 4, verbose: bool = True) -> str:
         obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + ".o")
         stamped = os.path.basename(src) == "api_common.hip"          # the one file that carries the source hash
         if force or _stale(obj, [src] + headers) or (stamped and stamp_changed):
-            cmd = [hipcc, *flags, *([f'-DMOJO_SRC_HASH="{src_hash}"'] if stamped else []), "-c", src, "-o", obj]
+            cmd = [hipcc, *flags, *UNIT_FLAGS.get(os.path.basename(src), []),
+                   *([f'-DMOJO_SRC_HASH="{src_hash}"'] if stamped else []), "-c", src, "-o", obj]
             if verbose:
                 print("[mojo_hip] hipcc", os.path.basename(src), flush=True)
             res = subprocess.run(cmd, capture_output=True, text=True)
