@@ -984,6 +984,40 @@ int mojo_hip_paged_prefill_sage_gqa(const void* query, const void* query_scale, 
                                     int64_t cache_head_stride, int64_t cache_token_stride, int64_t max_q_len,
                                     int64_t max_total_seq_len, float softmax_scale, int abab, mojo_stream_t stream);
 
+/* ---- Native sparse attention, decode (NSA_ATTN_OPS: MojoDecodeNSA, MojoPagedDecodeNSA; core/operators/attention.py, DESIGN
+ *      4.28).  MHA: query [batch, heads, dim] dense, K / V with the same heads, out as query; gate_proj [heads, dim, 3] dense,
+ *      gate_dtype = dtype or MOJO_F32; dtype MOJO_BF16 / MOJO_F16.  For a sequence of sl keys and one head, with
+ *      s_t = softmax_scale * q . k_t (fp32), cr = compress_ratio, bs = block_size, C = sl / cr, nb = ceil(sl / bs):
+ *        compressed  c_j = mean of s_t over group j (t in [j cr, j cr + cr), j < C), pc = softmax_j(c_j);
+ *        selection   block b scores the sum of pc_j over its bs / cr groups with j < C (0 without one); the
+ *                    min(num_selected_blocks, nb) highest blocks are taken, the LOWER index first among equal scores;
+ *                    psel = softmax of s_t over the keys of the taken blocks;
+ *        window      pwin = softmax of s_t over the last min(window_size, sl) keys;
+ *        gate        g = sigmoid(q . gate_proj[h]) (three values);
+ *        out = sum_t (g0 pc[t / cr] / cr [t < C cr] + g1 psel_t + g2 pwin_t) v_t, fp32, rounded once.  sl <= 0: zeros.
+ *      Paged (block_tables != NULL): key / value [num_blocks, heads, page, dim], strides in elements, block_tables int32 with
+ *      row stride table_stride and max_pages columns, total_seq_lens int32 [batch]; a length above page * max_pages is cut to
+ *      it.  Every key from the first page id that is negative or >= num_blocks on is a zero K / V row (score 0, counted by
+ *      the three softmaxes); such a page is never read.  Contiguous (block_tables == NULL): key / value [batch, S, heads,
+ *      dim] given as page = S, max_pages = 1, kv_block_stride = the batch stride; total_seq_lens may be NULL (sl = S).
+ *      Envelope (MOJO_EUNSUPPORTED otherwise): dim 64 / 128, block_size % compress_ratio == 0, num_selected_blocks <= 64,
+ *      paged pages of a multiple of 16 tokens up to 256, strides multiples of 8 elements, ceil(capacity / block_size) <= 8192.
+ *      num_splits: 0 = planned from the shapes, 1 = the fused form (one launch, the score row in LDS; refused when
+ *      4 * (capacity + capacity / cr + capacity / bs) bytes exceed 56 KiB), > 1 = the split form with that many key slices
+ *      (scores, select, values, merge: four launches, rows and partials in the workspace).  Planned: fused when it fits and
+ *      batch * heads >= 256, else split into ceil(512 / (batch * heads)) slices of at least 256 keys.  The workspace query
+ *      answers 0 for the fused form and -1 for a refused geometry.  No atomics: two calls give the same bits.
+ *      Tags `nsa_decode:fused:d<dim>`, `nsa_decode:split<slices>:d<dim>`.                                                  */
+int64_t mojo_hip_nsa_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t head_dim, int64_t kv_capacity,
+                                            int64_t compress_ratio, int64_t block_size, int64_t num_splits);
+int mojo_hip_nsa_decode(const void* query, const void* key, const void* value, const void* gate_proj,
+                        const int32_t* total_seq_lens, const int32_t* block_tables, void* out, void* workspace,
+                        int64_t workspace_bytes, int64_t batch, int64_t heads, int64_t head_dim, int64_t num_blocks,
+                        int64_t page, int64_t max_pages, int64_t table_stride, int64_t kv_block_stride,
+                        int64_t kv_head_stride, int64_t kv_token_stride, int64_t compress_ratio, int64_t block_size,
+                        int64_t num_selected_blocks, int64_t window_size, float softmax_scale, int dtype, int gate_dtype,
+                        int64_t num_splits, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

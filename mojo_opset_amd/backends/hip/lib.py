@@ -154,6 +154,8 @@ SIGNATURES = {
     "mojo_hip_causal_conv1d_row_thread_max_t": (c_int64, []),
     "mojo_hip_causal_conv1d": (c_int, [_P] * 8 + [c_int] + [_I] * 18 + [c_int, c_int, _P]),
     "mojo_hip_paged_prefill_sage_gqa": (c_int, [_P] * 10 + [_I] * 14 + [c_float, c_int, _P]),
+    "mojo_hip_nsa_decode_workspace_bytes": (c_int64, [_I] * 7),
+    "mojo_hip_nsa_decode": (c_int, [_P] * 8 + [_I] * 15 + [c_float, c_int, c_int, _I, _P]),
 }
 
 _lock = threading.Lock()

@@ -1,6 +1,6 @@
 from .activation import MojoGelu, MojoSilu, MojoSwiGLU
-from .attention import (MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
-                        MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
+from .attention import (MojoDecodeNSA, MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
+                        MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeNSA, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
                         MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillSageGQA,
                         MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoPackedSdpa, MojoSdpa,
                         MojoSWA)
@@ -80,3 +80,7 @@ SHORT_CONV_OPS = ("MojoCausalConv1dUpdateState", "MojoCausalConv1d")
 # cache with per-channel scales, probabilities quantised to [0, 127]; both contractions are int8 products.  A set of its own
 # likewise (golden: the core class's own `forward`, checked against tests/sage_golden.py)
 SAGE_ATTN_OPS = ("MojoPagedPrefillSageGQA",)
+# native sparse attention, decode: the compressed, selected and window branches of one step blended by a per-head gate, over
+# contiguous K/V and over a paged cache.  A set of its own likewise (golden: the core classes' own `forward`, checked against
+# tests/nsa_golden.py); the prefill pair of the reference is not built
+NSA_ATTN_OPS = ("MojoDecodeNSA", "MojoPagedDecodeNSA")

@@ -325,6 +325,125 @@ class MojoPagedPrefillSageGQA(_PagedGQABase, MojoOperator):
                 f"context_dtype={self.context_dtype!r}, compute_dtype={self.compute_dtype!r}")
 
 
+class _NSADecodeBase:
+    """Constructor and per-sequence golden of the native-sparse-attention decode pair (`NSA_ATTN_OPS`;
+    `mojo_opset/experimental/operators/attention.py:1266-1485`).  MHA: K/V have the query's ``H`` heads.  For one sequence of
+    ``sl`` keys and one head, with ``scale = softmax_scale or 1/sqrt(D)``, ``cr = compress_ratio``, ``bs = block_size`` (the
+    SELECTION block, not the cache page), ``nsel = num_selected_blocks``, ``ws = window_size``:
+
+    * compressed: ``C = sl // cr`` groups of ``cr`` consecutive keys (the ``sl % cr`` tail keys are in no group), ``ck_j`` /
+      ``cv_j`` the group means, ``pc = softmax_j(scale * q.ck_j)``, ``out_comp = sum_j pc_j cv_j``; zeros when ``C == 0``;
+    * selection: block ``b`` of ``nb = ceil(sl / bs)`` scores the sum of ``pc_j`` over its ``bs // cr`` groups with
+      ``j < C`` (0 without one); the ``min(nsel, nb)`` highest blocks are taken per head — AMONG EQUAL SCORES THE LOWER BLOCK
+      INDEX FIRST (this project's rule: the reference's ``torch.topk`` leaves ties unspecified) — and ``out_sel`` is softmax
+      attention over the keys of the taken blocks, the partial last block included;
+    * window: ``out_win`` is softmax attention over the last ``min(ws, sl)`` keys;
+    * ``g = sigmoid(q . gate_proj[h])`` (three values, parameter ``gate_proj [H, D, 3]``) and
+      ``out = g0 out_comp + g1 out_sel + g2 out_win``.  A sequence with ``sl <= 0`` gives zeros; ``is_causal`` has no effect.
+
+    ``forward`` of the two classes is the golden, with the reference's roundings: group means rounded to the storage dtype,
+    score einsums in the storage dtype, probabilities cast to it before P.V, each branch and the gate in it.  A backend that
+    keeps scores, probabilities and the weighted sum in fp32 and rounds once (the HIP one) stays inside the reference's
+    ``atol = rtol = 1e-2``; where two block scores are closer than these roundings' noise the two may take different blocks."""
+
+    def _init_nsa(self, num_heads, head_dim, compress_ratio, num_selected_blocks, block_size, window_size, is_causal):
+        self.num_heads, self.head_dim = num_heads, head_dim
+        self.compress_ratio, self.num_selected_blocks = compress_ratio, num_selected_blocks
+        self.block_size, self.window_size, self.is_causal = block_size, window_size, is_causal
+        self.gate_proj = torch.nn.Parameter(torch.empty(num_heads, head_dim, 3))
+
+    def extra_repr(self) -> str:
+        return (f"num_heads={self.num_heads}, head_dim={self.head_dim}, compress_ratio={self.compress_ratio}, "
+                f"num_selected_blocks={self.num_selected_blocks}, block_size={self.block_size}, "
+                f"window_size={self.window_size}, is_causal={self.is_causal}")
+
+    @staticmethod
+    def _attend(q, k, v, scale, mask=None):
+        """q [H,D], k / v [S,H,D] -> [H,D]: fp32 softmax of the storage-dtype scores, probabilities back in the storage dtype."""
+        scores = torch.einsum("hd,shd->hs", q, k).float() * scale
+        if mask is not None:
+            scores = scores.masked_fill(~mask, float("-inf"))
+        probs = torch.nan_to_num(torch.softmax(scores, dim=-1, dtype=torch.float32).to(q.dtype), nan=0.0)
+        return torch.einsum("hs,shd->hd", probs, v)
+
+    def _decode_one(self, q, k, v, scale):
+        sl, heads, dim = k.shape
+        cr, bs = self.compress_ratio, self.block_size
+        n_groups, nb = sl // cr, (sl + bs - 1) // bs
+        ck = k[:n_groups * cr].reshape(n_groups, cr, heads, dim).mean(dim=1)
+        cv = v[:n_groups * cr].reshape(n_groups, cr, heads, dim).mean(dim=1)
+        pc = (torch.einsum("hd,chd->hc", q, ck) * scale).softmax(dim=-1, dtype=torch.float32)
+        block_score = torch.zeros(heads, nb, dtype=torch.float32, device=q.device)
+        for b in range(nb):
+            if b * (bs // cr) < n_groups:
+                block_score[:, b] = pc[:, b * (bs // cr):min((b + 1) * (bs // cr), n_groups)].sum(dim=-1)
+        taken = torch.sort(block_score, dim=-1, descending=True, stable=True).indices[:, :min(self.num_selected_blocks, nb)]
+        block_mask = torch.zeros(heads, nb, dtype=torch.bool, device=q.device).scatter_(1, taken, True)
+        mask = block_mask.repeat_interleave(bs, dim=1)[:, :sl]
+        start = max(0, sl - self.window_size)
+        g = torch.sigmoid(torch.einsum("hd,hdc->hc", q, self.gate_proj.to(q.dtype)))
+        return (g[:, 0:1] * self._attend(q, ck, cv, scale) + g[:, 1:2] * self._attend(q, k, v, scale, mask) +
+                g[:, 2:3] * self._attend(q, k[start:], v[start:], scale))
+
+
+class MojoDecodeNSA(_NSADecodeBase, MojoOperator):
+    """Native sparse attention, one query token per sequence over contiguous K/V (see `_NSADecodeBase`).
+
+    forward(query [B,H,D], key [B,S,H,D], value [B,S,H,D], total_seq_lens=None ([B] i32; None: S), softmax_scale=None)
+    -> [B,H,D]"""
+
+    def __init__(self, num_heads, head_dim, compress_ratio=4, num_selected_blocks=16, block_size=64, window_size=512,
+                 is_causal=True, **kwargs):
+        super().__init__(**kwargs)
+        self._init_nsa(num_heads, head_dim, compress_ratio, num_selected_blocks, block_size, window_size, is_causal)
+
+    def forward(self, query, key, value, total_seq_lens: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None):
+        if total_seq_lens is not None:
+            assert total_seq_lens.dtype == torch.int32
+        scale = query.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale
+        out = torch.zeros_like(query)
+        lens = [key.shape[1]] * query.shape[0] if total_seq_lens is None else total_seq_lens.tolist()
+        for i, sl in enumerate(lens):
+            if sl > 0:
+                out[i] = self._decode_one(query[i], key[i, :sl], value[i, :sl], scale)
+        return out
+
+
+class MojoPagedDecodeNSA(_NSADecodeBase, MojoOperator):
+    """Native sparse attention, one query token per sequence over a paged KV cache (see `_NSADecodeBase`).  The cache page
+    and the selection block are independent.  Every key from the first negative or out-of-pool page id on is a zero K / V
+    row; a negative FIRST page id of a sequence with keys raises ``ValueError``.
+
+    forward(query [B,H,D], key_cache / value_cache [N,H,page,D], total_seq_lens [B] i32, block_tables [B,nb] i32,
+            softmax_scale=None) -> [B,H,D]"""
+
+    def __init__(self, num_heads, head_dim, compress_ratio=4, num_selected_blocks=16, block_size=64, window_size=512,
+                 is_causal=True, **kwargs):
+        super().__init__(**kwargs)
+        self._init_nsa(num_heads, head_dim, compress_ratio, num_selected_blocks, block_size, window_size, is_causal)
+
+    def forward(self, query, key_cache, value_cache, total_seq_lens, block_tables, softmax_scale: Optional[float] = None):
+        assert_paged_decode_contract(block_tables, total_seq_lens)
+        n_blocks, heads, page, dim = key_cache.shape
+        scale = dim ** -0.5 if softmax_scale is None else softmax_scale
+        out = torch.zeros_like(query)
+        for i, sl in enumerate(total_seq_lens.tolist()):
+            if sl <= 0:
+                continue
+            ids = block_tables[i, :(sl + page - 1) // page].tolist()
+            if ids[0] < 0:
+                raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
+            bad = [j for j, n in enumerate(ids) if n < 0 or n >= n_blocks]
+            ids = ids[:bad[0]] if bad else ids
+            k = torch.zeros(len(ids) * page + sl, heads, dim, dtype=query.dtype, device=query.device)
+            v = torch.zeros_like(k)
+            if ids:
+                k[:len(ids) * page] = key_cache[ids].transpose(1, 2).reshape(-1, heads, dim)
+                v[:len(ids) * page] = value_cache[ids].transpose(1, 2).reshape(-1, heads, dim)
+            out[i] = self._decode_one(query[i], k[:sl], v[:sl], scale)
+        return out
+
+
 class _PagedSWAKVDequantBase:
     """Constructor of the windowed int8-cache pair (`mojo_opset/experimental/operators/attention.py:806-848`, :988-1030):
     the attributes of `_PagedSWABase` and of `_PagedGQAKVDequantBase` together — ``is_causal``, ``gqa_layout``,
