@@ -1018,6 +1018,44 @@ int mojo_hip_nsa_decode(const void* query, const void* key, const void* value, c
                         int64_t num_selected_blocks, int64_t window_size, float softmax_scale, int dtype, int gate_dtype,
                         int64_t num_splits, mojo_stream_t stream);
 
+/* ---- The gated delta rule (LINEAR_ATTN_OPS: MojoGatedDeltaRule, MojoGatedDeltaRuleUpdateState; core/operators/linear_attention.py):
+ *      per (sequence, value head h) an fp32 state S [dk][dv]; the key head is h / (value_heads / key_heads).  With
+ *      use_qk_l2norm, q^ = q rsqrt(sum q^2 + 1e-6) and k^ likewise, else q^ = q, k^ = k.  For each token in order:
+ *        S = exp(g_t) S;   d = beta_t (v_t - S^T k^_t);   S = S + k^_t (x) d;   o_t = scale S^T q^_t
+ *      q / k [.., key_heads, dk] and v [.., value_heads, dv] are addressed by (batch, token, head) strides in elements
+ *      (64-bit, multiples of 8; the head dimension dense; bases 16-byte aligned), so the column slices of a fused projection
+ *      buffer are read in place.  g (log decay, <= 0) and beta [batch][tokens][value_heads] dense, fp32 or the query's dtype
+ *      (gate_dtype); out [batch][tokens][value_heads][dv] dense; the states fp32 [sequences][value_heads][dk][dv] dense.
+ *      dk, dv 64 or 128, value_heads % key_heads == 0; anything else MOJO_EUNSUPPORTED.  No atomics, no host
+ *      synchronisation, graph-capturable; two calls give the same bits.
+ *      mojo_hip_gated_delta_rule (bf16): the chunked form on the matrix cores, 64 tokens a chunk, one workgroup per
+ *      (sequence, value head, slice of dv_slice state columns); dv_slice 0 = planned (64 once sequences x value_heads x dv / 64
+ *      fills the CUs, else 32), 32 or 64 forces; mojo_hip_gated_delta_rule_dv_slice() answers what a call takes.  Batched
+ *      (cu_seqlens == NULL): `sequences` rows of `tokens` tokens.  Packed: cu_seqlens int32 / int64 (cu_i64) [sequences + 1] ON
+ *      THE DEVICE, tokens = the packed token count, the batch strides unused; a bound is clamped into [0, tokens]; rows outside
+ *      every sequence are not written.  initial_state may be NULL (zeros), final_state may be NULL (not written) and must not be
+ *      initial_state.  A sequence without tokens writes no output and final_state = initial_state or zeros.  Tags
+ *      `gated_delta_rule:chunk64:dk<Dk>:dvs<slice>:<batched|packed>`.
+ *      mojo_hip_gated_delta_rule_update (bf16 / fp16): 1 <= tokens <= 8, batched; `state` is read once and rewritten in place
+ *      with the state after the last token; one fixed order: S^T k^ and d in fp64 (d is a difference of nearly equal numbers once
+ *      the state has learned the key), the decay and the rank-one update one rounding per state element and token, S^T q^ in
+ *      fp32, one rounding of the output.  Tags
+ *      `gated_delta_rule_update:dk<Dk>:t<tokens>`. */
+int64_t mojo_hip_gated_delta_rule_dv_slice(int64_t sequences, int64_t value_heads, int64_t dv, int64_t dv_slice);
+int mojo_hip_gated_delta_rule(const void* q, const void* k, const void* v, const void* g, const void* beta,
+                              const float* initial_state, float* final_state, void* out, const void* cu_seqlens, int cu_i64,
+                              int64_t sequences, int64_t tokens, int64_t key_heads, int64_t value_heads, int64_t dk, int64_t dv,
+                              int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride, int64_t k_batch_stride,
+                              int64_t k_token_stride, int64_t k_head_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                              int64_t v_head_stride, float scale, int use_qk_l2norm, int gate_dtype, int dtype, int64_t dv_slice,
+                              mojo_stream_t stream);
+int mojo_hip_gated_delta_rule_update(const void* q, const void* k, const void* v, const void* g, const void* beta, float* state,
+                                     void* out, int64_t batch, int64_t tokens, int64_t key_heads, int64_t value_heads, int64_t dk,
+                                     int64_t dv, int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride,
+                                     int64_t k_batch_stride, int64_t k_token_stride, int64_t k_head_stride, int64_t v_batch_stride,
+                                     int64_t v_token_stride, int64_t v_head_stride, float scale, int use_qk_l2norm, int gate_dtype,
+                                     int dtype, mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

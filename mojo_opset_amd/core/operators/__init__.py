@@ -8,6 +8,7 @@ from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllRe
 from .convolution import MojoCausalConv1d, MojoCausalConv1dUpdateState
 from .embedding import MojoEmbedding, MojoParallelEmbedding
 from .gemm import MojoGemm, MojoGroupGemm, MojoQuantGemm
+from .linear_attention import MojoGatedDeltaRule, MojoGatedDeltaRuleUpdateState
 from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStorePagedMLAKVCache,
                        build_paged_kv_chunk_metadata)
 from .mla import MojoPagedDecodeMLA, MojoPagedPrefillMLA
@@ -84,3 +85,8 @@ SAGE_ATTN_OPS = ("MojoPagedPrefillSageGQA",)
 # contiguous K/V and over a paged cache.  A set of its own likewise (golden: the core classes' own `forward`, checked against
 # tests/nsa_golden.py); the prefill pair of the reference is not built
 NSA_ATTN_OPS = ("MojoDecodeNSA", "MojoPagedDecodeNSA")
+# the gated delta rule, the mixer behind SHORT_CONV_OPS in a GatedDeltaNet layer (Qwen3-Next, the FLA family): a linear
+# recurrence over an fp32 state per (sequence, value head), as a chunked prefill and a 1..8-token state update.  The reference
+# has no class for either.  A set of its own likewise (golden: the core classes' own `forward`, checked against
+# tests/gated_delta_golden.py)
+LINEAR_ATTN_OPS = ("MojoGatedDeltaRule", "MojoGatedDeltaRuleUpdateState")

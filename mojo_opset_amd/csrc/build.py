@@ -22,9 +22,10 @@ LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmojo_hip.so")
 ARCH = "gfx950"
 # flags of single units, behind the common ones: no packed fp32 VALU forms (v_pk_mul_f32 and kin) in the score / exp chains of the
-# int8 prefill, whose integers must be the golden's, nor in the NSA decode's score, softmax and weight chains
+# int8 prefill, whose integers must be the golden's, nor in the NSA decode's score, softmax and weight chains, nor in the gated
+# delta rule's decay, norm and state-update chains
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"sage_prefill.hip": _NO_PACKED_FP32, "nsa_decode.hip": _NO_PACKED_FP32}
+UNIT_FLAGS = {"sage_prefill.hip": _NO_PACKED_FP32, "nsa_decode.hip": _NO_PACKED_FP32, "gated_delta_rule.hip": _NO_PACKED_FP32}
 
 
 def _hipcc() -> str:
