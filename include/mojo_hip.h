@@ -1018,6 +1018,31 @@ int mojo_hip_nsa_decode(const void* query, const void* key, const void* value, c
                         int64_t num_selected_blocks, int64_t window_size, float softmax_scale, int dtype, int gate_dtype,
                         int64_t num_splits, mojo_stream_t stream);
 
+/* ---- Native sparse attention, prefill (NSA_PREFILL_OPS: MojoPrefillNSA, MojoPagedPrefillNSA).  query / out
+ *      [total_q, heads, dim] dense, packed sequences bounded by cu_q_lens int32 [batch + 1]; gate_proj, dtypes and the branch
+ *      definitions as in the decode block above.  Row r of a sequence with q_len queries and kv_len keys is that decode step on
+ *      the first t_kv keys, t_kv = kv_len - q_len + r + 1 (is_causal) or kv_len; t_kv <= 0 gives zeros; 0 < t_kv <
+ *      compress_ratio takes groups of ONE key (the compressed branch is softmax attention over the t_kv raw keys), where
+ *      decode gives that branch zeros.  Rows behind cu_q_lens[batch] are not written.
+ *      Paged (block_tables != NULL): caches, tables, holes and the cut of a length above page * max_pages as in decode; kv_len
+ *      from cu_total_seq_lens int32 [batch + 1], or q_len when it is NULL.  Contiguous (block_tables == NULL): key / value
+ *      [total_q, heads, dim], key j of sequence b is row cu_q_lens[b] + j; page = total_q, max_pages = 1, cu_total_seq_lens
+ *      NULL.  Nothing behind the last key a row tile sees is read.
+ *      Envelope (MOJO_EUNSUPPORTED otherwise): dim 64 / 128, block_size % compress_ratio == 0, compress_ratio a divisor of 16,
+ *      num_selected_blocks <= 64, paged pages of a multiple of 16 tokens up to 256, strides multiples of 8 elements,
+ *      ceil(page * max_pages / block_size) <= 959 (two fp32 statistics per (row, block) live in LDS: 16 rows per wave, 4, 2 or
+ *      1 waves per workgroup as 120 KiB allow).  One launch, no workspace: the query answers 0, or -1 for a refused
+ *      geometry.  No float atomics: two calls give the same bits.  Tag `nsa_prefill:w<waves>:d<dim>`.                      */
+int64_t mojo_hip_nsa_prefill_workspace_bytes(int64_t total_q, int64_t batch, int64_t heads, int64_t head_dim,
+                                             int64_t kv_capacity, int64_t compress_ratio, int64_t block_size);
+int mojo_hip_nsa_prefill(const void* query, const void* key, const void* value, const void* gate_proj,
+                         const int32_t* cu_q_lens, const int32_t* cu_total_seq_lens, const int32_t* block_tables, void* out,
+                         void* workspace, int64_t workspace_bytes, int64_t total_q, int64_t batch, int64_t heads,
+                         int64_t head_dim, int64_t num_blocks, int64_t page, int64_t max_pages, int64_t table_stride,
+                         int64_t kv_block_stride, int64_t kv_head_stride, int64_t kv_token_stride, int64_t compress_ratio,
+                         int64_t block_size, int64_t num_selected_blocks, int64_t window_size, int is_causal,
+                         float softmax_scale, int dtype, int gate_dtype, mojo_stream_t stream);
+
 /* ---- The gated delta rule (LINEAR_ATTN_OPS: MojoGatedDeltaRule, MojoGatedDeltaRuleUpdateState; core/operators/linear_attention.py):
  *      per (sequence, value head h) an fp32 state S [dk][dv]; the key head is h / (value_heads / key_heads).  With
  *      use_qk_l2norm, q^ = q rsqrt(sum q^2 + 1e-6) and k^ likewise, else q^ = q, k^ = k.  For each token in order:

@@ -6,7 +6,7 @@ the registry ignores them; on a ROCm host they are the first-priority backend.
 from .operators.attention import *  # noqa: F401,F403
 from .operators.kv_int8 import *  # noqa: F401,F403
 from .operators.sage import HIPPagedPrefillSageGQA  # noqa: F401
-from .operators.nsa import HIPDecodeNSA, HIPPagedDecodeNSA  # noqa: F401
+from .operators.nsa import HIPDecodeNSA, HIPPagedDecodeNSA, HIPPagedPrefillNSA, HIPPrefillNSA  # noqa: F401
 from .operators.linear_attention import HIPGatedDeltaRule, HIPGatedDeltaRuleUpdateState  # noqa: F401
 from .operators.streaming import *  # noqa: F401,F403
 from .operators.convolution import HIPCausalConv1d, HIPCausalConv1dUpdateState  # noqa: F401

@@ -156,6 +156,8 @@ SIGNATURES = {
     "mojo_hip_paged_prefill_sage_gqa": (c_int, [_P] * 10 + [_I] * 14 + [c_float, c_int, _P]),
     "mojo_hip_nsa_decode_workspace_bytes": (c_int64, [_I] * 7),
     "mojo_hip_nsa_decode": (c_int, [_P] * 8 + [_I] * 15 + [c_float, c_int, c_int, _I, _P]),
+    "mojo_hip_nsa_prefill_workspace_bytes": (c_int64, [_I] * 7),
+    "mojo_hip_nsa_prefill": (c_int, [_P] * 9 + [_I] * 16 + [c_int, c_float, c_int, c_int, _P]),
     "mojo_hip_gated_delta_rule_dv_slice": (c_int64, [_I] * 4),
     "mojo_hip_gated_delta_rule": (c_int, [_P] * 9 + [c_int] + [_I] * 15 + [c_float, c_int, c_int, c_int, _I, _P]),
     "mojo_hip_gated_delta_rule_update": (c_int, [_P] * 7 + [_I] * 15 + [c_float, c_int, c_int, c_int, _P]),

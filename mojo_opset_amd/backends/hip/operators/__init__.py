@@ -1,7 +1,7 @@
 from .attention import *  # noqa: F401,F403
 from .kv_int8 import *  # noqa: F401,F403
 from .sage import HIPPagedPrefillSageGQA  # noqa: F401
-from .nsa import HIPDecodeNSA, HIPPagedDecodeNSA  # noqa: F401
+from .nsa import HIPDecodeNSA, HIPPagedDecodeNSA, HIPPagedPrefillNSA, HIPPrefillNSA  # noqa: F401
 from .linear_attention import HIPGatedDeltaRule, HIPGatedDeltaRuleUpdateState  # noqa: F401
 from .convolution import HIPCausalConv1d, HIPCausalConv1dUpdateState  # noqa: F401
 from .embedding import (HIPEmbedding, HIPNF4DequantEmbedding, HIPOverEncoding, HIPOverEncodingNGram,  # noqa: F401

@@ -1,7 +1,7 @@
 from .activation import MojoGelu, MojoSilu, MojoSwiGLU
 from .attention import (MojoDecodeNSA, MojoPagedDecodeGQA, MojoPagedDecodeGQAWithKVDequant, MojoPagedDecodeNstepSWA,
                         MojoPagedDecodeNstepSWAWithKVDequant, MojoPagedDecodeNSA, MojoPagedDecodeSWA, MojoPagedDecodeSWAWithKVDequant,
-                        MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillSageGQA,
+                        MojoPagedPrefillGQA, MojoPagedPrefillGQAWithKVDequant, MojoPagedPrefillNSA, MojoPagedPrefillSageGQA, MojoPrefillNSA,
                         MojoPagedPrefillSWA, MojoPagedPrefillSWAWithKVDequant, MojoPackedSdpa, MojoSdpa,
                         MojoSWA)
 from .compute_with_comm import MojoAllGatherGemm, MojoGemmAll2All, MojoGemmAllReduce, MojoGemmReduceScatter
@@ -83,8 +83,11 @@ SHORT_CONV_OPS = ("MojoCausalConv1dUpdateState", "MojoCausalConv1d")
 SAGE_ATTN_OPS = ("MojoPagedPrefillSageGQA",)
 # native sparse attention, decode: the compressed, selected and window branches of one step blended by a per-head gate, over
 # contiguous K/V and over a paged cache.  A set of its own likewise (golden: the core classes' own `forward`, checked against
-# tests/nsa_golden.py); the prefill pair of the reference is not built
+# tests/nsa_golden.py)
 NSA_ATTN_OPS = ("MojoDecodeNSA", "MojoPagedDecodeNSA")
+# native sparse attention, prefill: every packed query row is the decode step on its own causal prefix, over contiguous K/V and
+# over a paged cache (golden: the core classes' own `forward`, checked against tests/nsa_prefill_golden.py)
+NSA_PREFILL_OPS = ("MojoPrefillNSA", "MojoPagedPrefillNSA")
 # the gated delta rule, the mixer behind SHORT_CONV_OPS in a GatedDeltaNet layer (Qwen3-Next, the FLA family): a linear
 # recurrence over an fp32 state per (sequence, value head), as a chunked prefill and a 1..8-token state update.  The reference
 # has no class for either.  A set of its own likewise (golden: the core classes' own `forward`, checked against

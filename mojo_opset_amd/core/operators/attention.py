@@ -444,6 +444,87 @@ class MojoPagedDecodeNSA(_NSADecodeBase, MojoOperator):
         return out
 
 
+class _NSAPrefillBase(_NSADecodeBase):
+    """Per-row golden of the native-sparse-attention prefill pair (`NSA_PREFILL_OPS`;
+    `mojo_opset/experimental/operators/attention.py:1488-1638`).  Row ``t`` of a sequence with ``q_len`` queries and ``kv_len``
+    keys sees the first ``t_kv`` keys, ``t_kv = kv_len - q_len + t + 1`` when ``is_causal`` and ``kv_len`` otherwise (unlike
+    decode, ``is_causal`` matters), and its result is the decode step of `_NSADecodeBase` on them.  Two exceptions: a row with
+    ``t_kv <= 0`` gives zeros, and a row with ``0 < t_kv < compress_ratio`` IS NOT COMPRESSED (the reference's rule): its
+    compressed branch is softmax attention over the ``t_kv`` raw keys, where decode gives that branch zeros at such a length.
+    Roundings, ties and tolerances as in `_NSADecodeBase`."""
+
+    def _prefill_seq(self, out, q, k, v, scale):
+        """``out [q_len,H,D]`` (zeros) of one sequence: ``q [q_len,H,D]``, ``k`` / ``v [kv_len,H,D]``."""
+        q_len, kv_len, cr = q.shape[0], k.shape[0], self.compress_ratio
+        for t in range(q_len):
+            t_kv = kv_len - q_len + t + 1 if self.is_causal else kv_len
+            if t_kv >= cr:
+                out[t] = self._decode_one(q[t], k[:t_kv], v[:t_kv], scale)
+            elif t_kv > 0:         # one block, taken; the window is the context: three times the same attention unless ws < t_kv
+                g = torch.sigmoid(torch.einsum("hd,hdc->hc", q[t], self.gate_proj.to(q.dtype)))
+                full = self._attend(q[t], k[:t_kv], v[:t_kv], scale)
+                start = max(0, t_kv - self.window_size)
+                sel = full if self.num_selected_blocks > 0 else torch.zeros_like(full)
+                out[t] = g[:, 0:1] * full + g[:, 1:2] * sel + g[:, 2:3] * self._attend(q[t], k[start:t_kv], v[start:t_kv], scale)
+
+
+class MojoPrefillNSA(_NSAPrefillBase, MojoOperator):
+    """Native sparse attention for packed var-len queries over contiguous K/V, ``kv_len = q_len`` (see `_NSAPrefillBase`).
+
+    forward(query [T,H,D], key [T,H,D], value [T,H,D], cu_q_lens [B+1] i32, softmax_scale=None) -> [T,H,D]"""
+
+    def __init__(self, num_heads, head_dim, compress_ratio=4, num_selected_blocks=16, block_size=64, window_size=512,
+                 is_causal=True, **kwargs):
+        super().__init__(**kwargs)
+        self._init_nsa(num_heads, head_dim, compress_ratio, num_selected_blocks, block_size, window_size, is_causal)
+
+    def forward(self, query, key, value, cu_q_lens, softmax_scale: Optional[float] = None):
+        assert cu_q_lens.dtype == torch.int32
+        scale = query.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale
+        out, cu = torch.zeros_like(query), cu_q_lens.tolist()
+        for s, e in zip(cu[:-1], cu[1:]):
+            self._prefill_seq(out[s:e], query[s:e], key[s:e], value[s:e], scale)
+        return out
+
+
+class MojoPagedPrefillNSA(_NSAPrefillBase, MojoOperator):
+    """Native sparse attention for packed var-len queries over a paged KV cache (see `_NSAPrefillBase`).  The cache page and
+    the selection block are independent.  Every key from the first negative or out-of-pool page id on is a zero K / V
+    row; a negative FIRST page id of a sequence with keys raises ``ValueError``.
+
+    forward(query [T,H,D], key_cache / value_cache [N,H,page,D], cu_q_lens [B+1] i32, block_tables [B,nb] i32,
+            softmax_scale=None, cu_total_seq_lens=None ([B+1] i32; None: kv_len = q_len)) -> [T,H,D]"""
+
+    def __init__(self, num_heads, head_dim, compress_ratio=4, num_selected_blocks=16, block_size=64, window_size=512,
+                 is_causal=True, **kwargs):
+        super().__init__(**kwargs)
+        self._init_nsa(num_heads, head_dim, compress_ratio, num_selected_blocks, block_size, window_size, is_causal)
+
+    def forward(self, query, key_cache, value_cache, cu_q_lens, block_tables, softmax_scale: Optional[float] = None,
+                cu_total_seq_lens: Optional[torch.Tensor] = None):
+        assert_paged_prefill_contract(cu_q_lens, block_tables, cu_total_seq_lens)
+        n_blocks, heads, page, dim = key_cache.shape
+        scale = dim ** -0.5 if softmax_scale is None else softmax_scale
+        out, cu = torch.zeros_like(query), cu_q_lens.tolist()
+        cu_kv = cu if cu_total_seq_lens is None else cu_total_seq_lens.tolist()
+        for i, (s, e) in enumerate(zip(cu[:-1], cu[1:])):
+            sl = min(cu_kv[i + 1] - cu_kv[i], page * block_tables.shape[1])
+            if e <= s or sl <= 0:
+                continue
+            ids = block_tables[i, :(sl + page - 1) // page].tolist()
+            if ids[0] < 0:
+                raise ValueError("Paged decode requires a valid block table for rows with kv lens > 0.")
+            bad = [j for j, n in enumerate(ids) if n < 0 or n >= n_blocks]
+            ids = ids[:bad[0]] if bad else ids
+            k = torch.zeros(len(ids) * page + sl, heads, dim, dtype=query.dtype, device=query.device)
+            v = torch.zeros_like(k)
+            if ids:
+                k[:len(ids) * page] = key_cache[ids].transpose(1, 2).reshape(-1, heads, dim)
+                v[:len(ids) * page] = value_cache[ids].transpose(1, 2).reshape(-1, heads, dim)
+            self._prefill_seq(out[s:e], query[s:e], k[:sl], v[:sl], scale)
+        return out
+
+
 class _PagedSWAKVDequantBase:
     """Constructor of the windowed int8-cache pair (`mojo_opset/experimental/operators/attention.py:806-848`, :988-1030):
     the attributes of `_PagedSWABase` and of `_PagedGQAKVDequantBase` together — ``is_causal``, ``gqa_layout``,

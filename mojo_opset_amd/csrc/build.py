@@ -25,7 +25,8 @@ ARCH = "gfx950"
 # int8 prefill, whose integers must be the golden's, nor in the NSA decode's score, softmax and weight chains, nor in the gated
 # delta rule's decay, norm and state-update chains
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"sage_prefill.hip": _NO_PACKED_FP32, "nsa_decode.hip": _NO_PACKED_FP32, "gated_delta_rule.hip": _NO_PACKED_FP32}
+UNIT_FLAGS = {"sage_prefill.hip": _NO_PACKED_FP32, "nsa_decode.hip": _NO_PACKED_FP32, "nsa_prefill.hip": _NO_PACKED_FP32,
+              "gated_delta_rule.hip": _NO_PACKED_FP32}
 
 
 def _hipcc() -> str:
