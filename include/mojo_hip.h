@@ -1081,6 +1081,28 @@ int mojo_hip_gated_delta_rule_update(const void* q, const void* k, const void* v
                                      int64_t v_token_stride, int64_t v_head_stride, float scale, int use_qk_l2norm, int gate_dtype,
                                      int dtype, mojo_stream_t stream);
 
+/* ---- MXFP4 (MXFP4_OPS: MojoMXFP4Quant, MojoMXFP4Gemm; core/operators/mxfp4.py): OCP microscaling fp4.  A row of k elements,
+ *      k % 32 == 0, is k / 2 data bytes (element 2j in bits 0-3 of byte j, element 2j + 1 in bits 4-7; a nibble is a sign and
+ *      an E2M1 code: 0, 0.5, 1, 1.5, 2, 3, 4, 6) and k / 32 scale bytes (E8M0: byte e means 2^(e - 127); 0xFF is NaN and outside
+ *      the product's contract).  All tensors dense, data 16-byte aligned.  No atomics, no host synchronisation,
+ *      graph-capturable; two calls give the same bits.
+ *      mojo_hip_mxfp4_quant: x [m][k] bf16 / fp16 with `row_stride` elements between rows (a multiple of 8, x 16-byte aligned)
+ *      -> data [m][k / 2], scale [m][k / 32], per block of 32: e = clamp(floor(log2 amax) - 2, -127, 127), scale byte e + 127
+ *      (amax == 0: byte 0), elements x 2^-e rounded to the nearest E2M1 value with ties to the even code, saturated at +-6, the
+ *      sign kept (also of zero); a block holding Inf or NaN gets the byte 0xFF and zero nibbles.  Tag `mxfp4_quant`.
+ *      mojo_hip_mxfp4_gemm: out [m][n] (fp32 / fp16 / bf16) = dequant(input [m][k / 2], input_scale [m][k / 32]) x
+ *      dequant(weight [n][k / 2], weight_scale [n][k / 32])^T on v_mfma_scale_f32_16x16x128_f8f6f4 with fp4 operands, both
+ *      block scales applied by the instruction, fp32 accumulation, one rounding.  n % 16 == 0 (else MOJO_EUNSUPPORTED), any
+ *      m >= 1.  The form is planned from the shapes alone: m <= 32 the weight-streaming skinny form with a split over K whose
+ *      partial sums are merged in split order through `workspace` (mojo_hip_mxfp4_gemm_workspace_bytes, 16-byte aligned), else
+ *      the 128 x 128 tile form.  Tags `mxfp4_gemm:tile128`, `mxfp4_gemm:skinny:mg<1|2>:splitk<S>`. */
+int mojo_hip_mxfp4_quant(const void* x, void* data, void* scale, int64_t m, int64_t k, int64_t row_stride, int dtype,
+                         mojo_stream_t stream);
+int64_t mojo_hip_mxfp4_gemm_workspace_bytes(int64_t m, int64_t k, int64_t n);
+int mojo_hip_mxfp4_gemm(const void* input, const void* input_scale, const void* weight, const void* weight_scale, void* out,
+                        int64_t m, int64_t k, int64_t n, int out_dtype, void* workspace, int64_t workspace_bytes,
+                        mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,9 @@ SIGNATURES = {
     "mojo_hip_gated_delta_rule_dv_slice": (c_int64, [_I] * 4),
     "mojo_hip_gated_delta_rule": (c_int, [_P] * 9 + [c_int] + [_I] * 15 + [c_float, c_int, c_int, c_int, _I, _P]),
     "mojo_hip_gated_delta_rule_update": (c_int, [_P] * 7 + [_I] * 15 + [c_float, c_int, c_int, c_int, _P]),
+    "mojo_hip_mxfp4_quant": (c_int, [_P, _P, _P, _I, _I, _I, c_int, _P]),
+    "mojo_hip_mxfp4_gemm_workspace_bytes": (c_int64, [_I, _I, _I]),
+    "mojo_hip_mxfp4_gemm": (c_int, [_P] * 5 + [_I, _I, _I, c_int, _P, _I, _P]),
 }
 
 _lock = threading.Lock()

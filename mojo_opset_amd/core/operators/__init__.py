@@ -13,6 +13,7 @@ from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStore
                        build_paged_kv_chunk_metadata)
 from .mla import MojoPagedDecodeMLA, MojoPagedPrefillMLA
 from .mlp import MojoSwiGLUMLP
+from .mxfp4 import MojoMXFP4Gemm, MojoMXFP4Quant
 from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts, MojoQuantMoE
 from .over_encoding import MojoNF4DequantEmbedding, MojoOverEncoding, MojoOverEncodingNGram
 from .normalization import (MojoLayerNorm, MojoResidualAddLayerNorm, MojoResidualAddRMSNorm, MojoRMSNorm,
@@ -93,3 +94,7 @@ NSA_PREFILL_OPS = ("MojoPrefillNSA", "MojoPagedPrefillNSA")
 # has no class for either.  A set of its own likewise (golden: the core classes' own `forward`, checked against
 # tests/gated_delta_golden.py)
 LINEAR_ATTN_OPS = ("MojoGatedDeltaRule", "MojoGatedDeltaRuleUpdateState")
+# OCP microscaling fp4 (E2M1 elements, one E8M0 scale per 32 elements along K): the row quantiser and the block-scaled a4w4
+# product on CDNA4's scaled matrix instruction.  The reference has no class for either.  A set of its own likewise (golden: the
+# core classes' own `forward`, checked against tests/mxfp4_golden.py)
+MXFP4_OPS = ("MojoMXFP4Quant", "MojoMXFP4Gemm")

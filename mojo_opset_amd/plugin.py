@@ -56,7 +56,8 @@ def rebase_hip_backend(reference, platforms: Optional[Sequence[str]] = None) -> 
     for name in (list(mine.__all__) + list(mine.BEYOND_SURVEY_OPS) + list(mine.NSTEP_OPS) + list(mine.NSTEP_KV_INT8_OPS) +
                  list(mine.PACKED_ATTN_OPS) + list(mine.FULL_ATTN_OPS) + list(mine.QUANT_DENSE_OPS) + list(mine.DIT_BLOCK_OPS) +
                  list(mine.VISION_TOWER_OPS) + list(mine.EMBEDDING_OPS) + list(mine.SHORT_CONV_OPS) +
-                 list(mine.SAGE_ATTN_OPS) + list(mine.NSA_ATTN_OPS) + list(mine.NSA_PREFILL_OPS) + list(mine.LINEAR_ATTN_OPS)):
+                 list(mine.SAGE_ATTN_OPS) + list(mine.NSA_ATTN_OPS) + list(mine.NSA_PREFILL_OPS) + list(mine.LINEAR_ATTN_OPS) +
+                 list(mine.MXFP4_OPS)):
         if not name.startswith("Mojo") or name in ("MojoOperator", "MojoBackendRegistry"):
             continue
         hip_cls = getattr(hip_pkg, "HIP" + name[4:], None)
