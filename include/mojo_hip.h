@@ -1103,6 +1103,28 @@ int mojo_hip_mxfp4_gemm(const void* input, const void* input_scale, const void* 
                         int64_t m, int64_t k, int64_t n, int out_dtype, void* workspace, int64_t workspace_bytes,
                         mojo_stream_t stream);
 
+/* ---- MXFP4 MoE experts (MXFP4_MOE_OPS: MojoMXFP4GroupGemm, MojoMXFP4SwiGLUQuant, MojoMXFP4Experts): the format, instruction
+ *      and alignment rules above.  No atomics, no host synchronisation, graph-capturable; two calls give the same bits.
+ *      mojo_hip_mxfp4_group_gemm: `group_list` int32 [num_groups] ROW COUNTS ON THE DEVICE (negative: 0; the running sum is cut
+ *      at m_total); group g multiplies its rows by weight [g][n][k / 2], weight_scale [g][n][k / 32].  n % 16 == 0,
+ *      num_groups <= 1024.  Rows [sum, m_total) of every output are written as zeros.  swiglu_quant == 0: out [m_total][n] in
+ *      out_dtype, out_scale unused (may be NULL).  swiglu_quant != 0: n = 2 I with I % 32 == 0 (else MOJO_EINVAL), weight rows
+ *      [gate | up]; out is data [m_total][I / 2], out_scale [m_total][I / 32] = quantise(silu(gate) * up) by the rule of
+ *      mojo_hip_mxfp4_quant, of the unrounded fp32 products, silu and the multiply in fp32 (x / (1 + exp(-x))); out_dtype is
+ *      ignored.  A plan kernel prefix-sums the counts on the device and deals every group on its own: more than 32 rows to
+ *      128-row tiles, 1..32 rows to the weight-streaming skinny form, whose split over K (planned from the shapes) is merged in
+ *      split order through `workspace` (mojo_hip_mxfp4_group_gemm_workspace_bytes, 16-byte aligned).  Tags
+ *      `mxfp4_group_gemm:<plain|swiglu>:splitk<S>`.
+ *      mojo_hip_mxfp4_swiglu_quant: the same stage over a stored x [m][2 inter] (fp32 / bf16 / fp16, `row_stride` elements
+ *      between rows, a multiple of 4; x 16-byte aligned) -> data [m][inter / 2], scale [m][inter / 32].  Tag
+ *      `mxfp4_swiglu_quant`. */
+int64_t mojo_hip_mxfp4_group_gemm_workspace_bytes(int64_t m_total, int64_t k, int64_t n, int64_t num_groups, int swiglu_quant);
+int mojo_hip_mxfp4_group_gemm(const void* input, const void* input_scale, const void* weight, const void* weight_scale, void* out,
+                              void* out_scale, const void* group_list, int64_t m_total, int64_t k, int64_t n, int64_t num_groups,
+                              int swiglu_quant, int out_dtype, void* workspace, int64_t workspace_bytes, mojo_stream_t stream);
+int mojo_hip_mxfp4_swiglu_quant(const void* x, void* data, void* scale, int64_t m, int64_t inter, int64_t row_stride, int dtype,
+                                mojo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,17 +28,19 @@ checked against the fp64 model of ``tests/nsa_golden.py``; ``NSA_PREFILL_OPS`` i
 its own causal prefix), checked against ``tests/nsa_prefill_golden.py``.  ``LINEAR_ATTN_OPS`` (the gated delta rule: chunked prefill and state update)
 is one more; its golden is the core classes' ``forward``, checked against the fp64 model of ``tests/gated_delta_golden.py``.
 ``MXFP4_OPS`` (OCP microscaling fp4: the row quantiser and the block-scaled a4w4 product) is one more; its golden is the core
-classes' ``forward``, checked against the fp64 model of ``tests/mxfp4_golden.py``.
+classes' ``forward``, checked against the fp64 model of ``tests/mxfp4_golden.py``; ``MXFP4_MOE_OPS`` is its MoE form (the grouped
+product, the SwiGLU re-quantiser between the two expert GEMMs, the experts operator), checked against the same model.
 """
 from .core import *  # noqa: F401,F403
 from .core import __all__ as _core_all
 from .core import (BEYOND_SURVEY_OPS, EXTENDED_OPS, KV_INT8_OPS, KV_INT8_SWA_OPS, NSTEP_KV_INT8_OPS, NSTEP_OPS,  # noqa: F401
                    DIT_BLOCK_OPS, FULL_ATTN_OPS, PACKED_ATTN_OPS, QUANT_DENSE_OPS, QUANT_MOE_OPS, SAMPLING_OPS, VISION_TOWER_OPS,
-                   EMBEDDING_OPS, SHORT_CONV_OPS, SAGE_ATTN_OPS, NSA_ATTN_OPS, NSA_PREFILL_OPS, LINEAR_ATTN_OPS, MXFP4_OPS)
+                   EMBEDDING_OPS, SHORT_CONV_OPS, SAGE_ATTN_OPS, NSA_ATTN_OPS, NSA_PREFILL_OPS, LINEAR_ATTN_OPS, MXFP4_OPS,
+                   MXFP4_MOE_OPS)
 from . import core as _core
 from . import backends  # noqa: F401  (registers HIP<Op> classes)
 from .paged_cache import PagedDummyCache  # noqa: E402  device-side block allocator (SURVEY §8 f4)
 
 __all__ = list(_core_all) + ["PagedDummyCache"]
-globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS + NSTEP_OPS + NSTEP_KV_INT8_OPS + PACKED_ATTN_OPS + FULL_ATTN_OPS + QUANT_DENSE_OPS + DIT_BLOCK_OPS + VISION_TOWER_OPS + EMBEDDING_OPS + SHORT_CONV_OPS + SAGE_ATTN_OPS + NSA_ATTN_OPS + NSA_PREFILL_OPS + LINEAR_ATTN_OPS + MXFP4_OPS})   # beyond §8: not in __all__
+globals().update({_name: getattr(_core, _name) for _name in BEYOND_SURVEY_OPS + NSTEP_OPS + NSTEP_KV_INT8_OPS + PACKED_ATTN_OPS + FULL_ATTN_OPS + QUANT_DENSE_OPS + DIT_BLOCK_OPS + VISION_TOWER_OPS + EMBEDDING_OPS + SHORT_CONV_OPS + SAGE_ATTN_OPS + NSA_ATTN_OPS + NSA_PREFILL_OPS + LINEAR_ATTN_OPS + MXFP4_OPS + MXFP4_MOE_OPS})   # beyond §8: not in __all__
 __version__ = "0.1.0"

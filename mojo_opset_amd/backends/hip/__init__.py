@@ -8,7 +8,7 @@ from .operators.kv_int8 import *  # noqa: F401,F403
 from .operators.sage import HIPPagedPrefillSageGQA  # noqa: F401
 from .operators.nsa import HIPDecodeNSA, HIPPagedDecodeNSA, HIPPagedPrefillNSA, HIPPrefillNSA  # noqa: F401
 from .operators.linear_attention import HIPGatedDeltaRule, HIPGatedDeltaRuleUpdateState  # noqa: F401
-from .operators.mxfp4 import HIPMXFP4Gemm, HIPMXFP4Quant  # noqa: F401
+from .operators.mxfp4 import HIPMXFP4Experts, HIPMXFP4Gemm, HIPMXFP4GroupGemm, HIPMXFP4Quant, HIPMXFP4SwiGLUQuant  # noqa: F401
 from .operators.streaming import *  # noqa: F401,F403
 from .operators.convolution import HIPCausalConv1d, HIPCausalConv1dUpdateState  # noqa: F401
 from .operators.embedding import (HIPEmbedding, HIPNF4DequantEmbedding, HIPOverEncoding, HIPOverEncodingNGram,  # noqa: F401

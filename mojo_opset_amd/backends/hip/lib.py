@@ -164,6 +164,9 @@ SIGNATURES = {
     "mojo_hip_mxfp4_quant": (c_int, [_P, _P, _P, _I, _I, _I, c_int, _P]),
     "mojo_hip_mxfp4_gemm_workspace_bytes": (c_int64, [_I, _I, _I]),
     "mojo_hip_mxfp4_gemm": (c_int, [_P] * 5 + [_I, _I, _I, c_int, _P, _I, _P]),
+    "mojo_hip_mxfp4_group_gemm_workspace_bytes": (c_int64, [_I, _I, _I, _I, c_int]),
+    "mojo_hip_mxfp4_group_gemm": (c_int, [_P] * 7 + [_I, _I, _I, _I, c_int, c_int, _P, _I, _P]),
+    "mojo_hip_mxfp4_swiglu_quant": (c_int, [_P, _P, _P, _I, _I, _I, c_int, _P]),
 }
 
 _lock = threading.Lock()

@@ -13,7 +13,7 @@ from .kv_cache import (MojoStorePagedKVCache, MojoStorePagedKVCacheC8, MojoStore
                        build_paged_kv_chunk_metadata)
 from .mla import MojoPagedDecodeMLA, MojoPagedPrefillMLA
 from .mlp import MojoSwiGLUMLP
-from .mxfp4 import MojoMXFP4Gemm, MojoMXFP4Quant
+from .mxfp4 import MojoMXFP4Experts, MojoMXFP4Gemm, MojoMXFP4GroupGemm, MojoMXFP4Quant, MojoMXFP4SwiGLUQuant
 from .moe import MojoExperts, MojoMoE, MojoMoECombine, MojoMoEDispatch, MojoMoEGating, MojoQuantExperts, MojoQuantMoE
 from .over_encoding import MojoNF4DequantEmbedding, MojoOverEncoding, MojoOverEncodingNGram
 from .normalization import (MojoLayerNorm, MojoResidualAddLayerNorm, MojoResidualAddRMSNorm, MojoRMSNorm,
@@ -98,3 +98,8 @@ LINEAR_ATTN_OPS = ("MojoGatedDeltaRule", "MojoGatedDeltaRuleUpdateState")
 # product on CDNA4's scaled matrix instruction.  The reference has no class for either.  A set of its own likewise (golden: the
 # core classes' own `forward`, checked against tests/mxfp4_golden.py)
 MXFP4_OPS = ("MojoMXFP4Quant", "MojoMXFP4Gemm")
+# MXFP4 as the storage format of MoE expert weights: the grouped a4w4 product over ragged row groups (also with the fc1 -> fc2
+# stage, ``mxfp4_quantize(silu(gate) * up)``, fused into its epilogue), that stage as a stand-alone op, and the experts operator
+# with the arguments of `MojoExperts`.  A set of its own likewise (golden: the core classes' own `forward`, checked against
+# tests/mxfp4_golden.py)
+MXFP4_MOE_OPS = ("MojoMXFP4GroupGemm", "MojoMXFP4SwiGLUQuant", "MojoMXFP4Experts")

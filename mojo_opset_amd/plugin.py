@@ -57,7 +57,7 @@ def rebase_hip_backend(reference, platforms: Optional[Sequence[str]] = None) -> 
                  list(mine.PACKED_ATTN_OPS) + list(mine.FULL_ATTN_OPS) + list(mine.QUANT_DENSE_OPS) + list(mine.DIT_BLOCK_OPS) +
                  list(mine.VISION_TOWER_OPS) + list(mine.EMBEDDING_OPS) + list(mine.SHORT_CONV_OPS) +
                  list(mine.SAGE_ATTN_OPS) + list(mine.NSA_ATTN_OPS) + list(mine.NSA_PREFILL_OPS) + list(mine.LINEAR_ATTN_OPS) +
-                 list(mine.MXFP4_OPS)):
+                 list(mine.MXFP4_OPS) + list(mine.MXFP4_MOE_OPS)):
         if not name.startswith("Mojo") or name in ("MojoOperator", "MojoBackendRegistry"):
             continue
         hip_cls = getattr(hip_pkg, "HIP" + name[4:], None)
